@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — probe-tuples/s of the radix join on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 N = 1  headline workload = BASELINE.json configs[2] (the largest single-GPU configuration):
        single JoinNode, 1B ⋈ 1B INT32 keys, Zipf-0.9 probe keys, one INT64 payload column per
@@ -9,15 +9,20 @@ N = 1  headline workload = BASELINE.json configs[2] (the largest single-GPU conf
        One step = one rj_execute_resident() of that plan: Page-packed inputs already in HBM,
        page decode + histograms + 2 radix scatters per side + build/probe + Page-encoded result
        left in HBM, including the result-size read-back.  W untimed warmup steps, then exactly K
-       timed steps.  After the timed loop the LAST result is verified on the device in closed
-       form (every probe row exactly once, with its own key, next to the build row holding that
-       key: pyrj/workloads.py::verify_pk_fk) — a wrong join fails the bench.
-       The same JSON line carries, as extra fields, `configs` (BASELINE config 2 = 100M ⋈ 100M
-       uniform, and 1B ⋈ 1B uniform, each timed and verified the same way) and `plan_ms`
-       (end-to-end Contest::execute semantics, host pages in / host pages out, for the JOB plan
-       trees job/1a, job/13d and job/10c — the last one a 1M-row result with two VARCHAR columns —
-       over synthetic IMDB-shaped inputs: what the reference harness times,
-       tests/read_sql.cpp:1234-1236).
+       timed steps.  A plain run does only that (plus the result-size check of the last step)
+       and prints the JSON line.
+--full also verifies the LAST result on the device in closed form (every probe row exactly
+       once, with its own key, next to the build row holding that key:
+       pyrj/workloads.py::verify_pk_fk) — a wrong join fails the bench — and adds the extra
+       fields `configs` (BASELINE config 2 = 100M ⋈ 100M uniform, and 1B ⋈ 1B uniform, each
+       timed and verified the same way), `plan_ms` (end-to-end Contest::execute semantics, host
+       pages in / host pages out, for the JOB plan trees job/1a, job/13d and job/10c — the last
+       one a 1M-row result with two VARCHAR columns — over synthetic IMDB-shaped inputs: what
+       the reference harness times, tests/read_sql.cpp:1234-1236), `ingest` and `cpu_baseline`.
+       --no-verify, --no-extras and --no-cpu-baseline leave parts of that out again.
+--dump-outputs DIR  (N = 1) after the timed steps, writes the join result of the last step as
+       float64 .npy files under DIR (see dump_outputs()); inputs are seeded, so two builds run
+       with the same arguments can be compared output for output.
 N > 1  one process per GPU (torch.distributed, backend nccl = RCCL).  STRONG scaling: the same
        1B ⋈ 1B job, each rank holding 1/N of the rows of both relations; the join shards by key
        hash with one exchange step.  value = 1B probe tuples per
@@ -26,8 +31,9 @@ N > 1  one process per GPU (torch.distributed, backend nccl = RCCL).  STRONG sca
 `roofline` = the kernel with the longest average launch (the build/probe kernel): algorithmic
 bytes per launch (SURVEY.md §8d) over its HIP-event duration measured on the launch stream;
 `roofline.kernels` lists the same for every hot kernel and `roofline.min_frac_kernel` names the
-one furthest below the roofline.  `cpu_baseline` (N = 1) = the CPU oracle — a port of the
-reference algorithm — on a bounded sample of the headline workload's shape.
+one furthest below the roofline (all from the timed steps themselves).  `cpu_baseline` (N = 1,
+--full) = the CPU oracle — a port of the reference algorithm — on a bounded sample of the
+headline workload's shape.
 """
 import argparse
 import json
@@ -135,9 +141,66 @@ def roofline(stats, rows_build, rows_probe, steps_profiled, payload_bytes, workl
     }
 
 
-def run_single(name, device, dev_index, steps, warmup, verify=True, rows=None):
+DUMP_SAMPLE_ROWS = 1 << 20  # probe rows in the --dump-outputs sample (5 float64 arrays: 40 MB)
+DUMP_SEED = 20240613
+
+
+def dump_outputs(res, rel, out_dir, sample_rows=DUMP_SAMPLE_ROWS, chunk_pages=1 << 15):
+    """The join result `res` (resident, columns key / build payload / probe payload) as float64
+    .npy files under out_dir.  A join result is a set of rows: the order the device writes them
+    in carries no meaning, so rows are named by the probe row they came from (its payload is
+    row * PAY_MUL, or row for INT32 payloads).  Written:
+      num_rows.npy       [1]  rows of the whole result
+      probe_row.npy      [m]  a fixed, seeded sample of m = min(n, sample_rows) probe rows, ascending
+      matches.npy        [m]  output rows that carry each sampled probe row (1 for a correct join)
+      key.npy, build_payload.npy, probe_payload.npy  [m]  the output row of each sampled probe
+                              row (NaN where it has none; keys and payloads are exact in float64)"""
+    n, n_out = rel.n, res.num_rows
+    m = min(n, sample_rows)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    dev = rel.sk.device
+    slot = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    slot[torch.from_numpy(rows).to(dev)] = torch.arange(m, dtype=torch.int32, device=dev)
+    mul = wl.PAY_MUL if rel.payload64 else 1
+    rf = (wl.ROWS32,) + ((wl.ROWS64,) * 2 if rel.payload64 else (wl.ROWS32,) * 2)
+    vals = torch.zeros((3, m), dtype=torch.int64, device=dev)
+    count = torch.zeros(m, dtype=torch.int64, device=dev)
+    if n_out:
+        cols = [wl.result_column(res, c, n_out)[0] for c in range(3)]
+        step = chunk_pages * wl.ROWS32
+        for r0 in range(0, n_out, step):
+            r1 = min(n_out, r0 + step)
+
+            def rows_of(col2d, f):
+                p0, p1 = r0 // f, (r1 + f - 1) // f
+                return col2d[p0:p1].reshape(-1)[r0 - p0 * f : r1 - p0 * f].to(torch.int64)
+
+            chunk = [rows_of(cols[c], rf[c]) for c in range(3)]
+            prow = chunk[2] // mul
+            ok = (chunk[2] % mul == 0) & (prow >= 0) & (prow < n)
+            s = torch.full_like(prow, -1)
+            s[ok] = slot[prow[ok]].to(torch.int64)
+            hit = s >= 0
+            s = s[hit]
+            for c in range(3):
+                vals[c, s] = chunk[c][hit]
+            count.index_add_(0, s, torch.ones_like(s))
+            del chunk, prow, ok, s, hit
+    del slot
+    count_h = count.cpu().numpy().astype(np.float64)
+    vals_h = vals.cpu().numpy().astype(np.float64)
+    vals_h[:, count_h == 0] = np.nan
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"num_rows": np.array([n_out], dtype=np.float64), "probe_row": rows.astype(np.float64), "matches": count_h,
+              "key": vals_h[0], "build_payload": vals_h[1], "probe_payload": vals_h[2]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
+def run_single(name, device, dev_index, steps, warmup, verify=True, rows=None, dump_dir=None):
     """One workload on one GPU: build it on the device, W warmup + K timed steps, verify the last
-    result in closed form.  Own context, destroyed at the end (releases its HBM cache)."""
+    result in closed form (if `verify`), write it to `dump_dir` (if given).  Own context,
+    destroyed at the end (releases its HBM cache)."""
     ctx = capi.Context(device=dev_index, profile=os.environ.get("RJ_BENCH_PROFILE", "1") != "0")
     rel = wl.make_relations(name, device, rows=rows)
     R = wl.adopt(ctx, [rel.rk, rel.rp])
@@ -176,6 +239,8 @@ def run_single(name, device, dev_index, steps, warmup, verify=True, rows=None):
             digest = wl.verify_pk_fk(last, rel)
         except AssertionError as e:
             raise SystemExit(f"{name}: RESULT VERIFICATION FAILED: {e}")
+    if dump_dir:
+        dump_outputs(last, rel, dump_dir)
     last.free()
     info = ctx.device_info()
     out = {
@@ -394,11 +459,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="config3", choices=sorted(wl.WORKLOADS), help="headline workload at N=1")
     ap.add_argument("--rows", type=int, default=0, help="rows per relation overall (default: the workload's own size)")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the last result in closed form and add `configs`, `plan_ms`, `ingest` and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's join result as float64 .npy files under DIR (N = 1)")
     ap.add_argument("--cpu-sample", type=int, default=40_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra `configs` and `plan_ms` fields")
-    ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra `configs`, `plan_ms` and `ingest` fields")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the closed-form verification")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    verify = args.full and not args.no_verify
+    args.verify = verify  # read by bench_dist
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -409,8 +482,10 @@ def main():
     if args.gpus != world and (distributed or args.gpus > 1):
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch N > 1 as `python -m torch.distributed.run "
                          f"--nnodes=1 --nproc-per-node {args.gpus} --master-addr 127.0.0.1 bench.py --gpus {args.gpus} ...`")
+    if distributed and args.dump_outputs:
+        raise SystemExit("--dump-outputs is supported at --gpus 1 only")
     cpu = None
-    if not distributed and not args.no_cpu_baseline:
+    if args.full and not distributed and not args.no_cpu_baseline:
         # first, while this process has not touched the GPU yet (the workers are forked); it is
         # a reported baseline on the host cores, not part of any timed GPU region
         if torch.cuda.device_count() == 0:
@@ -432,7 +507,8 @@ def main():
 
         return bench_dist.main(args, rank, world, dev_index, device)
 
-    head, info = run_single(args.workload, device, dev_index, args.steps, args.warmup, verify=not args.no_verify, rows=args.rows or None)
+    head, info = run_single(args.workload, device, dev_index, args.steps, args.warmup, verify=verify, rows=args.rows or None,
+                            dump_dir=args.dump_outputs)
     out = {
         "metric": "probe_tuples_per_sec",
         "value": head["value"],
@@ -456,7 +532,7 @@ def main():
         },
         "roofline": head["roofline"],
     }
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # the extras never take the headline line with them: a failure is recorded in its place
         def guarded(fn, *a, **kw):
             try:
@@ -468,7 +544,7 @@ def main():
         for name, st, wu in (("config2", 10, 2), ("uniform1b", 5, 1)):
             if name == args.workload:
                 continue
-            got = guarded(run_single, name, device, dev_index, st, wu, verify=not args.no_verify)
+            got = guarded(run_single, name, device, dev_index, st, wu, verify=verify)
             if isinstance(got, dict):
                 extras[name] = got
                 continue

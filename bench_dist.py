@@ -124,7 +124,7 @@ def main(args, rank, world, dev_index, device):
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
     digest = None
-    if not args.no_verify:
+    if args.verify:  # --full
         try:
             digest = verify_sharded(last, rel, device)
         except AssertionError as e:

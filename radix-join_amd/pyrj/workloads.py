@@ -2,7 +2,8 @@
 join results (no oracle involved: the relations are PK-FK by construction, so every property
 of the result can be recomputed from the inputs).
 
-Shared by bench.py (which verifies the result of its timed loop) and the full-size GPU tests.
+Shared by bench.py (which verifies the result of its timed loop under --full) and the full-size
+GPU tests.
 Workload shapes follow SURVEY.md §8(d):
 
     config2     100 M ⋈ 100 M, INT32 keys (build = permutation, probe = uniform iid), one INT32
@@ -111,11 +112,26 @@ def join_plan(payload=None):
 
 
 # ------------------------------------------------------------------------------- relations
+def _cumsum_reproducible(w: torch.Tensor, row: int = 1 << 15) -> torch.Tensor:
+    """Inclusive prefix sum of a 1-D float tensor with the same bits on every run.  A 1-D
+    torch.cumsum on the device is a single-pass look-back scan whose float additions can happen
+    in another order from run to run; here each row of a 2-D view is scanned by itself (fixed
+    order) and the row totals are accumulated in sequence on the host."""
+    n = w.numel()
+    rows = max(2, (n + row - 1) // row)  # >= 2 rows: a one-row view would take the 1-D path again
+    x = torch.zeros(rows * row, dtype=w.dtype, device=w.device)
+    x[:n] = w
+    x = torch.cumsum(x.view(rows, row), 1)
+    off = torch.from_numpy(x[:, -1].cpu().numpy().cumsum()).to(w.device)
+    x[1:] += off[:-1, None]
+    return x.view(-1)[:n]
+
+
 def zipf_keys(n_keys, n, s, device, gen):
     """n draws of a Zipf(s) rank over [0, n_keys), scattered through a fixed bijection so that hot
     keys are not numerically adjacent (skew on the probe side only)."""
     w = torch.arange(1, n_keys + 1, device=device, dtype=torch.float64).pow_(-s)
-    cdf = torch.cumsum(w, 0)
+    cdf = _cumsum_reproducible(w)
     del w
     cdf /= cdf[-1].clone()
     out = torch.empty(n, device=device, dtype=torch.int64)

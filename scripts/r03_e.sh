@@ -4,10 +4,11 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 python -m pytest tests/test_gpu_wide_carry.py -x -q > gpurun_out/r03_e_tests.log 2>&1; tail -3 gpurun_out/r03_e_tests.log
-timeout -k 10 500 python bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/r03_e_bench.json 2> gpurun_out/r03_e_bench.err || exit 1
-python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r03_e_bench.json").readlines()[-1])
+out=${OUT_DIR:-bench_out}; mkdir -p "$out"  # records of the bench runs below
+timeout -k 10 500 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/r03_e_bench.json" 2> "$out/r03_e_bench.err" || exit 1
+python - "$out/r03_e_bench.json" <<'PY'
+import json, sys
+d = json.loads(open(sys.argv[1]).readlines()[-1])
 print("config3 %.2f G/s %.2f ms" % (d["value"] / 1e9, d["ms_per_step"]), {k: round(v["ms_per_step"], 2) for k, v in d["roofline"]["kernels"].items()})
 print("probe_read_frac", d["roofline"].get("probe_read_frac"))
 for k, v in d.get("configs", {}).items():
