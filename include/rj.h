@@ -342,6 +342,16 @@ typedef struct rj_kernel_stat {
 int  rj_profile_read(rj_context* ctx, rj_kernel_stat* out, uint64_t cap, uint64_t* n);
 void rj_profile_reset(rj_context* ctx);
 
+/* Launch log (tests): which kernel template instantiations ran.  on != 0 starts
+ * counting every launch of the join kernels per kernel handle, 0 stops; both clear
+ * the log.  Off by default (then a launch costs one untaken branch).  A group
+ * context logs the launches of all its devices.                                  */
+int  rj_debug_launch_log(rj_context* ctx, int on);
+/* Newline-separated "<mangled symbol of the kernel handle> <launches>" lines (a
+ * handle without a dynamic symbol: "+0x<offset from the library's base>"), NUL-
+ * terminated and truncated to cap bytes; *need = bytes the whole text takes.     */
+int  rj_debug_launch_read(rj_context* ctx, char* buf, uint64_t cap, uint64_t* need);
+
 /* Device properties the host side reports next to its numbers. */
 typedef struct rj_device_info {
     char     name[128];

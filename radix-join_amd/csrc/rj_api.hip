@@ -180,6 +180,31 @@ int rj_debug_parse_fp64(const char* field, uint64_t n, uint64_t* bits) {
     return rj::parse_fp64_host(field, n, bits);
 }
 
+int rj_debug_launch_log(rj_context* ctx, int on) {
+    if (!ctx) return RJ_ERR_ARG;
+    for (int l = 0; l < ctx->n_lanes(); ++l) {  // a group context: every device's launches
+        ctx->lane(l)->klog.clear();
+        ctx->lane(l)->klog.on = on != 0;
+    }
+    return RJ_OK;
+}
+
+int rj_debug_launch_read(rj_context* ctx, char* buf, uint64_t cap, uint64_t* need) {
+    if (!ctx || !need || (cap && !buf)) return RJ_ERR_ARG;
+    return guarded(ctx, [&] {
+        std::map<std::string, uint64_t> all;
+        for (int l = 0; l < ctx->n_lanes(); ++l) ctx->lane(l)->klog.merge_into(all);
+        std::string text;
+        for (const auto& kv : all) text += kv.first + " " + std::to_string(kv.second) + "\n";
+        *need = text.size() + 1;
+        if (cap) {
+            const size_t n = std::min<size_t>(text.size(), cap - 1);
+            memcpy(buf, text.data(), n);
+            buf[n] = 0;
+        }
+    });
+}
+
 uint64_t rj_table_num_rows(const rj_table* t) { return t ? t->num_rows : 0; }
 uint64_t rj_table_col_pages(const rj_table* t, uint64_t col) { return table_col_pages(t, col); }
 

@@ -1,4 +1,6 @@
 // rj_context.hip — context, HBM block cache, HIP-event profiler.
+#include <dlfcn.h>
+
 #include <chrono>
 #include <cstdlib>
 
@@ -179,6 +181,38 @@ Profiler::~Profiler() {
         (void)hipEventDestroy(r.b);
     }
     for (hipEvent_t e : spare_) (void)hipEventDestroy(e);
+}
+
+// -------------------------------------------------------------- LaunchLog --
+void LaunchLog::add(const void* kernel) {
+    std::lock_guard<std::mutex> g(mu_);
+    ++counts_[kernel];
+}
+
+void LaunchLog::clear() {
+    std::lock_guard<std::mutex> g(mu_);
+    counts_.clear();
+}
+
+void LaunchLog::merge_into(std::map<std::string, uint64_t>& out) {
+    std::lock_guard<std::mutex> g(mu_);
+    for (const auto& kv : counts_) {
+        auto it = names_.find(kv.first);
+        if (it == names_.end()) {
+            Dl_info     di{};
+            std::string name;
+            if (dladdr(kv.first, &di) && di.dli_sname && di.dli_saddr == kv.first) {
+                name = di.dli_sname;
+            } else {
+                char b[40];
+                snprintf(b, sizeof b, "+0x%llx",
+                         (unsigned long long)((const char*)kv.first - (const char*)di.dli_fbase));
+                name = b;
+            }
+            it = names_.emplace(kv.first, name).first;
+        }
+        out[it->second] += kv.second;
+    }
 }
 
 // ---------------------------------------------------------------- Context --

@@ -9,6 +9,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -115,6 +116,23 @@ class Profiler {
     hipEvent_t              get_event();
 };
 
+// --------------------------------------------------------------- launch log --
+// rj_debug_launch_log / rj_debug_launch_read: how often each kernel handle was launched, so that
+// tests can tell which template instantiation a plan ran.  Names are resolved when read.
+class LaunchLog {
+   public:
+    bool on = false;
+    void add(const void* kernel);
+    void clear();
+    // name -> launches ("+0x<offset>" from the library's base when the handle has no symbol)
+    void merge_into(std::map<std::string, uint64_t>& out);
+
+   private:
+    std::mutex                         mu_;
+    std::map<const void*, uint64_t>    counts_;
+    std::map<const void*, std::string> names_;  // resolved once per distinct handle
+};
+
 // ------------------------------------------------------------------- tables --
 struct TableColumn {
     int32_t  type = 0;
@@ -218,6 +236,7 @@ struct Context {
     int         radix_bits_override = 0;
     DevPool     pool;
     Profiler    prof;
+    LaunchLog   klog;
     std::string last_error;
     // pinned staging for H2D / D2H of page images
     void*  pinned = nullptr;
@@ -241,6 +260,8 @@ struct Context {
         L.timed = prof.on ? [](void* s, const char* n, hipEvent_t* a, hipEvent_t* b) {
             return static_cast<Context*>(s)->prof.timed(n, a, b);
         } : (bool (*)(void*, const char*, hipEvent_t*, hipEvent_t*)) nullptr;
+        L.logged = klog.on ? [](void* s, const void* k) { static_cast<Context*>(s)->klog.add(k); }
+                           : (void (*)(void*, const void*)) nullptr;
         return L;
     }
     // multi-GPU: a context created over several devices is lane 0 of a group and owns one

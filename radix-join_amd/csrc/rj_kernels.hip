@@ -2480,6 +2480,7 @@ __global__ void k_debug_stall(unsigned long long ticks) {
 #define RJ_KLAUNCH(L, NAME, KERNEL, GRID, BLOCK, ...)                                          \
     do {                                                                                       \
         hipEvent_t _ev0 = nullptr, _ev1 = nullptr;                                             \
+        if ((L).logged) (L).logged((L).self, reinterpret_cast<const void*>(KERNEL));           \
         if ((L).timed && (L).timed((L).self, NAME, &_ev0, &_ev1))                              \
             hipExtLaunchKernelGGL(KERNEL, dim3(GRID), dim3(BLOCK), 0, (L).stream, _ev0, _ev1,  \
                                   0, __VA_ARGS__);                                             \

@@ -10,10 +10,13 @@ namespace rj {
 // timed(): should this launch be timed?  If so it hands out the start/stop events the launch
 // itself records (hipExtLaunchKernelGGL: the timestamps of the dispatch packet — no extra
 // event packets, so no idle gaps at the kernel boundaries).
+// logged(): set only while the context's launch log is on (rj_debug_launch_log); receives the
+// kernel handle of every launch, so that tests can see which template instantiation ran.
 struct Launch {
     hipStream_t stream;
     bool (*timed)(void* self, const char* name, hipEvent_t* start, hipEvent_t* stop);
     void* self;
+    void (*logged)(void* self, const void* kernel);
 };
 
 // A launch the runtime rejected, or a template combination no kernel exists for: throws

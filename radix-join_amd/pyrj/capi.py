@@ -139,6 +139,8 @@ EXPORTS = [
     "rj_join_tuples",
     "rj_profile_read",
     "rj_profile_reset",
+    "rj_debug_launch_log",
+    "rj_debug_launch_read",
     "rj_device_query",
 ]
 
@@ -256,6 +258,10 @@ def load():
     L.rj_profile_read.restype = C.c_int
     L.rj_profile_reset.argtypes = [vp]
     L.rj_profile_reset.restype = None
+    L.rj_debug_launch_log.argtypes = [vp, C.c_int]
+    L.rj_debug_launch_log.restype = C.c_int
+    L.rj_debug_launch_read.argtypes = [vp, C.c_char_p, u64, C.POINTER(u64)]
+    L.rj_debug_launch_read.restype = C.c_int
     L.rj_device_query.argtypes = [vp, C.POINTER(rj_device_info)]
     L.rj_device_query.restype = C.c_int
     _LIB = L
@@ -515,6 +521,23 @@ class Context:
 
     def profile_reset(self):
         self.L.rj_profile_reset(self.h)
+
+    # -- launch log (tests: which kernel template instantiations ran)
+    def launch_log(self, on=True):
+        """Start (on) or stop counting launches per kernel handle; both clear the log."""
+        self._check(self.L.rj_debug_launch_log(self.h, 1 if on else 0))
+
+    def launches(self) -> dict:
+        """{mangled kernel-handle symbol: launches} since launch_log(True)."""
+        need = C.c_uint64()
+        self._check(self.L.rj_debug_launch_read(self.h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value + 256)
+        self._check(self.L.rj_debug_launch_read(self.h, buf, len(buf), C.byref(need)))
+        out = {}
+        for line in buf.value.decode().splitlines():
+            name, n = line.rsplit(" ", 1)
+            out[name] = int(n)
+        return out
 
     def device_info(self):
         d = rj_device_info()
