@@ -59,8 +59,35 @@ typedef enum rj_status {
  * out_idx/out_type ↔ PlanNode::output_attrs (vector<tuple<size_t,DataType>>):
  *   scan: index into the base table's columns;
  *   join: index into concat(left child outputs, right child outputs)
- *         (reference README.md:55, src/execute.cpp:236-242).                 */
-typedef enum rj_node_kind { RJ_NODE_SCAN = 0, RJ_NODE_JOIN = 1 } rj_node_kind;
+ *         (reference README.md:55, src/execute.cpp:236-242).
+ *
+ * Semi and anti joins (no reference counterpart: WHERE EXISTS / NOT EXISTS / IN).
+ * RJ_NODE_SEMI / RJ_NODE_ANTI use the fields of a join with the same meaning:
+ *   build_left picks the FILTER side (the side that is built, as for RJ_NODE_JOIN); the other
+ *   child is the PRESERVED side, which is probed.  out_idx indexes concat(left outputs, right
+ *   outputs) as for a join and may name columns of the preserved side only (a filter-side
+ *   column is RJ_ERR_ARG).
+ *   SEMI: every preserved row whose key equals at least one filter-side key, once, however many
+ *         partners it has.
+ *   ANTI: every preserved row for which no filter-side key is equal — NOT EXISTS, not NOT IN:
+ *         rows with a NULL key and FP64 rows with a NaN key are in the result, and a NULL on
+ *         the filter side changes nothing.
+ *   Key equality is the inner join's: the key type is the filter side's key type; INT32 / INT64
+ *   compare by value; FP64 by bit pattern, a NaN matches nothing; a preserved key of another
+ *   type matches nothing (SEMI: 0 rows, ANTI: every preserved row).  An empty filter side gives
+ *   0 rows (SEMI) or every preserved row (ANTI); an empty preserved side 0 rows with the declared
+ *   column types and zero pages.  The result is a multiset of preserved rows in no particular
+ *   order.  VARCHAR keys are RJ_ERR_UNSUPPORTED; VARCHAR payload columns of the preserved side
+ *   are fine.  The kinds nest freely with joins and with each other.  rj_execute_sharded refuses
+ *   plans that hold them (RJ_ERR_UNSUPPORTED), rj_plan_shardable reports them, and rj_execute on
+ *   a multi-device context runs such a plan on its first device.  A library older than these
+ *   kinds rejects them with RJ_ERR_ARG ("bad node kind").                                       */
+typedef enum rj_node_kind {
+    RJ_NODE_SCAN = 0,
+    RJ_NODE_JOIN = 1,
+    RJ_NODE_SEMI = 2, /* preserved rows with a partner on the filter side    */
+    RJ_NODE_ANTI = 3  /* preserved rows without one                          */
+} rj_node_kind;
 
 typedef struct rj_node {
     int32_t         kind;          /* rj_node_kind                            */
@@ -274,7 +301,8 @@ void     rj_result_free(rj_result* r);
  * all ranks' shards is the input.  out[d] receives local device d's slice of the result (rows
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
- * side (the BASELINE shape); others return RJ_ERR_UNSUPPORTED.                              */
+ * side (the BASELINE shape), and no node is a semi or anti join; others return
+ * RJ_ERR_UNSUPPORTED.                                                                         */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0

@@ -272,4 +272,29 @@ struct BcastParams {
     uint64_t        out_cap;
 };
 
+// ---- Semi / anti joins (RJ_NODE_SEMI / RJ_NODE_ANTI): "has this preserved row a partner?" ------
+// The filter side builds an LDS set of its DISTINCT hashed keys; the preserved side is probed and
+// the rows that hit (SEMI) or miss (ANTI) are emitted once each: the un-hashed key (if requested)
+// and the preserved carry.  The set holds JN_RMAX keys at most (load <= 50 %); a partition with
+// more distinct filter keys is filtered round by round (k_filter_join).
+struct FilterParams {
+    TupleSrc        F, P;         // broadcast: filter / preserved tuples straight from the columns;
+                                  // k_filter_nullkeys: P
+    Words           Fw, Pw;       // partitioned: filter key words / preserved tuples
+    const uint32_t* offF;         // [NP+1]
+    const uint32_t* offP;         // [NP+1]
+    uint32_t        NP;
+    uint32_t        radix_bits;
+    int32_t         packP, aosP;  // Pw.w[0] holds {hashed key, carry} pairs / 12-byte tuples
+    const uint32_t* heavy_tasks;  // [n][3] = {partition, p_begin, p_end} (k_heavy_tasks)
+    const uint32_t* n_heavy;
+    uint32_t        heavy_grid;   // the first heavy_grid workgroups of the launch take heavy tasks
+    int32_t         anti;         // 0: SEMI (emit hits), 1: ANTI (emit misses)
+    int32_t         keyless;      // 1: the key types differ, no row can match (keys are not read)
+    int32_t         pad;
+    OutStream       key, pc;      // emitted streams: key, preserved carry
+    unsigned long long* out_cursor;
+    uint64_t        out_cap;      // rows that fit the streams (= preserved rows)
+};
+
 }  // namespace rj

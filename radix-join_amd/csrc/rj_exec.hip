@@ -302,7 +302,8 @@ class Exec {
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
         if (n.kind == RJ_NODE_SCAN) return scan(n);
-        if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
+        if (n.kind != RJ_NODE_JOIN && n.kind != RJ_NODE_SEMI && n.kind != RJ_NODE_ANTI)
+            throw_fmt(RJ_ERR_ARG, "bad node kind");
         Rel      l = node(n.left, nullptr, depth + 1);
         Rel      r = node(n.right, nullptr, depth + 1);
         JoinSpec js;
@@ -312,6 +313,7 @@ class Exec {
         js.out_idx.assign(n.out_idx, n.out_idx + n.n_out);
         js.out_type.assign(n.out_type, n.out_type + n.n_out);
         js.forced_bits = ctx->radix_bits_override;
+        if (n.kind != RJ_NODE_JOIN) return filter_join(l, r, js, n.kind == RJ_NODE_ANTI, root_res);
         return join_core(l, r, js, root_res);
     }
 
@@ -778,8 +780,10 @@ class Exec {
         };
 
         // shared_nulls (sharded joins): {left, right} null_columns() OR-ed over all ranks
+        // filter_kind: RJ_NODE_JOIN, or RJ_NODE_SEMI / RJ_NODE_ANTI (filter_join: the build side is the
+        // filter side, it carries nothing)
         void join_prepare(Rel& left, Rel& right, const JoinSpec& js, bool is_root, JoinState& st,
-                          const uint64_t* shared_nulls = nullptr) {
+                          const uint64_t* shared_nulls = nullptr, int filter_kind = RJ_NODE_JOIN) {
             const size_t lw = left.cols.size(), rw = right.cols.size();
             st.lw = lw;
             st.rw = rw;
@@ -815,12 +819,18 @@ class Exec {
             st.f64 = bk.type == RJ_FP64;
             // matching keys are bit-identical on both sides (FP64 included: bit-pattern equality,
             // see SrcLoader::key2), so one emitted key stream serves either side's key column.
+            // A semi / anti join emits the preserved side's own key — through the key stream unless
+            // its type is not the key type (no key is read then) or ANTI may emit rows whose key is
+            // NULL (the stream has no validity): then the key column travels as a payload column.
+            const bool key_stream_ok =
+                filter_kind == RJ_NODE_JOIN ||
+                (!st.type_mismatch && !(filter_kind == RJ_NODE_ANTI && st.ps().rel->cols[st.ps().key_col].valid));
             // Which child columns must each side deliver?
             for (size_t k = 0; k < js.out_idx.size(); ++k) {
                 bool  is_left = js.out_idx[k] < lw;
                 Side& s = is_left ? ls : rs;
                 int   c = (int)(is_left ? js.out_idx[k] : js.out_idx[k] - lw);
-                if ((uint64_t)c == s.key_col && !st.vkey)
+                if ((uint64_t)c == s.key_col && !st.vkey && key_stream_ok)
                     st.need_key_stream = true;
                 else
                     s.need.insert(c);  // (a VARCHAR key column is gathered like any other column)
@@ -957,12 +967,100 @@ class Exec {
             return join_finish(st, js, bcast ? nullptr : &PB, bcast ? nullptr : &PP, bits, root_res);
         }
 
+        // Semi / anti join (RJ_NODE_SEMI / RJ_NODE_ANTI, semantics in rj.h): the build side is the
+        // filter side and carries nothing, the probe side is preserved; every preserved row that has
+        // (SEMI) or has not (ANTI) a partner comes out once, with the preserved side's columns only.
+        Rel filter_join(Rel& left, Rel& right, const JoinSpec& js, bool anti, Result* root_res) {
+            Rel&         fil = js.build_left ? left : right;
+            Rel&         pre = js.build_left ? right : left;
+            const size_t lw = left.cols.size();
+            for (uint64_t o : js.out_idx)
+                if (o < lw + right.cols.size() && (o < lw) == js.build_left)
+                    throw_fmt(RJ_ERR_ARG, "%s join: output attr %llu names a column of the filter side",
+                              anti ? "anti" : "semi", (unsigned long long)o);
+            const uint64_t fattr = js.build_left ? js.left_attr : js.right_attr;
+            if (fattr < fil.cols.size() && fil.cols[fattr].type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "%s join on a VARCHAR key", anti ? "anti" : "semi");
+            if (pre.n == 0 || (!anti && fil.n == 0)) return empty_rel(js, root_res);
+            JoinState st;
+            join_prepare(left, right, js, root_res != nullptr, st, nullptr, anti ? RJ_NODE_ANTI : RJ_NODE_SEMI);
+            if (st.type_mismatch && !anti) return empty_rel(js, root_res);
+            Side&     fs = st.bs();
+            Side&     ps = st.ps();
+            const int KW = st.KW;
+            prepare_wide(ps);
+            plan_carry_streams(st);
+            const bool keyless = st.type_mismatch;
+            // an empty filter side or keys of another type need no set: every row misses
+            const bool bcast = (fs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && ctx->tune.bcast != 0) ||
+                               fs.rel->n == 0 || keyless;
+            const uint32_t bits = join_bits(js, fs.rel->n);
+            if (ctx->tune.diag >= 2)
+                fprintf(stderr, "[rj diag] %s join filter=%llu preserved=%llu %s bits=%u cw=%d\n", anti ? "anti" : "semi",
+                        (unsigned long long)fs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
+                        bits, ps.CW);
+
+            // the output never holds more rows than the preserved side: streams of that size, no retry
+            const uint64_t cap = ps.rel->n;
+            const int      key_mode = st.need_key_stream ? stream_mode_of(st.is_root, KW * 4, true) : ST_NONE;
+            BufP           key_stream = key_mode != ST_NONE ? ctx->buf(stream_bytes(key_mode, cap)) : BufP();
+            ps.stream = ps.stream_mode != ST_NONE ? ctx->buf(stream_bytes(ps.stream_mode, cap)) : BufP();
+            BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
+            RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
+
+            FilterParams fp{};
+            fp.anti = anti ? 1 : 0;
+            fp.keyless = keyless ? 1 : 0;
+            fp.key = OutStream{key_stream ? key_stream->as<uint8_t>() : nullptr, key_mode, 0};
+            fp.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
+            fp.out_cursor = counters->as<unsigned long long>();
+            fp.out_cap = cap;
+            fp.P = make_src(st, ps, js);
+            const uint32_t stride_grid = (uint32_t)std::min<uint64_t>((ps.rel->n + JN_SUB - 1) / JN_SUB,
+                                                                      (uint64_t)ctx->compute_units() * 8);
+            Parted PF, PP;
+            BufP   tasks;
+            if (bcast) {
+                if (!keyless) fp.F = make_src(st, fs, js);
+                launch_filter_bcast(L, KW, ps.CW, fp, stride_grid);
+            } else {
+                // both sides partitioned as an inner join's would be; the filter side carries nothing
+                TupleSrc sf = make_src(st, fs, js);
+                PF = partition(&sf, nullptr, KW, 0, bits);
+                PP = partition(&fp.P, nullptr, KW, ps.CW, bits);
+                const uint32_t max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
+                tasks = ctx->buf((uint64_t)max_tasks * 12);
+                launch_heavy_tasks_zeroed(PF, PP, tasks, counters, max_tasks);
+                fp.Fw = PF.w;
+                fp.Pw = PP.w;
+                fp.offF = PF.off->as<uint32_t>();
+                fp.offP = PP.off->as<uint32_t>();
+                fp.NP = PF.NP;
+                fp.radix_bits = bits;
+                fp.packP = PP.packed ? 1 : 0;
+                fp.aosP = PP.aos3 ? 1 : 0;
+                fp.heavy_tasks = tasks->as<uint32_t>();
+                fp.n_heavy = counters->as<uint32_t>() + 2;
+                fp.heavy_grid = max_tasks;
+                launch_filter_join(L, KW, ps.CW, fp, max_tasks + PF.NP);
+                // the rows the first radix pass dropped: NULL keys, FP64 NaN keys
+                if (anti && (fp.P.key.valid || fp.P.key_f64)) launch_filter_nullkeys(L, KW, ps.CW, fp, stride_grid);
+            }
+            std::set<void*> finished;
+            finish_paged_streams(st, key_stream, key_mode, counters, cap, finished);
+            unsigned long long h = 0;
+            RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+            if (h > cap) throw_fmt(RJ_ERR_DEVICE, "%s join emitted %llu rows out of %llu", anti ? "anti" : "semi", h,
+                                   (unsigned long long)cap);
+            return join_assemble(st, js, key_stream, key_mode, h, finished, root_res);
+        }
+
         // Build + probe over co-partitioned tuples (PB / PP; nullptr = broadcast join straight
         // from the children's columns), output streams, late materialisation, result pages.
         Rel join_finish(JoinState& st, const JoinSpec& js, const Parted* PBp, const Parted* PPp,
                         uint32_t bits, Result* root_res) {
             Side &         ls = st.ls, &rs = st.rs, &bs = st.bs(), &ps = st.ps();
-            const size_t   lw = st.lw;
             const bool     is_root = st.is_root, bcast = PBp == nullptr;
             const int      KW = st.KW;
             const bool     need_key_stream = st.need_key_stream;
@@ -981,32 +1079,10 @@ class Exec {
 
             // stream destinations
             auto stream_mode = [&](int width, bool direct_output) -> int {
-                if (is_root && direct_output) return width == 4 ? ST_PAGED32 : ST_PAGED64;
-                return width == 4 ? ST_DENSE32 : ST_DENSE64;
-            };
-            auto stream_bytes = [&](int mode, uint64_t rows) -> uint64_t {
-                switch (mode) {
-                case ST_DENSE32: return rows * 4;
-                case ST_DENSE64: return rows * 8;
-                case ST_PAGED32: return pages_for(rows, 4) * PAGE_BYTES;
-                case ST_PAGED64: return pages_for(rows, 8) * PAGE_BYTES;
-                case ST_DENSE96: return rows * 12;
-                default: return 0;
-                }
+                return stream_mode_of(is_root, width, direct_output);
             };
             int key_mode = need_key_stream ? stream_mode(KW * 4, true) : ST_NONE;
-            for (Side* s : {&ls, &rs}) {
-                if (s->carry_mode == CARRY_NONE)
-                    s->stream_mode = ST_NONE;
-                else if (s->carry_mode == CARRY_ROWIDX)
-                    s->stream_mode = ST_DENSE32;
-                else if (s->carry_mode == CARRY_WIDE)
-                    s->stream_mode = s->CW == 2 ? ST_DENSE64 : ST_DENSE96;  // records, split below
-                else {
-                    const DCol& c = s->rel->cols[s->carry_col];
-                    s->stream_mode = stream_mode(c.width, c.type != RJ_VARCHAR);
-                }
-            }
+            plan_carry_streams(st);
 
             uint64_t cap = st.cap_hint;
             cap = std::min<uint64_t>(cap + 1024, 0xfffffff0ull);
@@ -1081,22 +1157,7 @@ class Exec {
             // Page headers of the streams the probe wrote straight into Page images: done on
             // the device from the device-side row count, so nothing waits for the read-back
             finished.clear();
-            {
-                uint8_t* fp[3];
-                int      fw[3];
-                uint32_t nf = 0;
-                auto add = [&](const BufP& b, int mode) {
-                    if (!b || (mode != ST_PAGED32 && mode != ST_PAGED64) || finished.count(b->p)) return;
-                    fp[nf] = b->as<uint8_t>();
-                    fw[nf] = mode == ST_PAGED32 ? 4 : 8;
-                    ++nf;
-                    finished.insert(b->p);
-                };
-                add(key_stream, key_mode);
-                add(ls.stream, ls.stream_mode);
-                add(rs.stream, rs.stream_mode);
-                launch_finish_streams(L, fp, fw, nf, counters->as<unsigned long long>(), cap);
-            }
+            finish_paged_streams(st, key_stream, key_mode, counters, cap, finished);
             unsigned long long h = 0;
             RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
             ctx->sync();
@@ -1109,6 +1170,65 @@ class Exec {
         }
 
         if (st.vkey && nrows) nrows = verify_varchar_pairs(st, nrows);
+        return join_assemble(st, js, key_stream, key_mode, nrows, finished, root_res);
+    }
+
+    static int stream_mode_of(bool is_root, int width, bool direct_output) {
+        if (is_root && direct_output) return width == 4 ? ST_PAGED32 : ST_PAGED64;
+        return width == 4 ? ST_DENSE32 : ST_DENSE64;
+    }
+    static uint64_t stream_bytes(int mode, uint64_t rows) {
+        switch (mode) {
+        case ST_DENSE32: return rows * 4;
+        case ST_DENSE64: return rows * 8;
+        case ST_PAGED32: return pages_for(rows, 4) * PAGE_BYTES;
+        case ST_PAGED64: return pages_for(rows, 8) * PAGE_BYTES;
+        case ST_DENSE96: return rows * 12;
+        default: return 0;
+        }
+    }
+    // the layout of each side's carry stream
+    static void plan_carry_streams(JoinState& st) {
+        for (Side* s : {&st.ls, &st.rs}) {
+            if (s->carry_mode == CARRY_NONE)
+                s->stream_mode = ST_NONE;
+            else if (s->carry_mode == CARRY_ROWIDX)
+                s->stream_mode = ST_DENSE32;
+            else if (s->carry_mode == CARRY_WIDE)
+                s->stream_mode = s->CW == 2 ? ST_DENSE64 : ST_DENSE96;  // records, split below
+            else {
+                const DCol& c = s->rel->cols[s->carry_col];
+                s->stream_mode = stream_mode_of(st.is_root, c.width, c.type != RJ_VARCHAR);
+            }
+        }
+    }
+    // headers + bitmaps of the streams a probe wrote straight into Page images, from the row count
+    // on the device (counters[0]); `finished` records them
+    void finish_paged_streams(JoinState& st, const BufP& key_stream, int key_mode, const BufP& counters,
+                              uint64_t cap, std::set<void*>& finished) {
+        uint8_t* fp[3];
+        int      fw[3];
+        uint32_t nf = 0;
+        auto add = [&](const BufP& b, int mode) {
+            if (!b || (mode != ST_PAGED32 && mode != ST_PAGED64) || finished.count(b->p)) return;
+            fp[nf] = b->as<uint8_t>();
+            fw[nf] = mode == ST_PAGED32 ? 4 : 8;
+            ++nf;
+            finished.insert(b->p);
+        };
+        add(key_stream, key_mode);
+        add(st.ls.stream, st.ls.stream_mode);
+        add(st.rs.stream, st.rs.stream_mode);
+        launch_finish_streams(L, fp, fw, nf, counters->as<unsigned long long>(), cap);
+    }
+
+    // What the probe's streams become: wide records split into columns, row-index carries gathered,
+    // and at the root Page images (late materialisation; shared by inner and semi / anti joins).
+    Rel join_assemble(JoinState& st, const JoinSpec& js, const BufP& key_stream, int key_mode, uint64_t nrows,
+                      std::set<void*>& finished, Result* root_res) {
+        Side &       ls = st.ls, &rs = st.rs;
+        const size_t lw = st.lw;
+        const bool   is_root = st.is_root;
 
         // wide carries: the emitted records -> one dense array (+ validity bytes) per column
         for (Side* s : {&ls, &rs}) {
@@ -1159,7 +1279,7 @@ class Exec {
             BufP buf;           // where this column's values/pages live
             int  buf_mode = ST_NONE;
             BufP valid;
-            if ((uint64_t)c == s.key_col) {
+            if ((uint64_t)c == s.key_col && st.need_key_stream) {
                 buf = key_stream;
                 buf_mode = key_mode;
             } else if (s.carry_mode == CARRY_COLUMN) {
@@ -1516,6 +1636,9 @@ class ShardedExec {
                 });
             return r;
         }
+        if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: %s join nodes run on one device",
+                      n.kind == RJ_NODE_SEMI ? "semi (RJ_NODE_SEMI)" : "anti (RJ_NODE_ANTI)");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -1896,6 +2019,12 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
             }
         return true;
     }
+    if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI) {
+        if (why)
+            *why = n.kind == RJ_NODE_SEMI ? "a semi join node (RJ_NODE_SEMI) runs on one device"
+                                          : "an anti join node (RJ_NODE_ANTI) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -1953,8 +2082,22 @@ Result* join_tuples(Context* ctx, const rj_tuples* build, const rj_tuples* probe
     return e.run_tuples(build, probe, skip_rank_bits);
 }
 
+// the node kinds ShardedExec refuses, found before any rank moves data
+static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
+    if (!plan || idx >= plan->n_nodes || depth > 4096) return;  // (the plan walk reports it)
+    const rj_node& n = plan->nodes[idx];
+    if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI)
+        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds %s join node; semi and anti joins run on one device",
+                  n.kind == RJ_NODE_SEMI ? "a semi (RJ_NODE_SEMI)" : "an anti (RJ_NODE_ANTI)");
+    if (n.kind == RJ_NODE_JOIN) {
+        refuse_filter_nodes(plan, n.left, depth + 1);
+        refuse_filter_nodes(plan, n.right, depth + 1);
+    }
+}
+
 void execute_sharded(Context* group, const rj_plan* plan, Table* const* tables, uint64_t n_inputs,
                      int flags, Result** out) {
+    if (plan) refuse_filter_nodes(plan, plan->root, 0);
     ShardedExec e(group, plan, tables, n_inputs, flags);
     e.run(out);
 }

@@ -116,6 +116,15 @@ void launch_join(const Launch& L, int key_words, int cw_build, int cw_probe, con
 void launch_join_bcast(const Launch& L, int key_words, int cw_build, int cw_probe,
                        const BcastParams& bp, uint32_t grid);
 
+// ---- semi / anti joins (FilterParams): key_words 1 or 2, cw_preserved 0..MAX_WORDS - key_words
+// broadcast: filter side of at most JN_RMAX rows, `grid` workgroups stride over the preserved rows
+void launch_filter_bcast(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid);
+// partitioned: grid = fp.heavy_grid + fp.NP (one workgroup per heavy task, then per partition)
+void launch_filter_join(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid);
+// ANTI after the partitioned filter: the preserved rows the first radix pass drops (NULL key,
+// FP64 NaN key) go out through the same cursor
+void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

@@ -48,6 +48,23 @@ class JoinNode:
     right_attr: int
 
 
+# rj_node_kind (include/rj.h)
+NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI = 0, 1, 2, 3
+
+
+@dataclass
+class FilterJoinNode:
+    """Semi (kind NODE_SEMI) or anti (NODE_ANTI) join: the rows of the preserved child that have
+    (or have no) partner in the filter child.  build_left picks the filter side; output_attrs may
+    name columns of the preserved side only (include/rj.h)."""
+    kind: int
+    build_left: bool
+    left: int
+    right: int
+    left_attr: int
+    right_attr: int
+
+
 @dataclass
 class PlanNode:
     data: object
@@ -62,6 +79,21 @@ class Plan:
 
     def new_join_node(self, build_left, left, right, left_attr, right_attr, output_attrs):
         self.nodes.append(PlanNode(JoinNode(bool(build_left), left, right, left_attr, right_attr), list(output_attrs)))
+        return len(self.nodes) - 1
+
+    def new_semi_join_node(self, build_left, left, right, left_attr, right_attr, output_attrs):
+        """WHERE EXISTS: rows of the preserved child (the one build_left does not name) whose key
+        has a partner in the filter child, once each."""
+        return self._filter_node(NODE_SEMI, build_left, left, right, left_attr, right_attr, output_attrs)
+
+    def new_anti_join_node(self, build_left, left, right, left_attr, right_attr, output_attrs):
+        """WHERE NOT EXISTS: rows of the preserved child whose key has no partner in the filter
+        child (NULL and NaN keys included)."""
+        return self._filter_node(NODE_ANTI, build_left, left, right, left_attr, right_attr, output_attrs)
+
+    def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
+        node = FilterJoinNode(kind, bool(build_left), left, right, left_attr, right_attr)
+        self.nodes.append(PlanNode(node, list(output_attrs)))
         return len(self.nodes) - 1
 
     def new_scan_node(self, base_table_id, output_attrs):
@@ -260,8 +292,8 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
         nd.n_out = k
         nd.out_idx = C.cast(idx, C.POINTER(C.c_uint64))
         nd.out_type = C.cast(typ, C.POINTER(C.c_int32))
-        if isinstance(n.data, JoinNode):
-            nd.kind = 1
+        if isinstance(n.data, (JoinNode, FilterJoinNode)):
+            nd.kind = n.data.kind if isinstance(n.data, FilterJoinNode) else NODE_JOIN
             nd.build_left = 1 if n.data.build_left else 0
             nd.left, nd.right = n.data.left, n.data.right
             nd.left_attr, nd.right_attr = n.data.left_attr, n.data.right_attr
