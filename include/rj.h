@@ -81,12 +81,42 @@ typedef enum rj_status {
  *   are fine.  The kinds nest freely with joins and with each other.  rj_execute_sharded refuses
  *   plans that hold them (RJ_ERR_UNSUPPORTED), rj_plan_shardable reports them, and rj_execute on
  *   a multi-device context runs such a plan on its first device.  A library older than these
- *   kinds rejects them with RJ_ERR_ARG ("bad node kind").                                       */
+ *   kinds rejects them with RJ_ERR_ARG ("bad node kind").
+ *
+ * Outer joins (LEFT / RIGHT OUTER JOIN; no reference counterpart).
+ * RJ_NODE_OUTER uses the fields of a join with the same meaning:
+ *   build_left picks the OPTIONAL side: the side that is built, and whose columns are NULL in the
+ *   rows of preserved rows without a partner.  The other child is the PRESERVED side, which is
+ *   probed.  SQL `left LEFT JOIN right` is build_left = 0, `left RIGHT JOIN right` build_left = 1.
+ *   out_idx indexes concat(left outputs, right outputs) as for a join and may name columns of both
+ *   sides, in any order, repeated or not, possibly none of one side.
+ *   Result: the inner join's rows (same key rules, duplicates multiply on both sides) plus, for
+ *   every preserved row that has NO partner, exactly one row holding that row's preserved columns
+ *   and NULL in every optional-side column.  "No partner" is what ANTI means by it: the preserved
+ *   key is NULL, is an FP64 NaN, is of another type than the optional side's key (then EVERY
+ *   preserved row is unmatched), or equals no optional key.  NULL and NaN keys on the optional
+ *   side match nothing and add no rows.  Key equality is the inner join's: the key type is the
+ *   optional (build) side's; INT32 / INT64 compare by value, FP64 by bit pattern.
+ *   The preserved side's key column, when output, is that row's own key, NULL included; the
+ *   optional side's key column, when output, is NULL in unmatched rows.  An empty optional side
+ *   gives every preserved row, padded; an empty preserved side 0 rows with the declared column
+ *   types and zero pages.  The result is a multiset in no particular order.  An output column
+ *   keeps its declared type; optional-side columns of the result are nullable even when the
+ *   source column is not.
+ *   VARCHAR keys are RJ_ERR_UNSUPPORTED.  VARCHAR payload columns of the preserved side are fine;
+ *   a VARCHAR column of the OPTIONAL side in out_idx is RJ_ERR_UNSUPPORTED (a VARCHAR value
+ *   travels as a row id of its base table, which has no way to say NULL).
+ *   The kind nests freely under and over joins, semi / anti joins and other outer joins; a parent
+ *   may join on a nullable column an outer join produced (NULL keys drop out as always).
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.
+ *   A library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").               */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
     RJ_NODE_JOIN = 1,
     RJ_NODE_SEMI = 2, /* preserved rows with a partner on the filter side    */
-    RJ_NODE_ANTI = 3  /* preserved rows without one                          */
+    RJ_NODE_ANTI = 3, /* preserved rows without one                          */
+    RJ_NODE_OUTER = 4 /* inner join + unmatched preserved rows, NULL-padded  */
 } rj_node_kind;
 
 typedef struct rj_node {
@@ -301,13 +331,14 @@ void     rj_result_free(rj_result* r);
  * all ranks' shards is the input.  out[d] receives local device d's slice of the result (rows
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
- * side (the BASELINE shape), and no node is a semi or anti join; others return
+ * side (the BASELINE shape), and no node is a semi, anti or outer join; others return
  * RJ_ERR_UNSUPPORTED.                                                                         */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
- * only: needs neither a context nor a GPU.                                                    */
+ * only: needs neither a context nor a GPU.  A plan that holds a semi, anti or outer join is not
+ * shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER).           */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

@@ -297,4 +297,32 @@ struct FilterParams {
     uint64_t        out_cap;      // rows that fit the streams (= preserved rows)
 };
 
+// ---- Outer joins (RJ_NODE_OUTER): the inner join's rows plus every preserved row without a
+// partner, once, with NULL in the optional (build) side's columns.  "NULL" travels in-band in the
+// build carry stream: the reserved row id OUTER_NO_ROW for a CARRY_ROWIDX optional side, an
+// all-zero record (validity word included, which such a carry always has) for a CARRY_WIDE one;
+// CARRY_COLUMN is not used for an optional side.  `pad_bc` is the first word of a padded row's
+// build carry, the other words are zero.
+constexpr uint32_t OUTER_NO_ROW = 0xffffffffu;
+struct OuterParams {
+    TupleSrc        B, P;         // broadcast: optional / preserved tuples straight from the columns;
+                                  // k_outer_nullkeys: P
+    Words           Bw, Pw;       // partitioned: optional / preserved tuples
+    const uint32_t* offB;         // [NP+1]
+    const uint32_t* offP;         // [NP+1]
+    uint32_t        NP;
+    uint32_t        radix_bits;
+    int32_t         packB, aosB;  // Bw.w[0] holds {hashed key, carry} pairs / 12-byte tuples
+    int32_t         packP, aosP;  // ... and Pw.w[0]
+    const uint32_t* heavy_tasks;  // [n][3] = {partition, p_begin, p_end} (k_heavy_tasks)
+    const uint32_t* n_heavy;
+    uint32_t        heavy_grid;   // the first heavy_grid workgroups of the launch take heavy tasks
+    int32_t         keyless;      // 1: the key types differ, no row can match (keys are not read)
+    uint32_t        pad_bc;       // OUTER_NO_ROW (row-index carry) or 0 (wide carry)
+    int32_t         pad;
+    OutStream       key, bc, pc;  // emitted streams: preserved key, optional carry, preserved carry
+    unsigned long long* out_cursor;
+    uint64_t        out_cap;      // rows that fit the streams; rows beyond are counted, not written
+};
+
 }  // namespace rj

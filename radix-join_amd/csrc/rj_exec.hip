@@ -302,7 +302,7 @@ class Exec {
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
         if (n.kind == RJ_NODE_SCAN) return scan(n);
-        if (n.kind != RJ_NODE_JOIN && n.kind != RJ_NODE_SEMI && n.kind != RJ_NODE_ANTI)
+        if (n.kind != RJ_NODE_JOIN && n.kind != RJ_NODE_SEMI && n.kind != RJ_NODE_ANTI && n.kind != RJ_NODE_OUTER)
             throw_fmt(RJ_ERR_ARG, "bad node kind");
         Rel      l = node(n.left, nullptr, depth + 1);
         Rel      r = node(n.right, nullptr, depth + 1);
@@ -313,6 +313,7 @@ class Exec {
         js.out_idx.assign(n.out_idx, n.out_idx + n.n_out);
         js.out_type.assign(n.out_type, n.out_type + n.n_out);
         js.forced_bits = ctx->radix_bits_override;
+        if (n.kind == RJ_NODE_OUTER) return outer_join(l, r, js, root_res);
         if (n.kind != RJ_NODE_JOIN) return filter_join(l, r, js, n.kind == RJ_NODE_ANTI, root_res);
         return join_core(l, r, js, root_res);
     }
@@ -715,8 +716,11 @@ class Exec {
             // every rank (bit c = column c; columns from 64 up count as nullable when `shared` is set)
             uint64_t null_mask = 0;
             bool     shared = false;
+            // the optional side of an outer join: every column it delivers can come out NULL (a padded
+            // row), whatever the source column holds
+            bool     optional = false;
             bool     nullable(int c) const {
-                if (rel->cols[c].valid != nullptr) return true;
+                if (optional || rel->cols[c].valid != nullptr) return true;
                 return shared && (c >= 64 || ((null_mask >> c) & 1u));
             }
         };
@@ -781,7 +785,8 @@ class Exec {
 
         // shared_nulls (sharded joins): {left, right} null_columns() OR-ed over all ranks
         // filter_kind: RJ_NODE_JOIN, or RJ_NODE_SEMI / RJ_NODE_ANTI (filter_join: the build side is the
-        // filter side, it carries nothing)
+        // filter side, it carries nothing), or RJ_NODE_OUTER (outer_join: the build side is the
+        // optional side, whose columns are nullable in the result)
         void join_prepare(Rel& left, Rel& right, const JoinSpec& js, bool is_root, JoinState& st,
                           const uint64_t* shared_nulls = nullptr, int filter_kind = RJ_NODE_JOIN) {
             const size_t lw = left.cols.size(), rw = right.cols.size();
@@ -822,15 +827,21 @@ class Exec {
             // A semi / anti join emits the preserved side's own key — through the key stream unless
             // its type is not the key type (no key is read then) or ANTI may emit rows whose key is
             // NULL (the stream has no validity): then the key column travels as a payload column.
+            // An outer join emits unmatched rows as ANTI does, so the preserved key follows ANTI's rule;
+            // the optional side's key column is NULL in those rows and never comes from the key stream:
+            // it travels as one of that side's payload columns.
+            const bool outer = filter_kind == RJ_NODE_OUTER;
+            const bool emits_unmatched = filter_kind == RJ_NODE_ANTI || outer;
             const bool key_stream_ok =
                 filter_kind == RJ_NODE_JOIN ||
-                (!st.type_mismatch && !(filter_kind == RJ_NODE_ANTI && st.ps().rel->cols[st.ps().key_col].valid));
+                (!st.type_mismatch && !(emits_unmatched && st.ps().rel->cols[st.ps().key_col].valid));
+            st.bs().optional = outer;
             // Which child columns must each side deliver?
             for (size_t k = 0; k < js.out_idx.size(); ++k) {
                 bool  is_left = js.out_idx[k] < lw;
                 Side& s = is_left ? ls : rs;
                 int   c = (int)(is_left ? js.out_idx[k] : js.out_idx[k] - lw);
-                if ((uint64_t)c == s.key_col && !st.vkey && key_stream_ok)
+                if ((uint64_t)c == s.key_col && !st.vkey && key_stream_ok && !s.optional)
                     st.need_key_stream = true;
                 else
                     s.need.insert(c);  // (a VARCHAR key column is gathered like any other column)
@@ -1056,6 +1067,112 @@ class Exec {
             return join_assemble(st, js, key_stream, key_mode, h, finished, root_res);
         }
 
+        // Outer join (RJ_NODE_OUTER, semantics in rj.h): the build side is the OPTIONAL side, the probe
+        // side is preserved.  The inner join's rows plus one row per preserved row without a partner,
+        // whose optional-side columns are NULL.  Both sides are partitioned as an inner join's are
+        // (or not at all: broadcast); one kernel family emits both halves.  NULL travels in-band in the
+        // optional side's carry (OuterParams), so that side never uses CARRY_COLUMN.
+        Rel outer_join(Rel& left, Rel& right, const JoinSpec& js, Result* root_res) {
+            Rel&           opt = js.build_left ? left : right;
+            Rel&           pre = js.build_left ? right : left;
+            const uint64_t oattr = js.build_left ? js.left_attr : js.right_attr;
+            if (oattr < opt.cols.size() && opt.cols[oattr].type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "outer join on a VARCHAR key");
+            if (pre.n == 0) return empty_rel(js, root_res);
+            JoinState st;
+            join_prepare(left, right, js, root_res != nullptr, st, nullptr, RJ_NODE_OUTER);
+            Side&     bs = st.bs();
+            Side&     ps = st.ps();
+            const int KW = st.KW;
+            for (int c : bs.need)
+                if (bs.rel->cols[c].type == RJ_VARCHAR)
+                    throw_fmt(RJ_ERR_UNSUPPORTED,
+                              "outer join: a VARCHAR column of the optional side in the output is not supported "
+                              "(child column %d)", c);
+            prepare_wide(bs);
+            prepare_wide(ps);
+            plan_carry_streams(st);
+            const bool keyless = st.type_mismatch;
+            // an empty optional side or keys of another type need no table: every row comes out padded
+            const bool bcast = (bs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && ctx->tune.bcast != 0) ||
+                               bs.rel->n == 0 || keyless;
+            const uint32_t bits = join_bits(js, bs.rel->n);
+            if (ctx->tune.diag >= 2)
+                fprintf(stderr, "[rj diag] outer join optional=%llu preserved=%llu %s bits=%u cw=%d/%d\n",
+                        (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
+                        bits, bs.CW, ps.CW);
+
+            OuterParams op{};
+            op.keyless = keyless ? 1 : 0;
+            op.pad_bc = bs.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
+            op.P = make_src(st, ps, js);
+            if (!keyless) op.B = make_src(st, bs, js);
+            BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
+            RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
+            op.out_cursor = counters->as<unsigned long long>();
+            const uint32_t stride_grid = (uint32_t)std::min<uint64_t>((ps.rel->n + JN_SUB - 1) / JN_SUB,
+                                                                      (uint64_t)ctx->compute_units() * 8);
+            Parted   PB, PP;
+            BufP     tasks;
+            uint32_t max_tasks = 0;
+            if (!bcast) {
+                PB = partition(&op.B, nullptr, KW, bs.CW, bits);
+                PP = partition(&op.P, nullptr, KW, ps.CW, bits);
+                max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
+                tasks = ctx->buf((uint64_t)max_tasks * 12);
+                launch_heavy_tasks_zeroed(PB, PP, tasks, counters, max_tasks);
+                op.Bw = PB.w;
+                op.Pw = PP.w;
+                op.offB = PB.off->as<uint32_t>();
+                op.offP = PP.off->as<uint32_t>();
+                op.NP = PB.NP;
+                op.radix_bits = bits;
+                op.packB = PB.packed ? 1 : 0;
+                op.aosB = PB.aos3 ? 1 : 0;
+                op.packP = PP.packed ? 1 : 0;
+                op.aosP = PP.aos3 ? 1 : 0;
+                op.heavy_tasks = tasks->as<uint32_t>();
+                op.n_heavy = counters->as<uint32_t>() + 2;
+                op.heavy_grid = max_tasks;
+            }
+
+            // The result holds at least the preserved rows and may hold many more (dup x dup): the
+            // inner join's protocol — count on the device, run the probe once more with the exact size.
+            const int key_mode = st.need_key_stream ? stream_mode_of(st.is_root, KW * 4, true) : ST_NONE;
+            uint64_t  cap = std::min<uint64_t>(std::max(st.cap_hint, ps.rel->n) + 1024, 0xfffffff0ull);
+            BufP            key_stream;
+            uint64_t        nrows = 0;
+            std::set<void*> finished;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                key_stream = key_mode != ST_NONE ? ctx->buf(stream_bytes(key_mode, cap)) : BufP();
+                for (Side* s : {&st.ls, &st.rs})
+                    s->stream = s->stream_mode != ST_NONE ? ctx->buf(stream_bytes(s->stream_mode, cap)) : BufP();
+                RJ_HIP(hipMemsetAsync(counters->p, 0, 8, ctx->stream));
+                op.key = OutStream{key_stream ? key_stream->as<uint8_t>() : nullptr, key_mode, 0};
+                op.bc = OutStream{bs.stream ? bs.stream->as<uint8_t>() : nullptr, bs.stream_mode, 0};
+                op.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
+                op.out_cap = cap;
+                if (bcast) {
+                    launch_outer_bcast(L, KW, bs.CW, ps.CW, op, stride_grid);
+                } else {
+                    launch_outer_join(L, KW, bs.CW, ps.CW, op, max_tasks + PB.NP);
+                    // the rows the first radix pass dropped: NULL keys, FP64 NaN keys
+                    if (op.P.key.valid || op.P.key_f64) launch_outer_nullkeys(L, KW, ps.CW, op, stride_grid);
+                }
+                finished.clear();
+                finish_paged_streams(st, key_stream, key_mode, counters, cap, finished);
+                unsigned long long h = 0;
+                RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
+                ctx->sync();
+                nrows = h;
+                if (nrows <= cap) break;
+                if (nrows > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "outer join result exceeds 2^32 rows (%llu)", h);
+                if (attempt == 1) throw_fmt(RJ_ERR_DEVICE, "outer join output overflowed twice");
+                cap = nrows;  // exact size, run the probe again
+            }
+            return join_assemble(st, js, key_stream, key_mode, nrows, finished, root_res);
+        }
+
         // Build + probe over co-partitioned tuples (PB / PP; nullptr = broadcast join straight
         // from the children's columns), output streams, late materialisation, result pages.
         Rel join_finish(JoinState& st, const JoinSpec& js, const Parted* PBp, const Parted* PPp,
@@ -1279,7 +1396,7 @@ class Exec {
             BufP buf;           // where this column's values/pages live
             int  buf_mode = ST_NONE;
             BufP valid;
-            if ((uint64_t)c == s.key_col && st.need_key_stream) {
+            if ((uint64_t)c == s.key_col && st.need_key_stream && !s.optional) {
                 buf = key_stream;
                 buf_mode = key_mode;
             } else if (s.carry_mode == CARRY_COLUMN) {
@@ -1293,7 +1410,14 @@ class Exec {
             } else {
                 // generic path: gather the child column through the row-index stream
                 const uint32_t* idx = s.stream->as<uint32_t>();
-                if (src.kind == COL_IOTA) {
+                if (s.optional) {
+                    // an outer join's optional side: the row ids of padded rows are OUTER_NO_ROW, which
+                    // k_outer_gather turns into NULLs without reading a row (the relation may be empty)
+                    buf_mode = src.width == 4 ? ST_DENSE32 : ST_DENSE64;
+                    buf = ctx->buf(stream_bytes(buf_mode, std::max<uint64_t>(nrows, 1)));
+                    valid = ctx->buf(std::max<uint64_t>(nrows, 1));
+                    launch_outer_gather(L, src.ref(), idx, nrows, buf->as<uint8_t>(), valid->as<uint8_t>());
+                } else if (src.kind == COL_IOTA) {
                     buf = s.stream;  // row ids of the base table ARE the stream
                     buf_mode = ST_DENSE32;
                 } else {
@@ -1636,9 +1760,11 @@ class ShardedExec {
                 });
             return r;
         }
-        if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI)
+        if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: %s join nodes run on one device",
-                      n.kind == RJ_NODE_SEMI ? "semi (RJ_NODE_SEMI)" : "anti (RJ_NODE_ANTI)");
+                      n.kind == RJ_NODE_SEMI   ? "semi (RJ_NODE_SEMI)"
+                      : n.kind == RJ_NODE_ANTI ? "anti (RJ_NODE_ANTI)"
+                                               : "outer (RJ_NODE_OUTER)");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -2025,6 +2151,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
                                           : "an anti join node (RJ_NODE_ANTI) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_OUTER) {
+        if (why) *why = "an outer join node (RJ_NODE_OUTER) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -2089,6 +2219,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI)
         throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds %s join node; semi and anti joins run on one device",
                   n.kind == RJ_NODE_SEMI ? "a semi (RJ_NODE_SEMI)" : "an anti (RJ_NODE_ANTI)");
+    if (n.kind == RJ_NODE_OUTER)
+        throw_fmt(RJ_ERR_UNSUPPORTED,
+                  "rj_execute_sharded: the plan holds an outer (RJ_NODE_OUTER) join node; outer joins run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

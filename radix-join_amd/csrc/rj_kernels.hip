@@ -2615,6 +2615,383 @@ __global__ __launch_bounds__(JN_THREADS) void k_filter_join(FilterParams fp) {
     }
 }
 
+// ============================================================ outer joins
+// RJ_NODE_OUTER: the inner join's rows (duplicates multiply) plus, ONCE, every preserved row that
+// has no partner, with NULL in the optional (build) side's columns.  Both halves come out of one
+// pass over the preserved tuples and through one output cursor.
+// The LDS table is k_join_bcast's: buckets of four slots with an insert counter each (a slot is
+// valid when its index is below the counter; a counter above 4 sends the walk on to the next
+// bucket), key words + a REFERENCE to the build tuple (its row in the child for k_outer_bcast, its
+// index in the partitioned arrays for k_outer_join).  The optional side's carry is fetched through
+// the reference on emit: a few KB per table, cache resident.  (KW + 1) * 32 KiB + 8 KiB of LDS:
+// 72 KiB (two workgroups per CU) for 32-bit keys, 104 KiB (one) for 64-bit keys.
+// The home bucket is the multiplicative hash of the key words: their low radix bits are the same
+// for a whole partition, the product's high bits are not.
+// A padded row carries "NULL" in-band (rj_device.hpp, OuterParams): the build carry's first word is
+// op.pad_bc, the others zero.
+template <int KW>
+struct OuterTable {
+    static constexpr uint32_t NB = JN_CAP / 4, BMASK = NB - 1, LOG2 = ilog2_u32(NB);
+    uint32_t (*w)[JN_CAP];  // [KW + 1]
+    uint32_t* cnt;          // [NB]
+
+    __device__ __forceinline__ static uint32_t home(uint32_t lo, uint32_t hi) {
+        return ((lo ^ hi) * 0x9e3779b1u) >> (32 - LOG2);
+    }
+    // every thread of the workgroup; the caller puts a barrier behind it
+    __device__ __forceinline__ void clear() const {
+        for (uint32_t i = threadIdx.x; i < NB; i += blockDim.x) cnt[i] = 0;
+    }
+    // at most JN_RMAX inserts per table (load <= 50 %), so the walk ends
+    __device__ __forceinline__ void insert(uint32_t lo, uint32_t hi, uint32_t ref) const {
+        uint32_t b = home(lo, hi);
+        while (true) {
+            const uint32_t pos = atomicAdd(&cnt[b], 1u);
+            if (pos < 4) {
+                const uint32_t slot = b * 4 + pos;
+                w[0][slot] = lo;
+                if constexpr (KW == 2) w[1][slot] = hi;
+                w[KW][slot] = ref;
+                return;
+            }
+            b = (b + 1) & BMASK;
+        }
+    }
+    // matches of one key in bucket b: bit mask over its valid slots; `more`: the bucket overflowed
+    __device__ __forceinline__ uint32_t match(uint32_t b, uint32_t lo, uint32_t hi, bool& more) const {
+        const uint32_t c = cnt[b];
+        const uint4    kv = *reinterpret_cast<const uint4*>(&w[0][b * 4]);
+        uint32_t       eq = (uint32_t)(kv.x == lo) | ((uint32_t)(kv.y == lo) << 1) | ((uint32_t)(kv.z == lo) << 2) |
+                      ((uint32_t)(kv.w == lo) << 3);
+        if constexpr (KW == 2) {
+            const uint4 hv = *reinterpret_cast<const uint4*>(&w[1][b * 4]);
+            eq &= (uint32_t)(hv.x == hi) | ((uint32_t)(hv.y == hi) << 1) | ((uint32_t)(hv.z == hi) << 2) |
+                  ((uint32_t)(hv.w == hi) << 3);
+        }
+        more = c > 4;
+        return eq & ((1u << min(c, 4u)) - 1u);
+    }
+};
+
+// One tuple of a partitioned relation (the layouts partition() writes: 12-byte tuples, 8-byte
+// pairs, or word arrays whose last two carry words are one pair array).
+template <int KW, int CW>
+__device__ __forceinline__ void part_tuple(const Words& W, int pack, int aos, uint32_t idx, uint32_t (&t)[KW + CW]) {
+    constexpr int NW = KW + CW;
+    if constexpr (KW == 1 && CW == 2) {
+        if (aos) {
+            const uint32_t* p = W.w[0] + (size_t)idx * 3u;
+            t[0] = p[0];
+            t[1] = p[1];
+            t[2] = p[2];
+            return;
+        }
+    }
+    if constexpr (KW == 1 && CW == 1) {
+        if (pack) {
+            const uint2 v = reinterpret_cast<const uint2*>(W.w[0])[idx];
+            t[0] = v.x;
+            t[1] = v.y;
+            return;
+        }
+    }
+    constexpr int NA = CW >= 2 ? NW - 2 : NW;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) t[a] = W.w[a][idx];
+    if constexpr (CW >= 2) {
+        const uint2 v = reinterpret_cast<const uint2*>(W.w[NA])[idx];
+        t[NA] = v.x;
+        t[NA + 1] = v.y;
+    }
+}
+
+// Probe SPT items per thread against the table and emit: every match of an item with probe[j]
+// set, and one padded row for an item with padrow[j] set that has no match now and had none
+// before (hit[j], which is updated).  Offsets from the wave ballots (a shuffle scan where some lane
+// has several matches), ONE global reservation for the workgroup; rows beyond the stream capacity
+// are counted, not written (the host runs the probe again with exact-size streams).
+// bcarry(ref, b0, b1, b2) / pcarry(j, p0, p1, p2) deliver the carries.  Contains barriers: every
+// thread of the workgroup calls it.
+template <int KW, int CWB, int CWP, int SPT, class BCarry, class PCarry>
+__device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTable<KW>& T, const bool (&probe)[SPT],
+                                           const bool (&padrow)[SPT], bool (&hit)[SPT], const uint32_t (&klo)[SPT],
+                                           const uint32_t (&khi)[SPT], uint32_t* s_wtot, unsigned long long* s_obase,
+                                           BCarry bcarry, PCarry pcarry) {
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint32_t       m[SPT], cnt[SPT], pre[SPT], wave_total = 0;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        m[j] = 0;
+        if (probe[j]) {
+            uint32_t b = OuterTable<KW>::home(klo[j], khi[j]);
+            bool     more;
+            do {
+                m[j] += (uint32_t)__popc(T.match(b, klo[j], khi[j], more));
+                b = (b + 1) & OuterTable<KW>::BMASK;
+            } while (more);
+        }
+        hit[j] = hit[j] || m[j] != 0;
+        cnt[j] = m[j] ? m[j] : ((padrow[j] && !hit[j]) ? 1u : 0u);
+    }
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        uint32_t tot;
+        if (__ballot(cnt[j] > 1) == 0) {
+            const uint64_t mk = __ballot(cnt[j] == 1);
+            pre[j] = lane_prefix(mk);
+            tot = (uint32_t)__popcll(mk);
+        } else {
+            uint32_t incl = cnt[j];
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t t = __shfl_up(incl, off);
+                if (lane >= (uint32_t)off) incl += t;
+            }
+            pre[j] = incl - cnt[j];
+            tot = __shfl(incl, 63);
+        }
+        pre[j] += wave_total;
+        wave_total += tot;
+    }
+    if (lane == 0) s_wtot[wid] = wave_total;
+    lds_barrier();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (uint32_t w = 0; w < nw; ++w) tot += s_wtot[w];
+        *s_obase = tot ? atomicAdd(op.out_cursor, (unsigned long long)tot) : 0ull;
+    }
+    lds_barrier();
+    const uint64_t gbase = *s_obase;
+    uint64_t       obase = gbase;
+    uint32_t       block_total = 0;
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint32_t t = s_wtot[w];
+        if (w < wid) obase += t;
+        block_total += t;
+    }
+    if (gbase + block_total <= op.out_cap) {
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            if (cnt[j] == 0) continue;
+            uint64_t row = obase + pre[j];
+            uint32_t k0 = 0, k1 = 0;
+            if (op.key.mode != ST_NONE) {
+                if constexpr (KW == 1) {
+                    k0 = unfmix32(klo[j]);
+                } else {
+                    const uint64_t k64 = unfmix64((uint64_t)klo[j] | ((uint64_t)khi[j] << 32));
+                    k0 = (uint32_t)k64;
+                    k1 = (uint32_t)(k64 >> 32);
+                }
+            }
+            uint32_t p0 = 0, p1 = 0, p2 = 0;
+            if constexpr (CWP >= 1) pcarry(j, p0, p1, p2);
+            if (m[j] == 0) {  // no partner in any round: the padded row
+                stream_store(op.key, row, k0, k1);
+                if constexpr (CWB >= 1) stream_store(op.bc, row, op.pad_bc, 0u, 0u);
+                if constexpr (CWP >= 1) stream_store(op.pc, row, p0, p1, p2);
+                continue;
+            }
+            uint32_t b = OuterTable<KW>::home(klo[j], khi[j]);
+            bool     more;
+            do {
+                uint32_t eq = T.match(b, klo[j], khi[j], more);
+                while (eq) {
+                    const uint32_t slot = b * 4 + (uint32_t)__builtin_ctz(eq);
+                    eq &= eq - 1;
+                    stream_store(op.key, row, k0, k1);
+                    if constexpr (CWB >= 1) {
+                        uint32_t b0, b1, b2;
+                        bcarry(T.w[KW][slot], b0, b1, b2);
+                        stream_store(op.bc, row, b0, b1, b2);
+                    }
+                    if constexpr (CWP >= 1) stream_store(op.pc, row, p0, p1, p2);
+                    ++row;
+                }
+                b = (b + 1) & OuterTable<KW>::BMASK;
+            } while (more);
+        }
+    }
+    lds_barrier();  // s_wtot / s_obase are reused by the next call
+}
+
+// Broadcast form: an optional side of at most JN_RMAX rows.  Every workgroup builds the SAME table
+// straight from the optional child's key column (page decode, NULL / NaN drop, hashing on the way)
+// and streams a grid-strided slice of the preserved child past it.  A preserved row whose key is
+// NULL or NaN has no partner and comes out padded here.  keyless (the key types differ) or an
+// empty optional side: no key is read or no tuple inserted, every row comes out padded.
+template <int KW, int CWB, int CWP>
+__global__ __launch_bounds__(JN_THREADS) void k_outer_bcast(OuterParams op) {
+    __shared__ __attribute__((aligned(16))) uint32_t t_w[KW + 1][JN_CAP];
+    __shared__ __attribute__((aligned(16))) uint32_t t_cnt[JN_CAP / 4];
+    __shared__ uint32_t s_wtot[JN_THREADS / 64];
+    __shared__ unsigned long long s_obase;
+    const OuterTable<KW> T{t_w, t_cnt};
+    T.clear();
+    lds_barrier();
+    if (!op.keyless) {
+        for (uint32_t r = threadIdx.x; r < op.B.n_rows; r += JN_THREADS) {
+            uint32_t lo, hi;
+            if (src_key<KW>(op.B, r, lo, hi)) T.insert(lo, hi, r);
+        }
+    }
+    lds_barrier();
+    const uint32_t n = op.P.n_rows;
+    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
+        uint32_t klo[JN_SPT], khi[JN_SPT];
+        bool     probe[JN_SPT], padrow[JN_SPT], hit[JN_SPT];
+#pragma unroll
+        for (int j = 0; j < JN_SPT; ++j) {
+            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
+            klo[j] = khi[j] = 0;
+            hit[j] = false;
+            padrow[j] = row < n;
+            probe[j] = row < n && !op.keyless && src_key<KW>(op.P, (uint32_t)row, klo[j], khi[j]);
+        }
+        outer_emit<KW, CWB, CWP, JN_SPT>(
+            op, T, probe, padrow, hit, klo, khi, s_wtot, &s_obase,
+            [&](uint32_t ref, uint32_t& b0, uint32_t& b1, uint32_t& b2) { src_carry<CWB>(op.B, ref, b0, b1, b2); },
+            [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
+                src_carry<CWP>(op.P, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), p0, p1, p2);
+            });
+    }
+}
+
+// The partitioned path's leftovers: the preserved rows the first radix pass drops (NULL key; FP64
+// NaN key) have no partner, so they come out padded.  Grid-strided over the preserved child, the
+// same tuple formation (src_key / src_carry over the TupleSrc) and output cursor as the probe.
+template <int KW, int CWP>
+__global__ __launch_bounds__(JN_THREADS) void k_outer_nullkeys(OuterParams op) {
+    __shared__ uint32_t s_wtot[JN_THREADS / 64];
+    __shared__ unsigned long long s_obase;
+    const OuterTable<KW> T{nullptr, nullptr};  // (nothing is probed)
+    const uint32_t       n = op.P.n_rows;
+    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
+        uint32_t klo[JN_SPT], khi[JN_SPT];
+        bool     probe[JN_SPT], padrow[JN_SPT], hit[JN_SPT];
+#pragma unroll
+        for (int j = 0; j < JN_SPT; ++j) {
+            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
+            klo[j] = khi[j] = 0;
+            probe[j] = hit[j] = false;
+            padrow[j] = row < n && !src_key<KW>(op.P, (uint32_t)row, klo[j], khi[j]);
+        }
+        // (the build carry's width is a run-time property of op.bc here: 1 stands for "some")
+        outer_emit<KW, 1, CWP, JN_SPT>(
+            op, T, probe, padrow, hit, klo, khi, s_wtot, &s_obase,
+            [&](uint32_t, uint32_t& b0, uint32_t& b1, uint32_t& b2) { b0 = b1 = b2 = 0; },
+            [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
+                src_carry<CWP>(op.P, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), p0, p1, p2);
+            });
+    }
+}
+
+// Partitioned form: one workgroup per co-partition, or per heavy task of a preserved partition
+// above JN_HEAVY tuples (k_heavy_tasks; every task sees its partition's whole build side, and a
+// partition WITHOUT build tuples stays with its main workgroup, which pads it whole).  The loop
+// order is k_filter_join's: a JN_SUB-tuple chunk of preserved tuples stays in registers while the
+// partition's build tuples pass by in table rounds of JN_RMAX tuples; every round emits its
+// matches, a per-tuple "matched in some round" flag is OR-ed over the rounds, and the LAST round
+// also emits the padded rows of the tuples that never matched.  The usual partition needs one
+// round, i.e. one reservation per chunk.  No memory outside the registers holds a flag.
+template <int KW, int CWB, int CWP>
+__global__ __launch_bounds__(JN_THREADS) void k_outer_join(OuterParams op) {
+    constexpr int TH = JN_THREADS, SPT = JN_SPT, SUB = JN_SUB, SW = KW + CWP, BW = KW + CWB;
+    static_assert(SPT * TH == SUB, "sub-chunk geometry");
+    __shared__ __attribute__((aligned(16))) uint32_t t_w[KW + 1][JN_CAP];
+    __shared__ __attribute__((aligned(16))) uint32_t t_cnt[JN_CAP / 4];
+    __shared__ uint32_t s_wtot[TH / 64];
+    __shared__ unsigned long long s_obase;
+    const OuterTable<KW> T{t_w, t_cnt};
+
+    uint32_t q, sbeg, send;
+    if (blockIdx.x < op.heavy_grid) {
+        if (blockIdx.x >= *op.n_heavy) return;
+        q = op.heavy_tasks[3 * blockIdx.x + 0];
+        sbeg = op.heavy_tasks[3 * blockIdx.x + 1];
+        send = op.heavy_tasks[3 * blockIdx.x + 2];
+    } else {
+        q = blockIdx.x - op.heavy_grid;
+        if (q >= op.NP) return;
+        sbeg = op.offP[q];
+        send = op.offP[q + 1];
+        if (send - sbeg > JN_HEAVY && op.offB[q + 1] != op.offB[q]) return;  // split into heavy tasks
+    }
+    const uint32_t rbeg = op.offB[q], rend = op.offB[q + 1];
+    if (sbeg >= send) return;
+
+    // one round of the table: build tuples [from, from + JN_RMAX); returns where the round ended
+    auto build_round = [&](uint32_t from) -> uint32_t {
+        lds_barrier();  // nobody still probes the previous round
+        T.clear();
+        lds_barrier();
+        const uint32_t to = from + min((uint32_t)JN_RMAX, rend - from);
+        for (uint32_t i = from + threadIdx.x; i < to; i += TH) {
+            uint32_t t[BW];
+            part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, i, t);
+            T.insert(t[0], KW == 2 ? t[KW - 1] : 0u, i);
+        }
+        lds_barrier();
+        return to;
+    };
+
+    uint32_t       sw[SPT][SW];
+    const uint32_t first_end = build_round(rbeg);
+    const bool     one_round = first_end == rend;
+    for (uint32_t sc = sbeg; sc < send; sc += SUB) {
+        const uint32_t sn = min((uint32_t)SUB, send - sc);
+        uint32_t       klo[SPT], khi[SPT];
+        bool           in[SPT], padrow[SPT], hit[SPT];
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            // (items past the chunk re-read its last tuple; they are masked off)
+            part_tuple<KW, CWP>(op.Pw, op.packP, op.aosP, sc + min((uint32_t)(j * TH + threadIdx.x), sn - 1u), sw[j]);
+            klo[j] = sw[j][0];
+            khi[j] = KW == 2 ? sw[j][KW - 1] : 0u;
+            in[j] = (uint32_t)(j * TH + threadIdx.x) < sn;
+            hit[j] = false;
+        }
+        uint32_t end = (one_round || sc == sbeg) ? first_end : build_round(rbeg);
+        while (true) {
+            const bool last = end == rend;
+#pragma unroll
+            for (int j = 0; j < SPT; ++j) padrow[j] = last && in[j];
+            outer_emit<KW, CWB, CWP, SPT>(
+                op, T, in, padrow, hit, klo, khi, s_wtot, &s_obase,
+                [&](uint32_t ref, uint32_t& b0, uint32_t& b1, uint32_t& b2) {
+                    uint32_t t[BW];
+                    part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, ref, t);
+                    b0 = CWB >= 1 ? t[KW < BW ? KW : 0] : 0u;
+                    b1 = CWB >= 2 ? t[KW + 1 < BW ? KW + 1 : 0] : 0u;
+                    b2 = CWB == 3 ? t[BW - 1] : 0u;
+                },
+                [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
+                    p0 = CWP >= 1 ? sw[j][KW < SW ? KW : 0] : 0u;
+                    p1 = CWP >= 2 ? sw[j][KW + 1 < SW ? KW + 1 : 0] : 0u;
+                    p2 = CWP == 3 ? sw[j][SW - 1] : 0u;
+                });
+            if (last) break;
+            end = build_round(end);
+        }
+    }
+}
+
+// k_gather for the row-index stream of an outer join's optional side: OUTER_NO_ROW (a padded row)
+// is never dereferenced and gives a NULL; every row gets a validity byte.
+template <int WIDTH>
+__global__ __launch_bounds__(256) void k_outer_gather(ColRef src, const uint32_t* idx, uint64_t n, uint8_t* dst,
+                                                      uint8_t* dst_valid) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t r = idx[i];
+    const bool     there = r != OUTER_NO_ROW;
+    if (WIDTH == 4)
+        reinterpret_cast<uint32_t*>(dst)[i] = there ? col_load32(src, r) : 0u;
+    else
+        reinterpret_cast<uint64_t*>(dst)[i] = there ? col_load64(src, r) : 0ull;
+    dst_valid[i] = there ? (src.valid ? src.valid[r] : (uint8_t)1) : (uint8_t)0;
+}
+
 // ================================================================== K7 gather
 // Late materialisation: out[i] = column[idx[i]] (reference counterpart: the
 // per-row `out.push_back(lrow[ci])`, src/execute.cpp:236-242).
@@ -3234,6 +3611,64 @@ void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, co
     RJ_FILTER_DISPATCH("filter_nullkeys", k_filter_nullkeys)
 }
 #undef RJ_FILTER_DISPATCH
+
+// outer joins: KW 1 with 0..3 optional and 0..3 preserved carry words, KW 2 with 0..2 of each
+#define RJ_OUTER_ROW(NAME, KERNEL, KW, CWB, C0)                                                       \
+    case C0 + 0: RJ_KLAUNCH(L, NAME, (KERNEL<KW, CWB, 0>), grid, JN_THREADS, op); break;              \
+    case C0 + 1: RJ_KLAUNCH(L, NAME, (KERNEL<KW, CWB, 1>), grid, JN_THREADS, op); break;              \
+    case C0 + 2: RJ_KLAUNCH(L, NAME, (KERNEL<KW, CWB, 2>), grid, JN_THREADS, op); break;
+#define RJ_OUTER_DISPATCH(NAME, KERNEL)                                                               \
+    if (!grid) return;                                                                                \
+    switch (key_words * 100 + cw_optional * 10 + cw_preserved) {                                      \
+        RJ_OUTER_ROW(NAME, KERNEL, 1, 0, 100)                                                         \
+    case 103: RJ_KLAUNCH(L, NAME, (KERNEL<1, 0, 3>), grid, JN_THREADS, op); break;                    \
+        RJ_OUTER_ROW(NAME, KERNEL, 1, 1, 110)                                                         \
+    case 113: RJ_KLAUNCH(L, NAME, (KERNEL<1, 1, 3>), grid, JN_THREADS, op); break;                    \
+        RJ_OUTER_ROW(NAME, KERNEL, 1, 2, 120)                                                         \
+    case 123: RJ_KLAUNCH(L, NAME, (KERNEL<1, 2, 3>), grid, JN_THREADS, op); break;                    \
+        RJ_OUTER_ROW(NAME, KERNEL, 1, 3, 130)                                                         \
+    case 133: RJ_KLAUNCH(L, NAME, (KERNEL<1, 3, 3>), grid, JN_THREADS, op); break;                    \
+        RJ_OUTER_ROW(NAME, KERNEL, 2, 0, 200)                                                         \
+        RJ_OUTER_ROW(NAME, KERNEL, 2, 1, 210)                                                         \
+        RJ_OUTER_ROW(NAME, KERNEL, 2, 2, 220)                                                         \
+    default: launch_failed(NAME, "no kernel for this key/carry word count", true);                    \
+    }
+
+void launch_outer_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
+                        uint32_t grid) {
+    RJ_OUTER_DISPATCH("outer_broadcast", k_outer_bcast)
+}
+
+void launch_outer_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
+                       uint32_t grid) {
+    RJ_OUTER_DISPATCH("outer_probe", k_outer_join)
+}
+#undef RJ_OUTER_DISPATCH
+#undef RJ_OUTER_ROW
+
+void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, const OuterParams& op, uint32_t grid) {
+    if (!grid) return;
+    switch (key_words * 10 + cw_preserved) {
+    case 10: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 0>), grid, JN_THREADS, op); break;
+    case 11: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 1>), grid, JN_THREADS, op); break;
+    case 12: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 2>), grid, JN_THREADS, op); break;
+    case 13: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 3>), grid, JN_THREADS, op); break;
+    case 20: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<2, 0>), grid, JN_THREADS, op); break;
+    case 21: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<2, 1>), grid, JN_THREADS, op); break;
+    case 22: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<2, 2>), grid, JN_THREADS, op); break;
+    default: launch_failed("outer_nullkeys", "no kernel for this key/carry word count", true);
+    }
+}
+
+void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
+                         uint8_t* dst_valid) {
+    if (!n) return;
+    const uint32_t grid = (uint32_t)((n + 255) / 256);
+    if (src.width == 4)
+        RJ_KLAUNCH(L, "outer_gather", (k_outer_gather<4>), grid, 256, src, idx, n, dst, dst_valid);
+    else
+        RJ_KLAUNCH(L, "outer_gather", (k_outer_gather<8>), grid, 256, src, idx, n, dst, dst_valid);
+}
 
 void launch_debug_stall(const Launch& L, uint32_t ms) {
     int dev = 0, khz = 0;

@@ -125,6 +125,22 @@ void launch_filter_join(const Launch& L, int key_words, int cw_preserved, const 
 // FP64 NaN key) go out through the same cursor
 void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid);
 
+// ---- outer joins (OuterParams): key_words 1 or 2; cw_optional 0 (nothing), 1 (row index) or the
+// words of a wide carry; cw_preserved 0..MAX_WORDS - key_words
+// broadcast: optional side of at most JN_RMAX rows (or none / keys of another type)
+void launch_outer_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
+                        uint32_t grid);
+// partitioned: grid = op.heavy_grid + op.NP (one workgroup per heavy task, then per partition)
+void launch_outer_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
+                       uint32_t grid);
+// after the partitioned probe: the preserved rows the first radix pass drops (NULL key, FP64 NaN
+// key) go out padded through the same cursor
+void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, const OuterParams& op, uint32_t grid);
+// k_gather for an optional side's row-index stream: OUTER_NO_ROW gives a NULL (valid byte 0, value
+// 0) and is never dereferenced; dense values and validity bytes for every row
+void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
+                         uint8_t* dst_valid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

@@ -49,7 +49,7 @@ class JoinNode:
 
 
 # rj_node_kind (include/rj.h)
-NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI = 0, 1, 2, 3
+NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER = 0, 1, 2, 3, 4
 
 
 @dataclass
@@ -58,6 +58,19 @@ class FilterJoinNode:
     (or have no) partner in the filter child.  build_left picks the filter side; output_attrs may
     name columns of the preserved side only (include/rj.h)."""
     kind: int
+    build_left: bool
+    left: int
+    right: int
+    left_attr: int
+    right_attr: int
+
+
+@dataclass
+class OuterJoinNode:
+    """Outer join (kind NODE_OUTER): the inner join's rows plus every row of the preserved child
+    without a partner, once, with NULL in the optional child's columns.  build_left picks the
+    OPTIONAL side (the one that is built); output_attrs may name columns of both sides
+    (include/rj.h)."""
     build_left: bool
     left: int
     right: int
@@ -90,6 +103,14 @@ class Plan:
         """WHERE NOT EXISTS: rows of the preserved child whose key has no partner in the filter
         child (NULL and NaN keys included)."""
         return self._filter_node(NODE_ANTI, build_left, left, right, left_attr, right_attr, output_attrs)
+
+    def new_outer_join_node(self, build_left, left, right, left_attr, right_attr, output_attrs):
+        """LEFT / RIGHT OUTER JOIN.  build_left names the optional side (NULL where a preserved row
+        has no partner): `left LEFT JOIN right` is build_left=False, `left RIGHT JOIN right` is
+        build_left=True."""
+        node = OuterJoinNode(bool(build_left), left, right, left_attr, right_attr)
+        self.nodes.append(PlanNode(node, list(output_attrs)))
+        return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
         node = FilterJoinNode(kind, bool(build_left), left, right, left_attr, right_attr)
@@ -292,8 +313,11 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
         nd.n_out = k
         nd.out_idx = C.cast(idx, C.POINTER(C.c_uint64))
         nd.out_type = C.cast(typ, C.POINTER(C.c_int32))
-        if isinstance(n.data, (JoinNode, FilterJoinNode)):
-            nd.kind = n.data.kind if isinstance(n.data, FilterJoinNode) else NODE_JOIN
+        if isinstance(n.data, (JoinNode, FilterJoinNode, OuterJoinNode)):
+            if isinstance(n.data, FilterJoinNode):
+                nd.kind = n.data.kind
+            else:
+                nd.kind = NODE_OUTER if isinstance(n.data, OuterJoinNode) else NODE_JOIN
             nd.build_left = 1 if n.data.build_left else 0
             nd.left, nd.right = n.data.left, n.data.right
             nd.left_attr, nd.right_attr = n.data.left_attr, n.data.right_attr
