@@ -110,13 +110,41 @@ typedef enum rj_status {
  *   may join on a nullable column an outer join produced (NULL keys drop out as always).
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.
+ *   A library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Full outer joins (FULL OUTER JOIN; no reference counterpart).
+ * RJ_NODE_FULL uses the fields of a join:
+ *   build_left picks which child is BUILT; the other child is PROBED.  It is an execution hint
+ *   only: the result is the same multiset either way (the executor builds an empty child whatever
+ *   the hint says).  out_idx indexes concat(left outputs, right outputs) and may name columns of
+ *   both sides, in any order, repeated or not, possibly none of one side.
+ *   Result: the union of (1) the inner join's rows (same key rules: the key type is the built
+ *   side's; INT32 / INT64 compare by value, FP64 by bit pattern; NULL and NaN match nothing;
+ *   duplicates multiply on both sides), (2) for every row of the probed child without a partner,
+ *   one row with that child's columns and NULL in every column of the built child, and (3) for
+ *   every row of the built child without a partner, one row with that child's columns and NULL in
+ *   every column of the probed child.  "Without a partner" is what ANTI and OUTER mean by it, on
+ *   both sides: the key is NULL, is an FP64 NaN, or equals no key of the other side; when the two
+ *   key columns have different types, every row of both children is unmatched.
+ *   A key column that is output is the key of the side it belongs to: that row's own key, NULL
+ *   included, and NULL in the rows padded on that side.  There is no COALESCE column.
+ *   An empty child gives every row of the other child, padded; two empty children give 0 rows with
+ *   the declared column types and zero pages.  The result is a multiset in no particular order.
+ *   Every output column keeps its declared type and is nullable, whatever the source column is.
+ *   VARCHAR keys (on either side) are RJ_ERR_UNSUPPORTED, and so is a VARCHAR column of EITHER
+ *   side in out_idx (both sides are optional: see RJ_NODE_OUTER).  Malformed nodes are RJ_ERR_ARG.
+ *   The kind nests freely under and over joins, semi / anti joins, outer joins and itself; a
+ *   parent may join on a nullable column it produced (NULL keys drop out as always).
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.
  *   A library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").               */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
     RJ_NODE_JOIN = 1,
     RJ_NODE_SEMI = 2, /* preserved rows with a partner on the filter side    */
     RJ_NODE_ANTI = 3, /* preserved rows without one                          */
-    RJ_NODE_OUTER = 4 /* inner join + unmatched preserved rows, NULL-padded  */
+    RJ_NODE_OUTER = 4, /* inner join + unmatched preserved rows, NULL-padded */
+    RJ_NODE_FULL = 5   /* inner join + unmatched rows of BOTH sides, padded  */
 } rj_node_kind;
 
 typedef struct rj_node {
@@ -331,14 +359,15 @@ void     rj_result_free(rj_result* r);
  * all ranks' shards is the input.  out[d] receives local device d's slice of the result (rows
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
- * side (the BASELINE shape), and no node is a semi, anti or outer join; others return
+ * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join; others return
  * RJ_ERR_UNSUPPORTED.                                                                         */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
- * only: needs neither a context nor a GPU.  A plan that holds a semi, anti or outer join is not
- * shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER).           */
+ * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
+ * join is not shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER /
+ * RJ_NODE_FULL).                                                                               */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

@@ -325,4 +325,18 @@ struct OuterParams {
     uint64_t        out_cap;      // rows that fit the streams; rows beyond are counted, not written
 };
 
+// ---- Full outer joins (RJ_NODE_FULL): an outer join's rows plus every BUILD row without a partner,
+// once, with NULL in the probed side's columns.  Both carries follow the optional rules above
+// (`pad_pc` is to the probed carry what OuterParams::pad_bc is to the build carry) and no key
+// stream is written.  `flags` holds one "matched" bit per build tuple (bit i = tuple i of the
+// partitioned build arrays, or row i of the built child on the broadcast path), zeroed once per
+// node; the probe kernels OR their matches in, the kernels launched after them emit the tuples
+// whose bit stayed clear.
+struct FullParams {
+    OuterParams     o;
+    uint32_t*       flags;
+    uint32_t        pad_pc;       // OUTER_NO_ROW (row-index carry) or 0 (wide carry)
+    int32_t         use_flags;    // k_full_buildrows: 1 = also emit the rows whose flag is clear (broadcast)
+};
+
 }  // namespace rj

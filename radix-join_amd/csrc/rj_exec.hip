@@ -302,7 +302,8 @@ class Exec {
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
         if (n.kind == RJ_NODE_SCAN) return scan(n);
-        if (n.kind != RJ_NODE_JOIN && n.kind != RJ_NODE_SEMI && n.kind != RJ_NODE_ANTI && n.kind != RJ_NODE_OUTER)
+        if (n.kind != RJ_NODE_JOIN && n.kind != RJ_NODE_SEMI && n.kind != RJ_NODE_ANTI && n.kind != RJ_NODE_OUTER &&
+            n.kind != RJ_NODE_FULL)
             throw_fmt(RJ_ERR_ARG, "bad node kind");
         Rel      l = node(n.left, nullptr, depth + 1);
         Rel      r = node(n.right, nullptr, depth + 1);
@@ -314,6 +315,7 @@ class Exec {
         js.out_type.assign(n.out_type, n.out_type + n.n_out);
         js.forced_bits = ctx->radix_bits_override;
         if (n.kind == RJ_NODE_OUTER) return outer_join(l, r, js, root_res);
+        if (n.kind == RJ_NODE_FULL) return full_join(l, r, js, root_res);
         if (n.kind != RJ_NODE_JOIN) return filter_join(l, r, js, n.kind == RJ_NODE_ANTI, root_res);
         return join_core(l, r, js, root_res);
     }
@@ -786,7 +788,8 @@ class Exec {
         // shared_nulls (sharded joins): {left, right} null_columns() OR-ed over all ranks
         // filter_kind: RJ_NODE_JOIN, or RJ_NODE_SEMI / RJ_NODE_ANTI (filter_join: the build side is the
         // filter side, it carries nothing), or RJ_NODE_OUTER (outer_join: the build side is the
-        // optional side, whose columns are nullable in the result)
+        // optional side, whose columns are nullable in the result), or RJ_NODE_FULL (full_join: both
+        // sides are optional)
         void join_prepare(Rel& left, Rel& right, const JoinSpec& js, bool is_root, JoinState& st,
                           const uint64_t* shared_nulls = nullptr, int filter_kind = RJ_NODE_JOIN) {
             const size_t lw = left.cols.size(), rw = right.cols.size();
@@ -830,12 +833,14 @@ class Exec {
             // An outer join emits unmatched rows as ANTI does, so the preserved key follows ANTI's rule;
             // the optional side's key column is NULL in those rows and never comes from the key stream:
             // it travels as one of that side's payload columns.
-            const bool outer = filter_kind == RJ_NODE_OUTER;
+            const bool full = filter_kind == RJ_NODE_FULL;
+            const bool outer = filter_kind == RJ_NODE_OUTER || full;
             const bool emits_unmatched = filter_kind == RJ_NODE_ANTI || outer;
             const bool key_stream_ok =
                 filter_kind == RJ_NODE_JOIN ||
                 (!st.type_mismatch && !(emits_unmatched && st.ps().rel->cols[st.ps().key_col].valid));
             st.bs().optional = outer;
+            st.ps().optional = full;  // (so neither side's key column comes from the key stream)
             // Which child columns must each side deliver?
             for (size_t k = 0; k < js.out_idx.size(); ++k) {
                 bool  is_left = js.out_idx[k] < lw;
@@ -1171,6 +1176,139 @@ class Exec {
                 cap = nrows;  // exact size, run the probe again
             }
             return join_assemble(st, js, key_stream, key_mode, nrows, finished, root_res);
+        }
+
+        // Full outer join (RJ_NODE_FULL, semantics in rj.h): an outer join whose probed side is
+        // optional too.  The probe kernels are the outer join's with one addition: every build tuple
+        // that matched gets its bit set in `flags` (HBM, one bit per build tuple, zeroed once per
+        // node; a rerun sets the same bits again).  A second phase in the same stream then emits the
+        // build tuples whose bit stayed clear, and the build rows the table never saw (NULL / NaN
+        // keys), with the probed side's carry padded.  NULL travels in-band in BOTH carries.
+        Rel full_join(Rel& left, Rel& right, const JoinSpec& js_in, Result* root_res) {
+            for (int side = 0; side < 2; ++side) {
+                const Rel&     r = side == 0 ? left : right;
+                const uint64_t a = side == 0 ? js_in.left_attr : js_in.right_attr;
+                if (a < r.cols.size() && r.cols[a].type == RJ_VARCHAR)
+                    throw_fmt(RJ_ERR_UNSUPPORTED, "full outer join on a VARCHAR key");
+            }
+            // what the node may output is a property of the plan, not of the data: a malformed node and
+            // a VARCHAR output column are refused whatever the children hold
+            auto refuse_varchar_outputs = [](JoinState& s) {
+                for (Side* sd : {&s.ls, &s.rs})
+                    for (int c : sd->need)
+                        if (sd->rel->cols[c].type == RJ_VARCHAR)
+                            throw_fmt(RJ_ERR_UNSUPPORTED,
+                                      "full outer join: a VARCHAR column in the output is not supported (%s child column %d)",
+                                      sd == &s.ls ? "left" : "right", c);
+            };
+            if (left.n == 0 && right.n == 0) {
+                JoinState chk;
+                join_prepare(left, right, js_in, root_res != nullptr, chk, nullptr, RJ_NODE_FULL);
+                refuse_varchar_outputs(chk);
+                return empty_rel(js_in, root_res);
+            }
+            // build_left is a hint: an empty probed side would leave the probe kernels without work
+            // and the partitioner without tuples, so the empty child is the one that is built
+            JoinSpec js = js_in;
+            if ((js.build_left ? right : left).n == 0) js.build_left = !js.build_left;
+            JoinState st;
+            join_prepare(left, right, js, root_res != nullptr, st, nullptr, RJ_NODE_FULL);
+            Side&     bs = st.bs();
+            Side&     ps = st.ps();
+            const int KW = st.KW;
+            refuse_varchar_outputs(st);
+            prepare_wide(bs);
+            prepare_wide(ps);
+            plan_carry_streams(st);
+            const bool keyless = st.type_mismatch;
+            const bool bcast = (bs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && ctx->tune.bcast != 0) ||
+                               bs.rel->n == 0 || keyless;
+            const uint32_t bits = join_bits(js, bs.rel->n);
+            if (ctx->tune.diag >= 2)
+                fprintf(stderr, "[rj diag] full outer join built=%llu probed=%llu %s bits=%u cw=%d/%d\n",
+                        (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
+                        bits, bs.CW, ps.CW);
+
+            FullParams   fp{};
+            OuterParams& op = fp.o;
+            op.keyless = keyless ? 1 : 0;
+            op.pad_bc = bs.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
+            fp.pad_pc = ps.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
+            op.P = make_src(st, ps, js);
+            op.B = make_src(st, bs, js);  // (keyless: its key is never read, its carry is)
+            BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
+            RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
+            op.out_cursor = counters->as<unsigned long long>();
+            const uint64_t max_grid = (uint64_t)ctx->compute_units() * 8;
+            const uint32_t stride_grid = (uint32_t)std::min<uint64_t>((ps.rel->n + JN_SUB - 1) / JN_SUB, max_grid);
+            const uint32_t build_grid = (uint32_t)std::min<uint64_t>((bs.rel->n + JN_SUB - 1) / JN_SUB, max_grid);
+            Parted   PB, PP;
+            BufP     tasks;
+            uint32_t max_tasks = 0;
+            if (!bcast) {
+                PB = partition(&op.B, nullptr, KW, bs.CW, bits);
+                PP = partition(&op.P, nullptr, KW, ps.CW, bits);
+                max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
+                tasks = ctx->buf((uint64_t)max_tasks * 12);
+                launch_heavy_tasks_zeroed(PB, PP, tasks, counters, max_tasks);
+                op.Bw = PB.w;
+                op.Pw = PP.w;
+                op.offB = PB.off->as<uint32_t>();
+                op.offP = PP.off->as<uint32_t>();
+                op.NP = PB.NP;
+                op.radix_bits = bits;
+                op.packB = PB.packed ? 1 : 0;
+                op.aosB = PB.aos3 ? 1 : 0;
+                op.packP = PP.packed ? 1 : 0;
+                op.aosP = PP.aos3 ? 1 : 0;
+                op.heavy_tasks = tasks->as<uint32_t>();
+                op.n_heavy = counters->as<uint32_t>() + 2;
+                op.heavy_grid = max_tasks;
+            }
+            // one matched bit per build tuple (partitioned: by index in PB's arrays; broadcast: by row
+            // of the built child), whole words, one spare word for the round that ends unaligned
+            const uint64_t flag_bytes = ((bcast ? (uint64_t)JN_RMAX : PB.n_tuples) / 32 + 2) * 4;
+            BufP           flags = ctx->buf(flag_bytes);
+            RJ_HIP(hipMemsetAsync(flags->p, 0, flag_bytes, ctx->stream));
+            fp.flags = flags->as<uint32_t>();
+            fp.use_flags = bcast ? 1 : 0;
+
+            // every row of both sides may come out, and dup x dup may exceed that: the inner join's
+            // protocol — count on the device, run the probe once more with the exact size
+            uint64_t cap = std::min<uint64_t>(std::max(st.cap_hint, bs.rel->n + ps.rel->n) + 1024, 0xfffffff0ull);
+            uint64_t nrows = 0;
+            std::set<void*> finished;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                for (Side* s : {&st.ls, &st.rs})
+                    s->stream = s->stream_mode != ST_NONE ? ctx->buf(stream_bytes(s->stream_mode, cap)) : BufP();
+                RJ_HIP(hipMemsetAsync(counters->p, 0, 8, ctx->stream));
+                op.key = OutStream{nullptr, ST_NONE, 0};
+                op.bc = OutStream{bs.stream ? bs.stream->as<uint8_t>() : nullptr, bs.stream_mode, 0};
+                op.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
+                op.out_cap = cap;
+                if (bcast) {
+                    launch_full_bcast(L, KW, bs.CW, ps.CW, fp, stride_grid);
+                    // unmatched build rows and build rows without a usable key, in one sweep
+                    launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
+                } else {
+                    launch_full_join(L, KW, bs.CW, ps.CW, fp, max_tasks + PB.NP);
+                    launch_full_unmatched(L, KW, bs.CW, fp, build_grid);
+                    // the rows the first radix pass dropped (NULL keys, FP64 NaN keys), either side
+                    if (op.P.key.valid || op.P.key_f64) launch_outer_nullkeys(L, KW, ps.CW, op, stride_grid);
+                    if (op.B.key.valid || op.B.key_f64) launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
+                }
+                finished.clear();
+                unsigned long long h = 0;
+                RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
+                ctx->sync();
+                nrows = h;
+                if (nrows <= cap) break;
+                if (nrows > 0xfffffff0ull)
+                    throw_fmt(RJ_ERR_UNSUPPORTED, "full outer join result exceeds 2^32 rows (%llu)", h);
+                if (attempt == 1) throw_fmt(RJ_ERR_DEVICE, "full outer join output overflowed twice");
+                cap = nrows;  // exact size, run the probe again
+            }
+            return join_assemble(st, js, BufP(), ST_NONE, nrows, finished, root_res);
         }
 
         // Build + probe over co-partitioned tuples (PB / PP; nullptr = broadcast join straight
@@ -1760,11 +1898,12 @@ class ShardedExec {
                 });
             return r;
         }
-        if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER)
+        if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER || n.kind == RJ_NODE_FULL)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: %s join nodes run on one device",
-                      n.kind == RJ_NODE_SEMI   ? "semi (RJ_NODE_SEMI)"
-                      : n.kind == RJ_NODE_ANTI ? "anti (RJ_NODE_ANTI)"
-                                               : "outer (RJ_NODE_OUTER)");
+                      n.kind == RJ_NODE_SEMI    ? "semi (RJ_NODE_SEMI)"
+                      : n.kind == RJ_NODE_ANTI  ? "anti (RJ_NODE_ANTI)"
+                      : n.kind == RJ_NODE_OUTER ? "outer (RJ_NODE_OUTER)"
+                                                : "full outer (RJ_NODE_FULL)");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -2155,6 +2294,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "an outer join node (RJ_NODE_OUTER) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_FULL) {
+        if (why) *why = "a full outer join node (RJ_NODE_FULL) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -2222,6 +2365,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_OUTER)
         throw_fmt(RJ_ERR_UNSUPPORTED,
                   "rj_execute_sharded: the plan holds an outer (RJ_NODE_OUTER) join node; outer joins run on one device");
+    if (n.kind == RJ_NODE_FULL)
+        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds a full outer (RJ_NODE_FULL) join node; full "
+                                      "outer joins run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

@@ -2712,11 +2712,16 @@ __device__ __forceinline__ void part_tuple(const Words& W, int pack, int aos, ui
 // are counted, not written (the host runs the probe again with exact-size streams).
 // bcarry(ref, b0, b1, b2) / pcarry(j, p0, p1, p2) deliver the carries.  Contains barriers: every
 // thread of the workgroup calls it.
-template <int KW, int CWB, int CWP, int SPT, class BCarry, class PCarry>
+// FULL (RJ_NODE_FULL, compile time): every matched build tuple is also recorded — bit
+// (ref - flag_base) of the workgroup's LDS words s_flag, which the caller merges into the node's
+// flags in HBM — and no key stream is written (a full outer join has none).  The counting loop
+// records, not the emitting one: a run that only counts (streams too small) flags all the same.
+template <bool FULL, int KW, int CWB, int CWP, int SPT, class BCarry, class PCarry>
 __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTable<KW>& T, const bool (&probe)[SPT],
                                            const bool (&padrow)[SPT], bool (&hit)[SPT], const uint32_t (&klo)[SPT],
                                            const uint32_t (&khi)[SPT], uint32_t* s_wtot, unsigned long long* s_obase,
-                                           BCarry bcarry, PCarry pcarry) {
+                                           BCarry bcarry, PCarry pcarry, uint32_t* s_flag = nullptr,
+                                           uint32_t flag_base = 0) {
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     uint32_t       m[SPT], cnt[SPT], pre[SPT], wave_total = 0;
 #pragma unroll
@@ -2726,7 +2731,16 @@ __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTab
             uint32_t b = OuterTable<KW>::home(klo[j], khi[j]);
             bool     more;
             do {
-                m[j] += (uint32_t)__popc(T.match(b, klo[j], khi[j], more));
+                uint32_t eq = T.match(b, klo[j], khi[j], more);
+                m[j] += (uint32_t)__popc(eq);
+                if constexpr (FULL) {
+                    while (eq) {
+                        const uint32_t bit = T.w[KW][b * 4 + (uint32_t)__builtin_ctz(eq)] - flag_base;
+                        eq &= eq - 1;
+                        // (a hot build tuple is flagged by many probes: look before the atomic)
+                        if (!((s_flag[bit >> 5] >> (bit & 31u)) & 1u)) atomicOr(&s_flag[bit >> 5], 1u << (bit & 31u));
+                    }
+                }
                 b = (b + 1) & OuterTable<KW>::BMASK;
             } while (more);
         }
@@ -2775,7 +2789,7 @@ __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTab
             if (cnt[j] == 0) continue;
             uint64_t row = obase + pre[j];
             uint32_t k0 = 0, k1 = 0;
-            if (op.key.mode != ST_NONE) {
+            if (!FULL && op.key.mode != ST_NONE) {
                 if constexpr (KW == 1) {
                     k0 = unfmix32(klo[j]);
                 } else {
@@ -2787,7 +2801,7 @@ __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTab
             uint32_t p0 = 0, p1 = 0, p2 = 0;
             if constexpr (CWP >= 1) pcarry(j, p0, p1, p2);
             if (m[j] == 0) {  // no partner in any round: the padded row
-                stream_store(op.key, row, k0, k1);
+                if constexpr (!FULL) stream_store(op.key, row, k0, k1);
                 if constexpr (CWB >= 1) stream_store(op.bc, row, op.pad_bc, 0u, 0u);
                 if constexpr (CWP >= 1) stream_store(op.pc, row, p0, p1, p2);
                 continue;
@@ -2799,7 +2813,7 @@ __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTab
                 while (eq) {
                     const uint32_t slot = b * 4 + (uint32_t)__builtin_ctz(eq);
                     eq &= eq - 1;
-                    stream_store(op.key, row, k0, k1);
+                    if constexpr (!FULL) stream_store(op.key, row, k0, k1);
                     if constexpr (CWB >= 1) {
                         uint32_t b0, b1, b2;
                         bcarry(T.w[KW][slot], b0, b1, b2);
@@ -2820,41 +2834,13 @@ __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTab
 // and streams a grid-strided slice of the preserved child past it.  A preserved row whose key is
 // NULL or NaN has no partner and comes out padded here.  keyless (the key types differ) or an
 // empty optional side: no key is read or no tuple inserted, every row comes out padded.
+// The body (rj_outer_bcast_body.inc) is shared with k_full_bcast (FULL, compile time): there the workgroup also keeps one
+// matched bit per build row in LDS (JN_RMAX bits) and ORs its non-zero words into gflags at the end.
 template <int KW, int CWB, int CWP>
 __global__ __launch_bounds__(JN_THREADS) void k_outer_bcast(OuterParams op) {
-    __shared__ __attribute__((aligned(16))) uint32_t t_w[KW + 1][JN_CAP];
-    __shared__ __attribute__((aligned(16))) uint32_t t_cnt[JN_CAP / 4];
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const OuterTable<KW> T{t_w, t_cnt};
-    T.clear();
-    lds_barrier();
-    if (!op.keyless) {
-        for (uint32_t r = threadIdx.x; r < op.B.n_rows; r += JN_THREADS) {
-            uint32_t lo, hi;
-            if (src_key<KW>(op.B, r, lo, hi)) T.insert(lo, hi, r);
-        }
-    }
-    lds_barrier();
-    const uint32_t n = op.P.n_rows;
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t klo[JN_SPT], khi[JN_SPT];
-        bool     probe[JN_SPT], padrow[JN_SPT], hit[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            klo[j] = khi[j] = 0;
-            hit[j] = false;
-            padrow[j] = row < n;
-            probe[j] = row < n && !op.keyless && src_key<KW>(op.P, (uint32_t)row, klo[j], khi[j]);
-        }
-        outer_emit<KW, CWB, CWP, JN_SPT>(
-            op, T, probe, padrow, hit, klo, khi, s_wtot, &s_obase,
-            [&](uint32_t ref, uint32_t& b0, uint32_t& b1, uint32_t& b2) { src_carry<CWB>(op.B, ref, b0, b1, b2); },
-            [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-                src_carry<CWP>(op.P, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), p0, p1, p2);
-            });
-    }
+    constexpr bool FULL = false;
+    uint32_t* const gflags = nullptr;
+#include "rj_outer_bcast_body.inc"
 }
 
 // The partitioned path's leftovers: the preserved rows the first radix pass drops (NULL key; FP64
@@ -2877,7 +2863,7 @@ __global__ __launch_bounds__(JN_THREADS) void k_outer_nullkeys(OuterParams op) {
             padrow[j] = row < n && !src_key<KW>(op.P, (uint32_t)row, klo[j], khi[j]);
         }
         // (the build carry's width is a run-time property of op.bc here: 1 stands for "some")
-        outer_emit<KW, 1, CWP, JN_SPT>(
+        outer_emit<false, KW, 1, CWP, JN_SPT>(
             op, T, probe, padrow, hit, klo, khi, s_wtot, &s_obase,
             [&](uint32_t, uint32_t& b0, uint32_t& b1, uint32_t& b2) { b0 = b1 = b2 = 0; },
             [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
@@ -2894,84 +2880,146 @@ __global__ __launch_bounds__(JN_THREADS) void k_outer_nullkeys(OuterParams op) {
 // matches, a per-tuple "matched in some round" flag is OR-ed over the rounds, and the LAST round
 // also emits the padded rows of the tuples that never matched.  The usual partition needs one
 // round, i.e. one reservation per chunk.  No memory outside the registers holds a flag.
+// The body (rj_outer_join_body.inc) is shared with k_full_join (FULL, compile time).  There the build tuples that matched
+// must be known AFTER the launch, across the heavy tasks of a partition and across table rounds:
+// the workgroup collects one bit per build tuple of the current round in LDS (FW words: JN_RMAX
+// bits from the 32-aligned index below the round's first tuple) and ORs the non-zero words into
+// gflags (one bit per tuple of the partitioned build arrays) before the table is rebuilt and when
+// the task ends — a few hundred vector atomics per task, not one per match.
 template <int KW, int CWB, int CWP>
 __global__ __launch_bounds__(JN_THREADS) void k_outer_join(OuterParams op) {
-    constexpr int TH = JN_THREADS, SPT = JN_SPT, SUB = JN_SUB, SW = KW + CWP, BW = KW + CWB;
-    static_assert(SPT * TH == SUB, "sub-chunk geometry");
-    __shared__ __attribute__((aligned(16))) uint32_t t_w[KW + 1][JN_CAP];
-    __shared__ __attribute__((aligned(16))) uint32_t t_cnt[JN_CAP / 4];
-    __shared__ uint32_t s_wtot[TH / 64];
-    __shared__ unsigned long long s_obase;
-    const OuterTable<KW> T{t_w, t_cnt};
+    constexpr bool FULL = false;
+    uint32_t* const gflags = nullptr;
+#include "rj_outer_join_body.inc"
+}
 
-    uint32_t q, sbeg, send;
-    if (blockIdx.x < op.heavy_grid) {
-        if (blockIdx.x >= *op.n_heavy) return;
-        q = op.heavy_tasks[3 * blockIdx.x + 0];
-        sbeg = op.heavy_tasks[3 * blockIdx.x + 1];
-        send = op.heavy_tasks[3 * blockIdx.x + 2];
-    } else {
-        q = blockIdx.x - op.heavy_grid;
-        if (q >= op.NP) return;
-        sbeg = op.offP[q];
-        send = op.offP[q + 1];
-        if (send - sbeg > JN_HEAVY && op.offB[q + 1] != op.offB[q]) return;  // split into heavy tasks
+// ======================================================= full outer joins
+// RJ_NODE_FULL: an outer join's rows plus, ONCE, every build row without a partner, with NULL in
+// the probed side's columns.  The probe kernels are the outer join's bodies with FULL set: they
+// write no key stream and leave one matched bit per build tuple in fp.flags.  The kernels below
+// run AFTER them in the same stream — the launch boundary makes every flag visible — and emit
+// the build rows through the same cursor and streams.
+template <int KW, int CWB, int CWP>
+__global__ __launch_bounds__(JN_THREADS) void k_full_bcast(FullParams fp) {
+    constexpr bool     FULL = true;
+    const OuterParams& op = fp.o;
+    uint32_t* const    gflags = fp.flags;
+#include "rj_outer_bcast_body.inc"
+}
+template <int KW, int CWB, int CWP>
+__global__ __launch_bounds__(JN_THREADS) void k_full_join(FullParams fp) {
+    constexpr bool     FULL = true;
+    const OuterParams& op = fp.o;
+    uint32_t* const    gflags = fp.flags;
+#include "rj_outer_join_body.inc"
+}
+
+// Rows for the items of one chunk a workgroup wants to emit: bit j of `emit` is the thread's item
+// j (lane-strided: item j of thread t is element j * JN_THREADS + t of the chunk).  Positions come
+// from the wave ballots, so the lanes of a wave write consecutive rows for each j; ONE reservation
+// on the output cursor per chunk.  Item j goes to row `first + pre[j]`; returns false when the
+// chunk's rows would pass the stream capacity (they are counted only).  Contains barriers: every
+// thread of the workgroup calls it.
+template <int SPT>
+__device__ __forceinline__ bool full_reserve(const OuterParams& op, uint32_t emit, uint32_t* s_wtot,
+                                             unsigned long long* s_obase, uint32_t (&pre)[SPT], uint64_t& first) {
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint32_t       wave_total = 0;
+#pragma unroll
+    for (int j = 0; j < SPT; ++j) {
+        const uint64_t mk = __ballot((emit >> j) & 1u);
+        pre[j] = wave_total + lane_prefix(mk);
+        wave_total += (uint32_t)__popcll(mk);
     }
-    const uint32_t rbeg = op.offB[q], rend = op.offB[q + 1];
-    if (sbeg >= send) return;
+    if (lane == 0) s_wtot[wid] = wave_total;
+    lds_barrier();
+    if (threadIdx.x == 0) {
+        uint32_t tot = 0;
+        for (uint32_t w = 0; w < nw; ++w) tot += s_wtot[w];
+        *s_obase = tot ? atomicAdd(op.out_cursor, (unsigned long long)tot) : 0ull;
+    }
+    lds_barrier();
+    const uint64_t gbase = *s_obase;
+    uint32_t       before = 0, total = 0;
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint32_t t = s_wtot[w];
+        if (w < wid) before += t;
+        total += t;
+    }
+    first = gbase + before;
+    lds_barrier();  // s_wtot / s_obase are reused by the next call
+    return gbase + total <= op.out_cap;
+}
 
-    // one round of the table: build tuples [from, from + JN_RMAX); returns where the round ended
-    auto build_round = [&](uint32_t from) -> uint32_t {
-        lds_barrier();  // nobody still probes the previous round
-        T.clear();
-        lds_barrier();
-        const uint32_t to = from + min((uint32_t)JN_RMAX, rend - from);
-        for (uint32_t i = from + threadIdx.x; i < to; i += TH) {
-            uint32_t t[BW];
-            part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, i, t);
-            T.insert(t[0], KW == 2 ? t[KW - 1] : 0u, i);
+// The build tuples nobody matched (partitioned path): a grid-strided walk over the partitioned
+// build arrays and the flags, lane-strided so that a wave reads 64 consecutive tuples and two flag
+// words per item and writes consecutive rows.  A tuple whose bit is clear comes out with its
+// carry as it is and the pad value (fp.pad_pc, then zeros) as the probed carry; which words the
+// probed carry stream takes is a run-time property of o.pc.
+template <int KW, int CWB>
+__global__ __launch_bounds__(JN_THREADS) void k_full_unmatched(FullParams fp) {
+    constexpr int BW = KW + CWB;
+    __shared__ uint32_t s_wtot[JN_THREADS / 64];
+    __shared__ unsigned long long s_obase;
+    const OuterParams& op = fp.o;
+    const uint32_t     n = op.offB[op.NP];
+    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
+        uint32_t emit = 0, pre[JN_SPT];
+#pragma unroll
+        for (int j = 0; j < JN_SPT; ++j) {
+            const uint64_t i = base + (uint64_t)j * JN_THREADS + threadIdx.x;
+            if (i < n) emit |= (uint32_t)!((fp.flags[i >> 5] >> (i & 31u)) & 1u) << j;
         }
-        lds_barrier();
-        return to;
-    };
+        uint64_t first;
+        if (!full_reserve<JN_SPT>(op, emit, s_wtot, &s_obase, pre, first)) continue;
+#pragma unroll
+        for (int j = 0; j < JN_SPT; ++j) {
+            if (!((emit >> j) & 1u)) continue;
+            const uint64_t row = first + pre[j];
+            if constexpr (CWB >= 1) {
+                uint32_t t[BW];
+                part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), t);
+                stream_store(op.bc, row, t[KW < BW ? KW : 0], CWB >= 2 ? t[KW + 1 < BW ? KW + 1 : 0] : 0u,
+                             CWB == 3 ? t[BW - 1] : 0u);
+            }
+            stream_store(op.pc, row, fp.pad_pc, 0u, 0u);
+        }
+    }
+}
 
-    uint32_t       sw[SPT][SW];
-    const uint32_t first_end = build_round(rbeg);
-    const bool     one_round = first_end == rend;
-    for (uint32_t sc = sbeg; sc < send; sc += SUB) {
-        const uint32_t sn = min((uint32_t)SUB, send - sc);
-        uint32_t       klo[SPT], khi[SPT];
-        bool           in[SPT], padrow[SPT], hit[SPT];
+// Build rows straight from the built child's column: those whose key is missing (NULL; FP64 NaN;
+// any key when the key types differ) have no partner — the first radix pass dropped them, or the
+// broadcast table never held them — and, with fp.use_flags (broadcast path, flags by child row),
+// the rows whose flag stayed clear go out in the same sweep.
+template <int KW, int CWB>
+__global__ __launch_bounds__(JN_THREADS) void k_full_buildrows(FullParams fp) {
+    __shared__ uint32_t s_wtot[JN_THREADS / 64];
+    __shared__ unsigned long long s_obase;
+    const OuterParams& op = fp.o;
+    const uint32_t     n = op.B.n_rows;
+    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
+        uint32_t emit = 0, pre[JN_SPT];
 #pragma unroll
-        for (int j = 0; j < SPT; ++j) {
-            // (items past the chunk re-read its last tuple; they are masked off)
-            part_tuple<KW, CWP>(op.Pw, op.packP, op.aosP, sc + min((uint32_t)(j * TH + threadIdx.x), sn - 1u), sw[j]);
-            klo[j] = sw[j][0];
-            khi[j] = KW == 2 ? sw[j][KW - 1] : 0u;
-            in[j] = (uint32_t)(j * TH + threadIdx.x) < sn;
-            hit[j] = false;
+        for (int j = 0; j < JN_SPT; ++j) {
+            const uint64_t r = base + (uint64_t)j * JN_THREADS + threadIdx.x;
+            if (r >= n) continue;
+            uint32_t lo, hi;
+            bool     unmatched = op.keyless || !src_key<KW>(op.B, (uint32_t)r, lo, hi);
+            if (!unmatched && fp.use_flags) unmatched = !((fp.flags[r >> 5] >> (r & 31u)) & 1u);
+            emit |= (uint32_t)unmatched << j;
         }
-        uint32_t end = (one_round || sc == sbeg) ? first_end : build_round(rbeg);
-        while (true) {
-            const bool last = end == rend;
+        uint64_t first;
+        if (!full_reserve<JN_SPT>(op, emit, s_wtot, &s_obase, pre, first)) continue;
 #pragma unroll
-            for (int j = 0; j < SPT; ++j) padrow[j] = last && in[j];
-            outer_emit<KW, CWB, CWP, SPT>(
-                op, T, in, padrow, hit, klo, khi, s_wtot, &s_obase,
-                [&](uint32_t ref, uint32_t& b0, uint32_t& b1, uint32_t& b2) {
-                    uint32_t t[BW];
-                    part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, ref, t);
-                    b0 = CWB >= 1 ? t[KW < BW ? KW : 0] : 0u;
-                    b1 = CWB >= 2 ? t[KW + 1 < BW ? KW + 1 : 0] : 0u;
-                    b2 = CWB == 3 ? t[BW - 1] : 0u;
-                },
-                [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-                    p0 = CWP >= 1 ? sw[j][KW < SW ? KW : 0] : 0u;
-                    p1 = CWP >= 2 ? sw[j][KW + 1 < SW ? KW + 1 : 0] : 0u;
-                    p2 = CWP == 3 ? sw[j][SW - 1] : 0u;
-                });
-            if (last) break;
-            end = build_round(end);
+        for (int j = 0; j < JN_SPT; ++j) {
+            if (!((emit >> j) & 1u)) continue;
+            const uint64_t row = first + pre[j];
+            if constexpr (CWB >= 1) {
+                uint32_t b0, b1, b2;
+                src_carry<CWB>(op.B, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), b0, b1, b2);
+                stream_store(op.bc, row, b0, b1, b2);
+            }
+            stream_store(op.pc, row, fp.pad_pc, 0u, 0u);
         }
     }
 }
@@ -3643,8 +3691,39 @@ void launch_outer_join(const Launch& L, int key_words, int cw_optional, int cw_p
                        uint32_t grid) {
     RJ_OUTER_DISPATCH("outer_probe", k_outer_join)
 }
+
+// full outer joins: the outer join's 25 shapes, both carries optional
+void launch_full_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& op,
+                       uint32_t grid) {
+    RJ_OUTER_DISPATCH("full_broadcast", k_full_bcast)
+}
+
+void launch_full_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& op,
+                      uint32_t grid) {
+    RJ_OUTER_DISPATCH("full_probe", k_full_join)
+}
 #undef RJ_OUTER_DISPATCH
 #undef RJ_OUTER_ROW
+
+#define RJ_FULL_BUILD_DISPATCH(NAME, KERNEL)                                                          \
+    if (!grid) return;                                                                                \
+    switch (key_words * 10 + cw_built) {                                                              \
+    case 10: RJ_KLAUNCH(L, NAME, (KERNEL<1, 0>), grid, JN_THREADS, fp); break;                        \
+    case 11: RJ_KLAUNCH(L, NAME, (KERNEL<1, 1>), grid, JN_THREADS, fp); break;                        \
+    case 12: RJ_KLAUNCH(L, NAME, (KERNEL<1, 2>), grid, JN_THREADS, fp); break;                        \
+    case 13: RJ_KLAUNCH(L, NAME, (KERNEL<1, 3>), grid, JN_THREADS, fp); break;                        \
+    case 20: RJ_KLAUNCH(L, NAME, (KERNEL<2, 0>), grid, JN_THREADS, fp); break;                        \
+    case 21: RJ_KLAUNCH(L, NAME, (KERNEL<2, 1>), grid, JN_THREADS, fp); break;                        \
+    case 22: RJ_KLAUNCH(L, NAME, (KERNEL<2, 2>), grid, JN_THREADS, fp); break;                        \
+    default: launch_failed(NAME, "no kernel for this key/carry word count", true);                    \
+    }
+void launch_full_unmatched(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid) {
+    RJ_FULL_BUILD_DISPATCH("full_unmatched", k_full_unmatched)
+}
+void launch_full_buildrows(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid) {
+    RJ_FULL_BUILD_DISPATCH("full_buildrows", k_full_buildrows)
+}
+#undef RJ_FULL_BUILD_DISPATCH
 
 void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, const OuterParams& op, uint32_t grid) {
     if (!grid) return;

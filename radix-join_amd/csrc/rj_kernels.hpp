@@ -141,6 +141,22 @@ void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, con
 void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
                          uint8_t* dst_valid);
 
+// ---- full outer joins (FullParams): the outer join's shapes, both carries under the optional rules
+// (0 = nothing, 1 = row index, 2 / 3 = a wide record that ends in a validity word)
+// broadcast probe: built side of at most JN_RMAX rows (or none / keys of another type); ORs the
+// matched build rows into fp.flags (bit = row of the built child)
+void launch_full_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& fp,
+                       uint32_t grid);
+// partitioned probe: grid = fp.o.heavy_grid + fp.o.NP; ORs the matched build tuples into fp.flags
+// (bit = index in the partitioned build arrays)
+void launch_full_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& fp,
+                      uint32_t grid);
+// after the partitioned probe: the build tuples whose flag stayed clear, probed side padded
+void launch_full_unmatched(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid);
+// after a probe: the rows of the built child without a usable key (NULL, FP64 NaN, keyless) and —
+// fp.use_flags, broadcast — the rows whose flag stayed clear, probed side padded
+void launch_full_buildrows(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

@@ -299,7 +299,8 @@ static void scan_order(const rj_plan* plan, uint64_t idx, int depth, std::vector
             seen[n.base_table_id] = true;
             order.push_back(n.base_table_id);
         }
-    } else if (n.kind == RJ_NODE_JOIN || n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER) {
+    } else if (n.kind == RJ_NODE_JOIN || n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER ||
+               n.kind == RJ_NODE_FULL) {
         scan_order(plan, n.left, depth + 1, seen, order);
         scan_order(plan, n.right, depth + 1, seen, order);
     }

@@ -49,7 +49,7 @@ class JoinNode:
 
 
 # rj_node_kind (include/rj.h)
-NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER = 0, 1, 2, 3, 4
+NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL = 0, 1, 2, 3, 4, 5
 
 
 @dataclass
@@ -70,6 +70,19 @@ class OuterJoinNode:
     """Outer join (kind NODE_OUTER): the inner join's rows plus every row of the preserved child
     without a partner, once, with NULL in the optional child's columns.  build_left picks the
     OPTIONAL side (the one that is built); output_attrs may name columns of both sides
+    (include/rj.h)."""
+    build_left: bool
+    left: int
+    right: int
+    left_attr: int
+    right_attr: int
+
+
+@dataclass
+class FullOuterJoinNode:
+    """Full outer join (kind NODE_FULL): the inner join's rows plus every row of EITHER child
+    without a partner, once, with NULL in the other child's columns.  build_left picks the child
+    that is built, an execution hint only; output_attrs may name columns of both sides
     (include/rj.h)."""
     build_left: bool
     left: int
@@ -109,6 +122,13 @@ class Plan:
         has no partner): `left LEFT JOIN right` is build_left=False, `left RIGHT JOIN right` is
         build_left=True."""
         node = OuterJoinNode(bool(build_left), left, right, left_attr, right_attr)
+        self.nodes.append(PlanNode(node, list(output_attrs)))
+        return len(self.nodes) - 1
+
+    def new_full_outer_join_node(self, build_left, left, right, left_attr, right_attr, output_attrs):
+        """FULL OUTER JOIN.  build_left names the child that is built; the result does not depend
+        on it."""
+        node = FullOuterJoinNode(bool(build_left), left, right, left_attr, right_attr)
         self.nodes.append(PlanNode(node, list(output_attrs)))
         return len(self.nodes) - 1
 
@@ -313,9 +333,11 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
         nd.n_out = k
         nd.out_idx = C.cast(idx, C.POINTER(C.c_uint64))
         nd.out_type = C.cast(typ, C.POINTER(C.c_int32))
-        if isinstance(n.data, (JoinNode, FilterJoinNode, OuterJoinNode)):
+        if isinstance(n.data, (JoinNode, FilterJoinNode, OuterJoinNode, FullOuterJoinNode)):
             if isinstance(n.data, FilterJoinNode):
                 nd.kind = n.data.kind
+            elif isinstance(n.data, FullOuterJoinNode):
+                nd.kind = NODE_FULL
             else:
                 nd.kind = NODE_OUTER if isinstance(n.data, OuterJoinNode) else NODE_JOIN
             nd.build_left = 1 if n.data.build_left else 0
