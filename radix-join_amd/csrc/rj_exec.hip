@@ -89,6 +89,40 @@ struct JoinSpec {
     uint32_t              top_bits_taken = 0;  // high hash bits that are constant in this input
 };
 
+JoinSpec join_spec(const rj_node& n, int forced_bits) {
+    JoinSpec js;
+    js.build_left = n.build_left != 0;
+    js.left_attr = n.left_attr;
+    js.right_attr = n.right_attr;
+    js.out_idx.assign(n.out_idx, n.out_idx + n.n_out);
+    js.out_type.assign(n.out_type, n.out_type + n.n_out);
+    js.forced_bits = forced_bits;
+    return js;
+}
+
+// What tells the five join node kinds apart outside their own functions.  The build side of
+// SEMI / ANTI is the filter side (it carries nothing); an optional side's columns come out NULL in
+// the rows that have no partner on that side.
+struct JoinKind {
+    int         node;             // RJ_NODE_*
+    const char* name;             // in messages and diagnostics
+    bool        emits_unmatched;  // probe rows without a partner come out too
+    bool        build_optional, probe_optional;
+    int         attempts;         // of the probe: 1 = the first streams hold any result, 2 = rerun at the exact size
+};
+const JoinKind& join_kind(int node) {
+    static const JoinKind kinds[] = {
+        {RJ_NODE_JOIN, "join", false, false, false, 2},
+        {RJ_NODE_SEMI, "semi join", false, false, false, 1},
+        {RJ_NODE_ANTI, "anti join", true, false, false, 1},
+        {RJ_NODE_OUTER, "outer join", true, true, false, 2},
+        {RJ_NODE_FULL, "full outer join", true, true, true, 2},
+    };
+    for (const JoinKind& k : kinds)
+        if (k.node == node) return k;
+    throw_fmt(RJ_ERR_ARG, "bad node kind");
+}
+
 uint32_t ceil_log2(uint64_t v) {
     uint32_t b = 0;
     while ((uint64_t(1) << b) < v) ++b;
@@ -302,21 +336,13 @@ class Exec {
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
         if (n.kind == RJ_NODE_SCAN) return scan(n);
-        if (n.kind != RJ_NODE_JOIN && n.kind != RJ_NODE_SEMI && n.kind != RJ_NODE_ANTI && n.kind != RJ_NODE_OUTER &&
-            n.kind != RJ_NODE_FULL)
-            throw_fmt(RJ_ERR_ARG, "bad node kind");
-        Rel      l = node(n.left, nullptr, depth + 1);
-        Rel      r = node(n.right, nullptr, depth + 1);
-        JoinSpec js;
-        js.build_left = n.build_left != 0;
-        js.left_attr = n.left_attr;
-        js.right_attr = n.right_attr;
-        js.out_idx.assign(n.out_idx, n.out_idx + n.n_out);
-        js.out_type.assign(n.out_type, n.out_type + n.n_out);
-        js.forced_bits = ctx->radix_bits_override;
-        if (n.kind == RJ_NODE_OUTER) return outer_join(l, r, js, root_res);
-        if (n.kind == RJ_NODE_FULL) return full_join(l, r, js, root_res);
-        if (n.kind != RJ_NODE_JOIN) return filter_join(l, r, js, n.kind == RJ_NODE_ANTI, root_res);
+        const JoinKind& K = join_kind(n.kind);
+        Rel             l = node(n.left, nullptr, depth + 1);
+        Rel             r = node(n.right, nullptr, depth + 1);
+        const JoinSpec  js = join_spec(n, ctx->radix_bits_override);
+        if (n.kind == RJ_NODE_OUTER) return outer_join(l, r, js, K, root_res);
+        if (n.kind == RJ_NODE_FULL) return full_join(l, r, js, K, root_res);
+        if (n.kind != RJ_NODE_JOIN) return filter_join(l, r, js, K, root_res);
         return join_core(l, r, js, root_res);
     }
 
@@ -497,935 +523,866 @@ class Exec {
                 uint64_t gt = (uint64_t)pp.tiles_per_group * PT_TILE;
                 n_groups = (uint32_t)((n + gt - 1) / gt);
             } else {
-                    pp.tiles_per_group = tiles_per_group(n / nseg_in + 1, 16);
-                    // the last pass of 12-byte-tuple plans (one 384-byte-run output stream) does
-                    // better with short groups — 2 tiles per workgroup: 9.3-10.3 -> 8.9-9.1 ms per step
-                    // at 1 B rows; packed 8-byte tuples lose with them
-                    // (profiles/r03_l_later_pass_group_size_ab.log)
-                    if (P.aos3 && p + 1 == passes) pp.tiles_per_group = std::min<uint32_t>(pp.tiles_per_group, 2u);
-                    uint64_t gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                    if (ctx->tune.tpg2 > 0) {
-                        pp.tiles_per_group = (uint32_t)ctx->tune.tpg2;
-                        gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                    }
-                    n_groups = (uint32_t)(n / gt + nseg_in);  // upper bound; exact count lives on device
-                    if (ctx->tune.xcd_split && n >= (uint64_t)ctx->tune.xcd_min_rows) {
-                        pp.xcd_remap = 1;
-                        n_groups += 8;  // 8 * ceil(G / 8) workgroups
-                    }
-                    const uint32_t* in_off = first_preseg ? shape->seg_begin : seg_off->as<uint32_t>();
-                    grp_start = ctx->buf(((uint64_t)nseg_in + 1) * 4);
-                    launch_group_table(L, in_off, nseg_in, (uint32_t)gt, grp_start->as<uint32_t>(),
-                                       first_preseg ? shape->seg_end : nullptr);
-                    pp.nseg = nseg_in;
-                    pp.seg_off = in_off;
-                    pp.seg_end = first_preseg ? shape->seg_end : nullptr;
-                    pp.oseg_shift = first_preseg ? shape->oseg_shift : 0u;
-                    pp.grp_start = grp_start->as<uint32_t>();
+                pp.tiles_per_group = tiles_per_group(n / nseg_in + 1, 16);
+                // the last pass of 12-byte-tuple plans (one 384-byte-run output stream) does
+                // better with short groups — 2 tiles per workgroup: 9.3-10.3 -> 8.9-9.1 ms per step
+                // at 1 B rows; packed 8-byte tuples lose with them
+                // (profiles/r03_l_later_pass_group_size_ab.log)
+                if (P.aos3 && p + 1 == passes) pp.tiles_per_group = std::min<uint32_t>(pp.tiles_per_group, 2u);
+                uint64_t gt = (uint64_t)pp.tiles_per_group * PT_TILE;
+                if (ctx->tune.tpg2 > 0) {
+                    pp.tiles_per_group = (uint32_t)ctx->tune.tpg2;
+                    gt = (uint64_t)pp.tiles_per_group * PT_TILE;
                 }
-                BufP off, hist, cursor;  // this pass' partition offsets, bin totals, write cursors
-                if (fine) {  // offsets and cursors of both passes came out of the fine histogram
-                    off = p == 0 ? coarse_off : fine_off;
-                    cursor = p == 0 ? coarse_cursor : fine_cursor;
-                    pp.cursor = cursor->as<uint32_t>();
-                    pp.xcd_log2 = (p == 0 && fine_xcd) ? 3u : 0u;
-                } else {
-                    // sub-ranges per XCD only where a partition gets many runs (big inputs)
-                    pp.xcd_log2 = (ctx->tune.xcd_split && p == 0 && !preseg && n >= (uint64_t)ctx->tune.xcd_min_rows) ? 3u : 0u;
-                    hist = ctx->buf((bins << pp.xcd_log2) * 4);
-                    off = ctx->buf((bins + 1) * 4);
-                    cursor = ctx->buf((bins << pp.xcd_log2) * 4);
-                    RJ_HIP(hipMemsetAsync(hist->p, 0, (bins << pp.xcd_log2) * 4, ctx->stream));
-                    pp.hist = hist->as<uint32_t>();
-                    pp.cursor = cursor->as<uint32_t>();
-                    if (p == 1 && chunk_second) {
-                        // ---- histogram / scan / scatter of this pass, `mall_chunk` input segments at a time,
-                        // chunks alternating between the context's two compute streams: the scatter of a
-                        // chunk re-reads what its histogram launch has just pulled through the Infinity
-                        // Cache.  Segments never share bins, cursors or output ranges, so the chunks are
-                        // independent; grids are exact (the segment sizes are on the host by now).
-                        RJ_HIP(hipEventSynchronize(chunk_ev.e));
-                        const uint32_t* hoff = static_cast<const uint32_t*>(ctx->small_pinned());
-                        const uint64_t  gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                        std::vector<uint32_t> gstart(nseg_in + 1, 0);
-                        for (uint32_t sgi = 0; sgi < nseg_in; ++sgi)
-                            gstart[sgi + 1] = gstart[sgi] + (uint32_t)(((uint64_t)(hoff[sgi + 1] - hoff[sgi]) + gt - 1) / gt);
-                        Ev2 e_in, e_aux;
-                        e_in.make();
-                        e_aux.make();
-                        hipStream_t aux = ctx->aux_stream();
-                        RJ_HIP(hipEventRecord(e_in.e, ctx->stream));  // (behind the previous scatter and the bin memset)
-                        RJ_HIP(hipStreamWaitEvent(aux, e_in.e, 0));
-                        Launch L2 = L;
-                        L2.stream = aux;
-                        const uint32_t CH = (uint32_t)ctx->tune.mall_chunk;
-                        uint32_t       c = 0;
-                        for (uint32_t s0 = 0; s0 < nseg_in; s0 += CH, ++c) {
-                            const uint32_t s1 = std::min(nseg_in, s0 + CH), G = gstart[s1] - gstart[s0];
-                            const Launch& Lc = (c & 1u) ? L2 : L;
-                            PassParams    pc = pp;
-                            pc.nseg = s1 - s0;
-                            pc.seg_off = pp.seg_off + s0;
-                            pc.grp_start = pp.grp_start + s0;
-                            pc.grp_base = gstart[s0];
-                            pc.hist = pp.hist + (size_t)s0 * F;
-                            pc.cursor = pp.cursor + (size_t)s0 * F;
-                            const uint32_t grid = pp.xcd_remap ? ((G + 7u) & ~7u) : G;
-                            if (G) launch_pass_hist_packed(Lc, cur.w[0], pc, grid);
-                            // (empty segments still need their partition offsets)
-                            launch_scan_segments(Lc, pc.hist, pc.seg_off, pc.nseg, F, 0, off->as<uint32_t>() + (size_t)s0 * F, pc.cursor);
-                            if (G) launch_pass_scatter_packed(Lc, cur.w[0], pc, grid, nxt.w[0]);
-                        }
-                        RJ_HIP(hipEventRecord(e_aux.e, aux));
-                        RJ_HIP(hipStreamWaitEvent(ctx->stream, e_aux.e, 0));  // (before any buffer of this pass is reused)
-                        seg_off = off;
-                        nseg = (uint32_t)bins;
-                        shift += pbits[p];
-                        cur = nxt;
-                        cur_is_a = (p % 2 == 0);
-                        nxt = cur_is_a ? wb : wa;
-                        continue;
-                    }
-                    if (p == 0 && !ws)
-                        launch_pass_hist_src(L, src, KW, pp, n_groups);
-                    else if ((mid_side || packed_side) && p > 0)
-                        launch_pass_hist_digits(L, SIDE[(p - 1) % 2]->as<uint16_t>(), pp, n_groups);
-                    else if (aos_mid && p > 0)
-                        launch_pass_hist_aos3(L, MID[(p - 1) % 2]->as<uint32_t>(), pp, n_groups);
-                    else if (P.packed && blocked_mid && p > 0)
-                        launch_pass_hist_blocked(L, cur.w[0], pp, n_groups);
-                    else if (P.packed)
-                        launch_pass_hist_packed(L, cur.w[0], pp, n_groups);
-                    else
-                        launch_pass_hist_dense(L, cur, pp, n_groups);
-                    // (one workgroup per OUTPUT segment; its base = where that segment starts)
-                    launch_scan_segments(L, pp.hist, first_preseg ? shape->oseg_off : (p == 0 ? nullptr : pp.seg_off),
-                                         n_oseg, F, pp.xcd_log2, off->as<uint32_t>(), pp.cursor);
+                n_groups = (uint32_t)(n / gt + nseg_in);  // upper bound; exact count lives on device
+                if (ctx->tune.xcd_split && n >= (uint64_t)ctx->tune.xcd_min_rows) {
+                    pp.xcd_remap = 1;
+                    n_groups += 8;  // 8 * ceil(G / 8) workgroups
                 }
-                if (p == 0 && after_offsets) (*after_offsets)(off->as<uint32_t>());
-                // the second pass in chunks needs this pass' partition sizes on the HOST (exact grids per
-                // chunk): they leave now, before the scatter is enqueued, and are read while it runs
-                if (p == 0 && chunk_second) {
-                    if ((bins + 1) * 4 > Context::SMALL_PINNED / 4) throw_fmt(RJ_ERR_DEVICE, "chunked pass: too many segments");
-                    RJ_HIP(hipMemcpyAsync(ctx->small_pinned(), off->p, (bins + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-                    chunk_ev.make();
-                    RJ_HIP(hipEventRecord(chunk_ev.e, ctx->stream));
-                }
-                BufP pt_diag;
-                if (ctx->tune.diag >= 3) {  // phase stamps of the scatter (diagnostic build only)
-                    pt_diag = ctx->buf(8 * 8);
-                    RJ_HIP(hipMemsetAsync(pt_diag->p, 0, 64, ctx->stream));
-                    pp.diag = pt_diag->as<unsigned long long>();
-                }
-                struct DiagDump {
-                    Context* ctx; BufP b; uint32_t p; uint64_t n; bool aos;
-                    ~DiagDump() {
-                        if (!b) return;
-                        unsigned long long h[8];
-                        if (hipMemcpyAsync(h, b->p, 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return;
-                        (void)hipStreamSynchronize(ctx->stream);
-                        static const char* names[] = {"clear+tail", "load issue+hash", "rank+barrier", "reserve+scan",
-                                                      "stage A", "copy-out A", "stage B", "copy-out B"};
-                        double tot = 0;
-                        for (int i = 0; i < 8; ++i) tot += (double)h[i];
-                        if (tot <= 0) return;
-                        fprintf(stderr, "[rj diag] scatter pass %u over %llu tuples, phase shares (thread 0 cycles):", p, (unsigned long long)n);
-                        for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.1f%%", names[i], 100.0 * h[i] / tot);
-                        fprintf(stderr, "  (%.0f cycles per tile)\n", tot / ((double)n / PT_TILE));
-                    }
-                } diag_dump{ctx, pt_diag, p, n, false};
-                if (aos_mid) {
-                    const bool last = p + 1 == passes;
-                    Words      o{};
-                    o.w[0] = last ? waos.w[0] : MID[p % 2]->as<uint32_t>();
-                    if (!last && mid_side) {
-                        pp.side_out = SIDE[p % 2]->as<uint16_t>();
-                        pp.next_shift = shift + pbits[p];
-                        pp.next_mask = (1u << pbits[p + 1]) - 1u;
-                    }
-                    if (p == 0 && !ws)
-                        launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, o, true);
-                    else if (p == 0)
-                        launch_pass_scatter_dense(L, cur, P.NW, KW, pp, n_groups, o, true);
-                    else
-                        launch_pass_scatter_aos3(L, MID[(p - 1) % 2]->as<uint32_t>(), pp, n_groups, o.w[0]);
-                    nxt = o;
-                } else if (P.packed) {
-                    if (packed_side && p + 1 < passes) {
-                        pp.side_out = SIDE[p % 2]->as<uint16_t>();
-                        pp.next_shift = shift + pbits[p];
-                        pp.next_mask = (1u << pbits[p + 1]) - 1u;
-                    }
-                    const bool blk_out = blocked_mid && p + 1 < passes;
-                    if (p == 0 && !ws)
-                        launch_pass_scatter_src_packed(L, src, pp, n_groups, nxt.w[0], blk_out);
-                    else if (blocked_mid)
-                        launch_pass_scatter_blocked(L, cur.w[0], pp, n_groups, nxt.w[0], blk_out);
-                    else
-                        launch_pass_scatter_packed(L, cur.w[0], pp, n_groups, nxt.w[0]);
-                } else if (p == 0 && !ws) {
-                    launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, nxt, P.aos3 && p + 1 == passes);
-                } else {
-                    launch_pass_scatter_dense(L, cur, P.NW, pair_word, pp, n_groups, nxt,
-                                              P.aos3 && p + 1 == passes);
-                }
-                seg_off = off;
-                nseg = (uint32_t)bins;
-                shift += pbits[p];
-                cur = nxt;
-                cur_is_a = (p % 2 == 0);
-                nxt = cur_is_a ? wb : wa;
-                if (P.aos3 && p + 2 == passes) nxt = waos;  // the next pass is the last one
-                if (aos_mid) {
-                    // (MID / SIDE buffers of a pass are read by the next one only; they go back to
-                    // the block cache when this function returns — all on one stream)
-                }
+                const uint32_t* in_off = first_preseg ? shape->seg_begin : seg_off->as<uint32_t>();
+                grp_start = ctx->buf(((uint64_t)nseg_in + 1) * 4);
+                launch_group_table(L, in_off, nseg_in, (uint32_t)gt, grp_start->as<uint32_t>(),
+                                   first_preseg ? shape->seg_end : nullptr);
+                pp.nseg = nseg_in;
+                pp.seg_off = in_off;
+                pp.seg_end = first_preseg ? shape->seg_end : nullptr;
+                pp.oseg_shift = first_preseg ? shape->oseg_shift : 0u;
+                pp.grp_start = grp_start->as<uint32_t>();
             }
-            P.w = cur;
-            for (int a = 0; a < P.NW; ++a) P.wbuf[a] = cur_is_a ? A[a] : B[a];
-            if (P.aos3) P.wbuf[0] = AOS;
-            P.off = seg_off;
-            P.NP = nseg;
-            P.pbits = pbits;
-            if (shape && !shape->prior_bits.empty()) P.pbits.insert(P.pbits.begin(), shape->prior_bits.begin(), shape->prior_bits.end());
-            P.n_tuples = n;
-            return P;
-        }
-
-        // ---------------------------------------------------------------- join
-        struct Side {
-            Rel*          rel = nullptr;
-            uint64_t      key_col = 0;
-            std::set<int> need;       // referenced columns that are not served by the key stream
-            int           carry_mode = CARRY_NONE;
-            int           carry_col = -1;
-            int           CW = 0;
-            BufP          stream;     // emitted carry stream
-            int           stream_mode = ST_NONE;
-            // CARRY_WIDE: the carried columns in record order (a 64-bit one first), then — if any of
-            // them has NULLs — one word of validity bits (bit i = wide_cols[i] is non-NULL)
-            std::vector<int> wide_cols;
-            int              wide = WIDE_NONE;
-            int              valid_word = -1;
-            BufP             vword;  // the packed validity word per row of the child
-            struct WideOut {
-                BufP values, valid;
-                int  mode = ST_NONE;  // dense values, or — root columns without NULLs — Page images straight away
-            };
-            std::map<int, WideOut> wide_out;  // per carried column: what k_split_records produced
-            // A sharded join's ranks must cut their tuples alike, and whether a column needs a validity
-            // word depends on the DATA of a shard: columns that hold NULLs on ANY rank are nullable on
-            // every rank (bit c = column c; columns from 64 up count as nullable when `shared` is set)
-            uint64_t null_mask = 0;
-            bool     shared = false;
-            // the optional side of an outer join: every column it delivers can come out NULL (a padded
-            // row), whatever the source column holds
-            bool     optional = false;
-            bool     nullable(int c) const {
-                if (optional || rel->cols[c].valid != nullptr) return true;
-                return shared && (c >= 64 || ((null_mask >> c) & 1u));
-            }
-        };
-        // which of a relation's (first 64) columns hold NULLs here
-        static uint64_t null_columns(const Rel& r) {
-            uint64_t m = 0;
-            for (size_t c = 0; c < r.cols.size() && c < 64; ++c)
-                if (r.cols[c].valid != nullptr) m |= 1ull << c;
-            return m;
-        }
-
-        static uint64_t pages_for(uint64_t rows, int width) {
-            uint64_t rf = width == 4 ? ROWS32 : ROWS64;
-            return (rows + rf - 1) / rf;
-        }
-
-        Rel empty_rel(const JoinSpec& js, Result* root_res) {
-            Rel r;
-            r.n = 0;
-            for (size_t k = 0; k < js.out_type.size(); ++k) {
-                DCol d;
-                d.type = js.out_type[k];
-                d.kind = COL_DENSE;
-                d.width = d.type == RJ_INT32 || d.type == RJ_VARCHAR ? 4 : 8;
-                r.cols.push_back(d);
-            }
-            if (root_res) {
-                root_res->num_rows = 0;
-                for (size_t k = 0; k < js.out_type.size(); ++k) {
-                    ResultColumn rc;
-                    rc.type = js.out_type[k];
-                    root_res->cols.push_back(std::move(rc));
-                }
-            }
-            return r;
-        }
-
-        // What a JoinNode decides before any tuple moves: key type, which columns each side
-        // must deliver and how they travel (execute_hash_join, reference src/execute.cpp:266-282,
-        // and the head of hash_join_omp, :43-83).
-        struct JoinState {
-            Side     ls, rs;
-            bool     build_left = true, is_root = false, f64 = false, need_key_stream = false;
-            bool     type_mismatch = false;  // probe key of another type: no row can match (:65-71)
-            size_t   lw = 0, rw = 0;
-            int      KW = 1;
-            uint64_t cap_hint = 0;  // rows the output streams are sized for at the first attempt
-            // VARCHAR join keys (hash_join_omp<std::string>, src/execute.cpp:278): each side's
-            // relation is copied with one extra column — the 64-bit FNV-1a of the key strings —
-            // which the join runs on; `rows` remembers where every string sits for the
-            // byte-for-byte check of the joined pairs
-            bool vkey = false;
-            struct VKey {
-                Rel            rel;
-                BufP           rows, hash, valid;
-                const uint8_t* pages = nullptr;
-                uint32_t       n_pages = 0;
-            } vk[2];  // [0] = left, [1] = right
-            Side&    bs() { return build_left ? ls : rs; }
-            Side&    ps() { return build_left ? rs : ls; }
-        };
-
-        // shared_nulls (sharded joins): {left, right} null_columns() OR-ed over all ranks
-        // filter_kind: RJ_NODE_JOIN, or RJ_NODE_SEMI / RJ_NODE_ANTI (filter_join: the build side is the
-        // filter side, it carries nothing), or RJ_NODE_OUTER (outer_join: the build side is the
-        // optional side, whose columns are nullable in the result), or RJ_NODE_FULL (full_join: both
-        // sides are optional)
-        void join_prepare(Rel& left, Rel& right, const JoinSpec& js, bool is_root, JoinState& st,
-                          const uint64_t* shared_nulls = nullptr, int filter_kind = RJ_NODE_JOIN) {
-            const size_t lw = left.cols.size(), rw = right.cols.size();
-            st.lw = lw;
-            st.rw = rw;
-            st.is_root = is_root;
-            st.build_left = js.build_left;
-            if (js.left_attr >= lw || js.right_attr >= rw)
-                throw_fmt(RJ_ERR_ARG, "join: key attr out of range");
-            for (size_t k = 0; k < js.out_idx.size(); ++k) {
-                if (js.out_idx[k] >= lw + rw) throw_fmt(RJ_ERR_ARG, "join: output attr out of range");
-                const DCol& c = js.out_idx[k] < lw ? left.cols[js.out_idx[k]]
-                                                   : right.cols[js.out_idx[k] - lw];
-                if (c.type != js.out_type[k])
-                    throw_fmt(RJ_ERR_ARG, "join: declared type differs from the child column's type");
-            }
-            Side &ls = st.ls, &rs = st.rs;
-            ls.rel = &left;
-            ls.key_col = js.left_attr;
-            rs.rel = &right;
-            rs.key_col = js.right_attr;
-            if (shared_nulls) {
-                ls.shared = rs.shared = true;
-                ls.null_mask = shared_nulls[0];
-                rs.null_mask = shared_nulls[1];
-            }
-            const DCol& bk = st.bs().rel->cols[st.bs().key_col];
-            const DCol& pk = st.ps().rel->cols[st.ps().key_col];
-            // KeyType = build side's key type (:271-273)
-            if (bk.type < RJ_INT32 || bk.type > RJ_VARCHAR) throw_fmt(RJ_ERR_ARG, "Unsupported join type");
-            // probe values of another variant alternative are never valid (:65-71)
-            st.type_mismatch = pk.type != bk.type;
-            st.vkey = bk.type == RJ_VARCHAR && !st.type_mismatch;
-            st.KW = bk.type == RJ_INT32 ? 1 : 2;
-            st.f64 = bk.type == RJ_FP64;
-            // matching keys are bit-identical on both sides (FP64 included: bit-pattern equality,
-            // see SrcLoader::key2), so one emitted key stream serves either side's key column.
-            // A semi / anti join emits the preserved side's own key — through the key stream unless
-            // its type is not the key type (no key is read then) or ANTI may emit rows whose key is
-            // NULL (the stream has no validity): then the key column travels as a payload column.
-            // An outer join emits unmatched rows as ANTI does, so the preserved key follows ANTI's rule;
-            // the optional side's key column is NULL in those rows and never comes from the key stream:
-            // it travels as one of that side's payload columns.
-            const bool full = filter_kind == RJ_NODE_FULL;
-            const bool outer = filter_kind == RJ_NODE_OUTER || full;
-            const bool emits_unmatched = filter_kind == RJ_NODE_ANTI || outer;
-            const bool key_stream_ok =
-                filter_kind == RJ_NODE_JOIN ||
-                (!st.type_mismatch && !(emits_unmatched && st.ps().rel->cols[st.ps().key_col].valid));
-            st.bs().optional = outer;
-            st.ps().optional = full;  // (so neither side's key column comes from the key stream)
-            // Which child columns must each side deliver?
-            for (size_t k = 0; k < js.out_idx.size(); ++k) {
-                bool  is_left = js.out_idx[k] < lw;
-                Side& s = is_left ? ls : rs;
-                int   c = (int)(is_left ? js.out_idx[k] : js.out_idx[k] - lw);
-                if ((uint64_t)c == s.key_col && !st.vkey && key_stream_ok && !s.optional)
-                    st.need_key_stream = true;
-                else
-                    s.need.insert(c);  // (a VARCHAR key column is gathered like any other column)
-            }
-            for (Side* s : {&ls, &rs}) {
-                if (st.vkey) {  // both row indices are needed for the string comparison of the pairs
-                    s->carry_mode = CARRY_ROWIDX;
-                    s->CW = 1;
-                } else if (s->need.empty()) {
-                    s->carry_mode = CARRY_NONE;
-                    s->CW = 0;
-                } else if (s->need.size() == 1 && !s->nullable(*s->need.begin())) {
-                    s->carry_mode = CARRY_COLUMN;
-                    s->carry_col = *s->need.begin();
-                    s->CW = s->rel->cols[s->carry_col].width / 4;
-                } else if (plan_wide_carry(*s, st.KW)) {
-                    s->carry_mode = CARRY_WIDE;
-                } else {
-                    s->carry_mode = CARRY_ROWIDX;
-                    s->CW = 1;
-                }
-            }
-            st.cap_hint = std::max(left.n, right.n);
-        }
-
-        // Can the columns a side must deliver travel WITH the key (reference src/execute.cpp:236-242
-        // copies any column list per output row; here up to MAX_WORDS - KW carry words do the same
-        // without a row index to gather through afterwards)?  Layouts: two or three 32-bit words, or
-        // a 64-bit column followed by one 32-bit word; a validity word counts as a 32-bit word.
-        bool plan_wide_carry(Side& s, int KW) {
-            if (!ctx->tune.wide_carry || s.need.empty()) return false;
-            int  words = 0, n64 = 0;
-            bool any_null = false;
-            for (int c : s.need) {
-                const DCol& col = s.rel->cols[c];
-                if (col.width != 4 && col.width != 8) return false;
-                words += col.width / 4;
-                n64 += col.width == 8;
-                any_null = any_null || s.nullable(c);
-            }
-            if (any_null) ++words;
-            if (words < 2 || words > MAX_WORDS - KW || n64 > 1 || (n64 == 1 && words != 3)) return false;
-            s.wide_cols.clear();
-            for (int c : s.need)
-                if (s.rel->cols[c].width == 8) s.wide_cols.push_back(c);
-            for (int c : s.need)
-                if (s.rel->cols[c].width == 4) s.wide_cols.push_back(c);
-            s.wide = n64 ? WIDE_64_32 : WIDE_32S;
-            s.valid_word = any_null ? words - 1 : -1;
-            s.CW = words;
-            return true;
-        }
-
-        // validity bits of a wide carry's columns, one word per row (k_pack_validity); call once
-        // per join before the side's tuples are formed
-        void prepare_wide(Side& s) {
-            if (s.carry_mode != CARRY_WIDE || s.valid_word < 0 || s.rel->n == 0) return;
-            const uint8_t* v[3] = {nullptr, nullptr, nullptr};
-            for (size_t i = 0; i < s.wide_cols.size() && i < 3; ++i) v[i] = s.rel->cols[s.wide_cols[i]].valid;
-            s.vword = ctx->buf(s.rel->n * 4);
-            launch_pack_validity(L, v[0], v[1], v[2], (uint32_t)s.rel->n, s.vword->as<uint32_t>());
-        }
-
-        // radix bit plan from the build cardinality; `top_bits_taken` high hash bits are constant
-        // on this rank (a sharded join's rank digit): the plan stays below them
-        uint32_t join_bits(const JoinSpec& js, uint64_t build_n, uint32_t top_bits_taken = 0) {
-            uint32_t bits = js.forced_bits > 0 ? (uint32_t)js.forced_bits
-                                               : ceil_log2((build_n + JN_TARGET_BUILD - 1) / JN_TARGET_BUILD);
-            // a third pass costs 20 B/tuple more than slightly fuller tables: stay at two passes
-            // (2 * PT_MAXBITS bits) while the mean build partition still fits the LDS table with
-            // a margin (rare larger partitions are joined in table-sized chunks anyway)
-            if (js.forced_bits <= 0 && bits > 2 * PT_MAXBITS &&
-                (build_n >> (2 * PT_MAXBITS)) <= (uint64_t)(JN_RMAX * 0.95))
-                bits = 2 * PT_MAXBITS;
-            // (at most 21: three passes of 7 bits — what 2^32 build rows ask for; more partitions than that
-            // and the join's launch would exceed 2^32 threads.  A larger forced value is clamped.)
-            bits = std::min<uint32_t>(std::max<uint32_t>(bits, 1), 21);
-            if (top_bits_taken && bits > 32 - top_bits_taken) bits = 32 - top_bits_taken;
-            return bits;
-        }
-
-        TupleSrc make_src(const JoinState& st, const Side& s, const JoinSpec& js) {
-            TupleSrc src{};
-            src.key = s.rel->cols[s.key_col].ref();
-            src.n_rows = (uint32_t)s.rel->n;
-            src.carry_mode = s.carry_mode;
-            if (s.carry_mode == CARRY_COLUMN) {
-                src.carry = s.rel->cols[s.carry_col].ref();
-                // a base table's row-id column (VARCHAR stand-in) IS the row index
-                if (src.carry.kind == COL_IOTA) src.carry_mode = CARRY_ROWIDX;
-            }
-            if (s.carry_mode == CARRY_WIDE) {
-                ColRef refs[3] = {};
-                size_t k = 0;
-                for (int c : s.wide_cols) refs[k++] = s.rel->cols[c].ref();
-                if (s.valid_word >= 0)
-                    refs[k++] = ColRef{s.vword ? s.vword->as<uint8_t>() : nullptr, nullptr, COL_DENSE, 4};
-                src.wide = s.wide;
-                src.carry = refs[0];
-                src.carry2 = refs[1];
-                src.carry3 = refs[2];
-            }
-            src.key_f64 = st.f64 ? 1 : 0;
-            src.prehashed = js.prehashed ? 1 : 0;
-            return src;
-        }
-
-        // execute_hash_join + hash_join_omp (reference src/execute.cpp:43-282) on one device
-        Rel join_core(Rel& left, Rel& right, const JoinSpec& js, Result* root_res) {
-            // with an empty child the reference returns {} before looking at anything (:50)
-            if (left.n == 0 || right.n == 0) return empty_rel(js, root_res);
-            JoinState st;
-            join_prepare(left, right, js, root_res != nullptr, st);
-            if (st.type_mismatch) return empty_rel(js, root_res);
-            if (st.vkey) hash_varchar_keys(st);
-            prepare_wide(st.ls);
-            prepare_wide(st.rs);
-            Side&          bs = st.bs();
-            Side&          ps = st.ps();
-            const uint32_t bits = join_bits(js, bs.rel->n, js.top_bits_taken);
-            if (ctx->tune.diag >= 2)
-                fprintf(stderr, "[rj diag] join build=%llu probe=%llu bits=%u cw=%d/%d\n",
-                        (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bits, bs.CW, ps.CW);
-            // A build side that fits one LDS table is not partitioned at all: every workgroup builds
-            // the same table and streams a slice of the probe child past it (k_join_bcast)
-            const bool bcast = bs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && !js.prehashed &&
-                               ctx->tune.bcast != 0;
-            Parted PB, PP;
-            if (!bcast) {
-                TupleSrc sb = make_src(st, bs, js), sp = make_src(st, ps, js);
-                PB = partition(&sb, nullptr, st.KW, bs.CW, bits);
-                PP = partition(&sp, nullptr, st.KW, ps.CW, bits);
-            }
-            return join_finish(st, js, bcast ? nullptr : &PB, bcast ? nullptr : &PP, bits, root_res);
-        }
-
-        // Semi / anti join (RJ_NODE_SEMI / RJ_NODE_ANTI, semantics in rj.h): the build side is the
-        // filter side and carries nothing, the probe side is preserved; every preserved row that has
-        // (SEMI) or has not (ANTI) a partner comes out once, with the preserved side's columns only.
-        Rel filter_join(Rel& left, Rel& right, const JoinSpec& js, bool anti, Result* root_res) {
-            Rel&         fil = js.build_left ? left : right;
-            Rel&         pre = js.build_left ? right : left;
-            const size_t lw = left.cols.size();
-            for (uint64_t o : js.out_idx)
-                if (o < lw + right.cols.size() && (o < lw) == js.build_left)
-                    throw_fmt(RJ_ERR_ARG, "%s join: output attr %llu names a column of the filter side",
-                              anti ? "anti" : "semi", (unsigned long long)o);
-            const uint64_t fattr = js.build_left ? js.left_attr : js.right_attr;
-            if (fattr < fil.cols.size() && fil.cols[fattr].type == RJ_VARCHAR)
-                throw_fmt(RJ_ERR_UNSUPPORTED, "%s join on a VARCHAR key", anti ? "anti" : "semi");
-            if (pre.n == 0 || (!anti && fil.n == 0)) return empty_rel(js, root_res);
-            JoinState st;
-            join_prepare(left, right, js, root_res != nullptr, st, nullptr, anti ? RJ_NODE_ANTI : RJ_NODE_SEMI);
-            if (st.type_mismatch && !anti) return empty_rel(js, root_res);
-            Side&     fs = st.bs();
-            Side&     ps = st.ps();
-            const int KW = st.KW;
-            prepare_wide(ps);
-            plan_carry_streams(st);
-            const bool keyless = st.type_mismatch;
-            // an empty filter side or keys of another type need no set: every row misses
-            const bool bcast = (fs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && ctx->tune.bcast != 0) ||
-                               fs.rel->n == 0 || keyless;
-            const uint32_t bits = join_bits(js, fs.rel->n);
-            if (ctx->tune.diag >= 2)
-                fprintf(stderr, "[rj diag] %s join filter=%llu preserved=%llu %s bits=%u cw=%d\n", anti ? "anti" : "semi",
-                        (unsigned long long)fs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
-                        bits, ps.CW);
-
-            // the output never holds more rows than the preserved side: streams of that size, no retry
-            const uint64_t cap = ps.rel->n;
-            const int      key_mode = st.need_key_stream ? stream_mode_of(st.is_root, KW * 4, true) : ST_NONE;
-            BufP           key_stream = key_mode != ST_NONE ? ctx->buf(stream_bytes(key_mode, cap)) : BufP();
-            ps.stream = ps.stream_mode != ST_NONE ? ctx->buf(stream_bytes(ps.stream_mode, cap)) : BufP();
-            BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
-            RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
-
-            FilterParams fp{};
-            fp.anti = anti ? 1 : 0;
-            fp.keyless = keyless ? 1 : 0;
-            fp.key = OutStream{key_stream ? key_stream->as<uint8_t>() : nullptr, key_mode, 0};
-            fp.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
-            fp.out_cursor = counters->as<unsigned long long>();
-            fp.out_cap = cap;
-            fp.P = make_src(st, ps, js);
-            const uint32_t stride_grid = (uint32_t)std::min<uint64_t>((ps.rel->n + JN_SUB - 1) / JN_SUB,
-                                                                      (uint64_t)ctx->compute_units() * 8);
-            Parted PF, PP;
-            BufP   tasks;
-            if (bcast) {
-                if (!keyless) fp.F = make_src(st, fs, js);
-                launch_filter_bcast(L, KW, ps.CW, fp, stride_grid);
+            BufP off, hist, cursor;  // this pass' partition offsets, bin totals, write cursors
+            if (fine) {  // offsets and cursors of both passes came out of the fine histogram
+                off = p == 0 ? coarse_off : fine_off;
+                cursor = p == 0 ? coarse_cursor : fine_cursor;
+                pp.cursor = cursor->as<uint32_t>();
+                pp.xcd_log2 = (p == 0 && fine_xcd) ? 3u : 0u;
             } else {
-                // both sides partitioned as an inner join's would be; the filter side carries nothing
-                TupleSrc sf = make_src(st, fs, js);
-                PF = partition(&sf, nullptr, KW, 0, bits);
-                PP = partition(&fp.P, nullptr, KW, ps.CW, bits);
-                const uint32_t max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
-                tasks = ctx->buf((uint64_t)max_tasks * 12);
-                launch_heavy_tasks_zeroed(PF, PP, tasks, counters, max_tasks);
-                fp.Fw = PF.w;
-                fp.Pw = PP.w;
-                fp.offF = PF.off->as<uint32_t>();
-                fp.offP = PP.off->as<uint32_t>();
-                fp.NP = PF.NP;
-                fp.radix_bits = bits;
-                fp.packP = PP.packed ? 1 : 0;
-                fp.aosP = PP.aos3 ? 1 : 0;
-                fp.heavy_tasks = tasks->as<uint32_t>();
-                fp.n_heavy = counters->as<uint32_t>() + 2;
-                fp.heavy_grid = max_tasks;
-                launch_filter_join(L, KW, ps.CW, fp, max_tasks + PF.NP);
-                // the rows the first radix pass dropped: NULL keys, FP64 NaN keys
-                if (anti && (fp.P.key.valid || fp.P.key_f64)) launch_filter_nullkeys(L, KW, ps.CW, fp, stride_grid);
+                // sub-ranges per XCD only where a partition gets many runs (big inputs)
+                pp.xcd_log2 = (ctx->tune.xcd_split && p == 0 && !preseg && n >= (uint64_t)ctx->tune.xcd_min_rows) ? 3u : 0u;
+                hist = ctx->buf((bins << pp.xcd_log2) * 4);
+                off = ctx->buf((bins + 1) * 4);
+                cursor = ctx->buf((bins << pp.xcd_log2) * 4);
+                RJ_HIP(hipMemsetAsync(hist->p, 0, (bins << pp.xcd_log2) * 4, ctx->stream));
+                pp.hist = hist->as<uint32_t>();
+                pp.cursor = cursor->as<uint32_t>();
+                if (p == 1 && chunk_second) {
+                    // ---- histogram / scan / scatter of this pass, `mall_chunk` input segments at a time,
+                    // chunks alternating between the context's two compute streams: the scatter of a
+                    // chunk re-reads what its histogram launch has just pulled through the Infinity
+                    // Cache.  Segments never share bins, cursors or output ranges, so the chunks are
+                    // independent; grids are exact (the segment sizes are on the host by now).
+                    RJ_HIP(hipEventSynchronize(chunk_ev.e));
+                    const uint32_t* hoff = static_cast<const uint32_t*>(ctx->small_pinned());
+                    const uint64_t  gt = (uint64_t)pp.tiles_per_group * PT_TILE;
+                    std::vector<uint32_t> gstart(nseg_in + 1, 0);
+                    for (uint32_t sgi = 0; sgi < nseg_in; ++sgi)
+                        gstart[sgi + 1] = gstart[sgi] + (uint32_t)(((uint64_t)(hoff[sgi + 1] - hoff[sgi]) + gt - 1) / gt);
+                    Ev2 e_in, e_aux;
+                    e_in.make();
+                    e_aux.make();
+                    hipStream_t aux = ctx->aux_stream();
+                    RJ_HIP(hipEventRecord(e_in.e, ctx->stream));  // (behind the previous scatter and the bin memset)
+                    RJ_HIP(hipStreamWaitEvent(aux, e_in.e, 0));
+                    Launch L2 = L;
+                    L2.stream = aux;
+                    const uint32_t CH = (uint32_t)ctx->tune.mall_chunk;
+                    uint32_t       c = 0;
+                    for (uint32_t s0 = 0; s0 < nseg_in; s0 += CH, ++c) {
+                        const uint32_t s1 = std::min(nseg_in, s0 + CH), G = gstart[s1] - gstart[s0];
+                        const Launch& Lc = (c & 1u) ? L2 : L;
+                        PassParams    pc = pp;
+                        pc.nseg = s1 - s0;
+                        pc.seg_off = pp.seg_off + s0;
+                        pc.grp_start = pp.grp_start + s0;
+                        pc.grp_base = gstart[s0];
+                        pc.hist = pp.hist + (size_t)s0 * F;
+                        pc.cursor = pp.cursor + (size_t)s0 * F;
+                        const uint32_t grid = pp.xcd_remap ? ((G + 7u) & ~7u) : G;
+                        if (G) launch_pass_hist_packed(Lc, cur.w[0], pc, grid);
+                        // (empty segments still need their partition offsets)
+                        launch_scan_segments(Lc, pc.hist, pc.seg_off, pc.nseg, F, 0, off->as<uint32_t>() + (size_t)s0 * F, pc.cursor);
+                        if (G) launch_pass_scatter_packed(Lc, cur.w[0], pc, grid, nxt.w[0]);
+                    }
+                    RJ_HIP(hipEventRecord(e_aux.e, aux));
+                    RJ_HIP(hipStreamWaitEvent(ctx->stream, e_aux.e, 0));  // (before any buffer of this pass is reused)
+                    seg_off = off;
+                    nseg = (uint32_t)bins;
+                    shift += pbits[p];
+                    cur = nxt;
+                    cur_is_a = (p % 2 == 0);
+                    nxt = cur_is_a ? wb : wa;
+                    continue;
+                }
+                if (p == 0 && !ws)
+                    launch_pass_hist_src(L, src, KW, pp, n_groups);
+                else if ((mid_side || packed_side) && p > 0)
+                    launch_pass_hist_digits(L, SIDE[(p - 1) % 2]->as<uint16_t>(), pp, n_groups);
+                else if (aos_mid && p > 0)
+                    launch_pass_hist_aos3(L, MID[(p - 1) % 2]->as<uint32_t>(), pp, n_groups);
+                else if (P.packed && blocked_mid && p > 0)
+                    launch_pass_hist_blocked(L, cur.w[0], pp, n_groups);
+                else if (P.packed)
+                    launch_pass_hist_packed(L, cur.w[0], pp, n_groups);
+                else
+                    launch_pass_hist_dense(L, cur, pp, n_groups);
+                // (one workgroup per OUTPUT segment; its base = where that segment starts)
+                launch_scan_segments(L, pp.hist, first_preseg ? shape->oseg_off : (p == 0 ? nullptr : pp.seg_off),
+                                     n_oseg, F, pp.xcd_log2, off->as<uint32_t>(), pp.cursor);
             }
-            std::set<void*> finished;
-            finish_paged_streams(st, key_stream, key_mode, counters, cap, finished);
+            if (p == 0 && after_offsets) (*after_offsets)(off->as<uint32_t>());
+            // the second pass in chunks needs this pass' partition sizes on the HOST (exact grids per
+            // chunk): they leave now, before the scatter is enqueued, and are read while it runs
+            if (p == 0 && chunk_second) {
+                if ((bins + 1) * 4 > Context::SMALL_PINNED / 4) throw_fmt(RJ_ERR_DEVICE, "chunked pass: too many segments");
+                RJ_HIP(hipMemcpyAsync(ctx->small_pinned(), off->p, (bins + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+                chunk_ev.make();
+                RJ_HIP(hipEventRecord(chunk_ev.e, ctx->stream));
+            }
+            BufP pt_diag;
+            if (ctx->tune.diag >= 3) {  // phase stamps of the scatter (diagnostic build only)
+                pt_diag = ctx->buf(8 * 8);
+                RJ_HIP(hipMemsetAsync(pt_diag->p, 0, 64, ctx->stream));
+                pp.diag = pt_diag->as<unsigned long long>();
+            }
+            struct DiagDump {
+                Context* ctx; BufP b; uint32_t p; uint64_t n; bool aos;
+                ~DiagDump() {
+                    if (!b) return;
+                    unsigned long long h[8];
+                    if (hipMemcpyAsync(h, b->p, 64, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return;
+                    (void)hipStreamSynchronize(ctx->stream);
+                    static const char* names[] = {"clear+tail", "load issue+hash", "rank+barrier", "reserve+scan",
+                                                  "stage A", "copy-out A", "stage B", "copy-out B"};
+                    double tot = 0;
+                    for (int i = 0; i < 8; ++i) tot += (double)h[i];
+                    if (tot <= 0) return;
+                    fprintf(stderr, "[rj diag] scatter pass %u over %llu tuples, phase shares (thread 0 cycles):", p, (unsigned long long)n);
+                    for (int i = 0; i < 8; ++i) fprintf(stderr, " %s %.1f%%", names[i], 100.0 * h[i] / tot);
+                    fprintf(stderr, "  (%.0f cycles per tile)\n", tot / ((double)n / PT_TILE));
+                }
+            } diag_dump{ctx, pt_diag, p, n, false};
+            if (aos_mid) {
+                const bool last = p + 1 == passes;
+                Words      o{};
+                o.w[0] = last ? waos.w[0] : MID[p % 2]->as<uint32_t>();
+                if (!last && mid_side) {
+                    pp.side_out = SIDE[p % 2]->as<uint16_t>();
+                    pp.next_shift = shift + pbits[p];
+                    pp.next_mask = (1u << pbits[p + 1]) - 1u;
+                }
+                if (p == 0 && !ws)
+                    launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, o, true);
+                else if (p == 0)
+                    launch_pass_scatter_dense(L, cur, P.NW, KW, pp, n_groups, o, true);
+                else
+                    launch_pass_scatter_aos3(L, MID[(p - 1) % 2]->as<uint32_t>(), pp, n_groups, o.w[0]);
+                nxt = o;
+            } else if (P.packed) {
+                if (packed_side && p + 1 < passes) {
+                    pp.side_out = SIDE[p % 2]->as<uint16_t>();
+                    pp.next_shift = shift + pbits[p];
+                    pp.next_mask = (1u << pbits[p + 1]) - 1u;
+                }
+                const bool blk_out = blocked_mid && p + 1 < passes;
+                if (p == 0 && !ws)
+                    launch_pass_scatter_src_packed(L, src, pp, n_groups, nxt.w[0], blk_out);
+                else if (blocked_mid)
+                    launch_pass_scatter_blocked(L, cur.w[0], pp, n_groups, nxt.w[0], blk_out);
+                else
+                    launch_pass_scatter_packed(L, cur.w[0], pp, n_groups, nxt.w[0]);
+            } else if (p == 0 && !ws) {
+                launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, nxt, P.aos3 && p + 1 == passes);
+            } else {
+                launch_pass_scatter_dense(L, cur, P.NW, pair_word, pp, n_groups, nxt,
+                                          P.aos3 && p + 1 == passes);
+            }
+            seg_off = off;
+            nseg = (uint32_t)bins;
+            shift += pbits[p];
+            cur = nxt;
+            cur_is_a = (p % 2 == 0);
+            nxt = cur_is_a ? wb : wa;
+            if (P.aos3 && p + 2 == passes) nxt = waos;  // the next pass is the last one
+            if (aos_mid) {
+                // (MID / SIDE buffers of a pass are read by the next one only; they go back to
+                // the block cache when this function returns — all on one stream)
+            }
+        }
+        P.w = cur;
+        for (int a = 0; a < P.NW; ++a) P.wbuf[a] = cur_is_a ? A[a] : B[a];
+        if (P.aos3) P.wbuf[0] = AOS;
+        P.off = seg_off;
+        P.NP = nseg;
+        P.pbits = pbits;
+        if (shape && !shape->prior_bits.empty()) P.pbits.insert(P.pbits.begin(), shape->prior_bits.begin(), shape->prior_bits.end());
+        P.n_tuples = n;
+        return P;
+    }
+
+    // ---------------------------------------------------------------- join
+    struct Side {
+        Rel*          rel = nullptr;
+        uint64_t      key_col = 0;
+        std::set<int> need;       // referenced columns that are not served by the key stream
+        int           carry_mode = CARRY_NONE;
+        int           carry_col = -1;
+        int           CW = 0;
+        BufP          stream;     // emitted carry stream
+        int           stream_mode = ST_NONE;
+        // CARRY_WIDE: the carried columns in record order (a 64-bit one first), then — if any of
+        // them has NULLs — one word of validity bits (bit i = wide_cols[i] is non-NULL)
+        std::vector<int> wide_cols;
+        int              wide = WIDE_NONE;
+        int              valid_word = -1;
+        BufP             vword;  // the packed validity word per row of the child
+        struct WideOut {
+            BufP values, valid;
+            int  mode = ST_NONE;  // dense values, or — root columns without NULLs — Page images straight away
+        };
+        std::map<int, WideOut> wide_out;  // per carried column: what k_split_records produced
+        // A sharded join's ranks must cut their tuples alike, and whether a column needs a validity
+        // word depends on the DATA of a shard: columns that hold NULLs on ANY rank are nullable on
+        // every rank (bit c = column c; columns from 64 up count as nullable when `shared` is set)
+        uint64_t null_mask = 0;
+        bool     shared = false;
+        // the optional side of an outer join: every column it delivers can come out NULL (a padded
+        // row), whatever the source column holds
+        bool     optional = false;
+        bool     nullable(int c) const {
+            if (optional || rel->cols[c].valid != nullptr) return true;
+            return shared && (c >= 64 || ((null_mask >> c) & 1u));
+        }
+    };
+    // which of a relation's (first 64) columns hold NULLs here
+    static uint64_t null_columns(const Rel& r) {
+        uint64_t m = 0;
+        for (size_t c = 0; c < r.cols.size() && c < 64; ++c)
+            if (r.cols[c].valid != nullptr) m |= 1ull << c;
+        return m;
+    }
+
+    static uint64_t pages_for(uint64_t rows, int width) {
+        uint64_t rf = width == 4 ? ROWS32 : ROWS64;
+        return (rows + rf - 1) / rf;
+    }
+
+    Rel empty_rel(const JoinSpec& js, Result* root_res) {
+        Rel r;
+        r.n = 0;
+        for (size_t k = 0; k < js.out_type.size(); ++k) {
+            DCol d;
+            d.type = js.out_type[k];
+            d.kind = COL_DENSE;
+            d.width = d.type == RJ_INT32 || d.type == RJ_VARCHAR ? 4 : 8;
+            r.cols.push_back(d);
+        }
+        if (root_res) {
+            root_res->num_rows = 0;
+            for (size_t k = 0; k < js.out_type.size(); ++k) {
+                ResultColumn rc;
+                rc.type = js.out_type[k];
+                root_res->cols.push_back(std::move(rc));
+            }
+        }
+        return r;
+    }
+
+    // What a JoinNode decides before any tuple moves: key type, which columns each side
+    // must deliver and how they travel (execute_hash_join, reference src/execute.cpp:266-282,
+    // and the head of hash_join_omp, :43-83).
+    struct JoinState {
+        Side     ls, rs;
+        bool     build_left = true, is_root = false, f64 = false, need_key_stream = false;
+        bool     type_mismatch = false;  // probe key of another type: no row can match (:65-71)
+        size_t   lw = 0, rw = 0;
+        int      KW = 1;
+        uint64_t cap_hint = 0;  // rows the output streams are sized for at the first attempt
+        const JoinKind* kind = nullptr;
+        // VARCHAR join keys (hash_join_omp<std::string>, src/execute.cpp:278): each side's
+        // relation is copied with one extra column — the 64-bit FNV-1a of the key strings —
+        // which the join runs on; `rows` remembers where every string sits for the
+        // byte-for-byte check of the joined pairs
+        bool vkey = false;
+        struct VKey {
+            Rel            rel;
+            BufP           rows, hash, valid;
+            const uint8_t* pages = nullptr;
+            uint32_t       n_pages = 0;
+        } vk[2];  // [0] = left, [1] = right
+        Side&    bs() { return build_left ? ls : rs; }
+        Side&    ps() { return build_left ? rs : ls; }
+    };
+
+    // shared_nulls (sharded joins): {left, right} null_columns() OR-ed over all ranks
+    void join_prepare(Rel& left, Rel& right, const JoinSpec& js, bool is_root, JoinState& st, const JoinKind& K,
+                      const uint64_t* shared_nulls = nullptr) {
+        st.kind = &K;
+        const size_t lw = left.cols.size(), rw = right.cols.size();
+        st.lw = lw;
+        st.rw = rw;
+        st.is_root = is_root;
+        st.build_left = js.build_left;
+        if (js.left_attr >= lw || js.right_attr >= rw)
+            throw_fmt(RJ_ERR_ARG, "join: key attr out of range");
+        for (size_t k = 0; k < js.out_idx.size(); ++k) {
+            if (js.out_idx[k] >= lw + rw) throw_fmt(RJ_ERR_ARG, "join: output attr out of range");
+            const DCol& c = js.out_idx[k] < lw ? left.cols[js.out_idx[k]]
+                                               : right.cols[js.out_idx[k] - lw];
+            if (c.type != js.out_type[k])
+                throw_fmt(RJ_ERR_ARG, "join: declared type differs from the child column's type");
+        }
+        Side &ls = st.ls, &rs = st.rs;
+        ls.rel = &left;
+        ls.key_col = js.left_attr;
+        rs.rel = &right;
+        rs.key_col = js.right_attr;
+        if (shared_nulls) {
+            ls.shared = rs.shared = true;
+            ls.null_mask = shared_nulls[0];
+            rs.null_mask = shared_nulls[1];
+        }
+        const DCol& bk = st.bs().rel->cols[st.bs().key_col];
+        const DCol& pk = st.ps().rel->cols[st.ps().key_col];
+        // KeyType = build side's key type (:271-273)
+        if (bk.type < RJ_INT32 || bk.type > RJ_VARCHAR) throw_fmt(RJ_ERR_ARG, "Unsupported join type");
+        // probe values of another variant alternative are never valid (:65-71)
+        st.type_mismatch = pk.type != bk.type;
+        st.vkey = bk.type == RJ_VARCHAR && !st.type_mismatch;
+        st.KW = bk.type == RJ_INT32 ? 1 : 2;
+        st.f64 = bk.type == RJ_FP64;
+        // matching keys are bit-identical on both sides (FP64 included: bit-pattern equality,
+        // see SrcLoader::key2), so one emitted key stream serves either side's key column.
+        // A semi / anti join emits the preserved side's own key — through the key stream unless
+        // its type is not the key type (no key is read then) or ANTI may emit rows whose key is
+        // NULL (the stream has no validity): then the key column travels as a payload column.
+        // An outer join emits unmatched rows as ANTI does, so the preserved key follows ANTI's rule;
+        // the optional side's key column is NULL in those rows and never comes from the key stream:
+        // it travels as one of that side's payload columns.
+        const bool key_stream_ok =
+            K.node == RJ_NODE_JOIN ||
+            (!st.type_mismatch && !(K.emits_unmatched && st.ps().rel->cols[st.ps().key_col].valid));
+        st.bs().optional = K.build_optional;
+        st.ps().optional = K.probe_optional;  // (both: neither side's key column comes from the key stream)
+        // Which child columns must each side deliver?
+        for (size_t k = 0; k < js.out_idx.size(); ++k) {
+            bool  is_left = js.out_idx[k] < lw;
+            Side& s = is_left ? ls : rs;
+            int   c = (int)(is_left ? js.out_idx[k] : js.out_idx[k] - lw);
+            if ((uint64_t)c == s.key_col && !st.vkey && key_stream_ok && !s.optional)
+                st.need_key_stream = true;
+            else
+                s.need.insert(c);  // (a VARCHAR key column is gathered like any other column)
+        }
+        for (Side* s : {&ls, &rs}) {
+            if (st.vkey) {  // both row indices are needed for the string comparison of the pairs
+                s->carry_mode = CARRY_ROWIDX;
+                s->CW = 1;
+            } else if (s->need.empty()) {
+                s->carry_mode = CARRY_NONE;
+                s->CW = 0;
+            } else if (s->need.size() == 1 && !s->nullable(*s->need.begin())) {
+                s->carry_mode = CARRY_COLUMN;
+                s->carry_col = *s->need.begin();
+                s->CW = s->rel->cols[s->carry_col].width / 4;
+            } else if (plan_wide_carry(*s, st.KW)) {
+                s->carry_mode = CARRY_WIDE;
+            } else {
+                s->carry_mode = CARRY_ROWIDX;
+                s->CW = 1;
+            }
+        }
+        st.cap_hint = std::max(left.n, right.n);
+    }
+
+    // Can the columns a side must deliver travel WITH the key (reference src/execute.cpp:236-242
+    // copies any column list per output row; here up to MAX_WORDS - KW carry words do the same
+    // without a row index to gather through afterwards)?  Layouts: two or three 32-bit words, or
+    // a 64-bit column followed by one 32-bit word; a validity word counts as a 32-bit word.
+    bool plan_wide_carry(Side& s, int KW) {
+        if (!ctx->tune.wide_carry || s.need.empty()) return false;
+        int  words = 0, n64 = 0;
+        bool any_null = false;
+        for (int c : s.need) {
+            const DCol& col = s.rel->cols[c];
+            if (col.width != 4 && col.width != 8) return false;
+            words += col.width / 4;
+            n64 += col.width == 8;
+            any_null = any_null || s.nullable(c);
+        }
+        if (any_null) ++words;
+        if (words < 2 || words > MAX_WORDS - KW || n64 > 1 || (n64 == 1 && words != 3)) return false;
+        s.wide_cols.clear();
+        for (int c : s.need)
+            if (s.rel->cols[c].width == 8) s.wide_cols.push_back(c);
+        for (int c : s.need)
+            if (s.rel->cols[c].width == 4) s.wide_cols.push_back(c);
+        s.wide = n64 ? WIDE_64_32 : WIDE_32S;
+        s.valid_word = any_null ? words - 1 : -1;
+        s.CW = words;
+        return true;
+    }
+
+    // validity bits of a wide carry's columns, one word per row (k_pack_validity); call once
+    // per join before the side's tuples are formed
+    void prepare_wide(Side& s) {
+        if (s.carry_mode != CARRY_WIDE || s.valid_word < 0 || s.rel->n == 0) return;
+        const uint8_t* v[3] = {nullptr, nullptr, nullptr};
+        for (size_t i = 0; i < s.wide_cols.size() && i < 3; ++i) v[i] = s.rel->cols[s.wide_cols[i]].valid;
+        s.vword = ctx->buf(s.rel->n * 4);
+        launch_pack_validity(L, v[0], v[1], v[2], (uint32_t)s.rel->n, s.vword->as<uint32_t>());
+    }
+
+    // radix bit plan from the build cardinality; `top_bits_taken` high hash bits are constant
+    // on this rank (a sharded join's rank digit): the plan stays below them
+    uint32_t join_bits(const JoinSpec& js, uint64_t build_n, uint32_t top_bits_taken = 0) {
+        uint32_t bits = js.forced_bits > 0 ? (uint32_t)js.forced_bits
+                                           : ceil_log2((build_n + JN_TARGET_BUILD - 1) / JN_TARGET_BUILD);
+        // a third pass costs 20 B/tuple more than slightly fuller tables: stay at two passes
+        // (2 * PT_MAXBITS bits) while the mean build partition still fits the LDS table with
+        // a margin (rare larger partitions are joined in table-sized chunks anyway)
+        if (js.forced_bits <= 0 && bits > 2 * PT_MAXBITS &&
+            (build_n >> (2 * PT_MAXBITS)) <= (uint64_t)(JN_RMAX * 0.95))
+            bits = 2 * PT_MAXBITS;
+        // (at most 21: three passes of 7 bits — what 2^32 build rows ask for; more partitions than that
+        // and the join's launch would exceed 2^32 threads.  A larger forced value is clamped.)
+        bits = std::min<uint32_t>(std::max<uint32_t>(bits, 1), 21);
+        if (top_bits_taken && bits > 32 - top_bits_taken) bits = 32 - top_bits_taken;
+        return bits;
+    }
+
+    TupleSrc make_src(const JoinState& st, const Side& s, const JoinSpec& js) {
+        TupleSrc src{};
+        src.key = s.rel->cols[s.key_col].ref();
+        src.n_rows = (uint32_t)s.rel->n;
+        src.carry_mode = s.carry_mode;
+        if (s.carry_mode == CARRY_COLUMN) {
+            src.carry = s.rel->cols[s.carry_col].ref();
+            // a base table's row-id column (VARCHAR stand-in) IS the row index
+            if (src.carry.kind == COL_IOTA) src.carry_mode = CARRY_ROWIDX;
+        }
+        if (s.carry_mode == CARRY_WIDE) {
+            ColRef refs[3] = {};
+            size_t k = 0;
+            for (int c : s.wide_cols) refs[k++] = s.rel->cols[c].ref();
+            if (s.valid_word >= 0)
+                refs[k++] = ColRef{s.vword ? s.vword->as<uint8_t>() : nullptr, nullptr, COL_DENSE, 4};
+            src.wide = s.wide;
+            src.carry = refs[0];
+            src.carry2 = refs[1];
+            src.carry3 = refs[2];
+        }
+        src.key_f64 = st.f64 ? 1 : 0;
+        src.prehashed = js.prehashed ? 1 : 0;
+        return src;
+    }
+
+    // ------------------------------------------------- the probe step of a join node
+    // What the five kinds share, each written once: whether the node is partitioned at all
+    // (broadcast_form), the co-partitions and their heavy-task list (CoParts), and the output
+    // protocol (emit_with_retry).  A kind's own function keeps its refusals and early returns, its
+    // parameter struct and the kernels it launches per attempt.
+
+    // A build side that fits one LDS table is not partitioned: every workgroup builds the same
+    // table and streams a slice of the probe child past it (the *_bcast kernels).  The kinds that
+    // get here with an empty build side or with keys of another type (they emit rows without a
+    // partner) need no table at all, which the broadcast kernels handle.
+    bool broadcast_form(JoinState& st, const JoinSpec& js) const {
+        const uint64_t nb = st.bs().rel->n;
+        return (nb <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && !js.prehashed && ctx->tune.bcast != 0) || nb == 0 ||
+               st.type_mismatch;
+    }
+    // workgroups that stride over `rows` rows in chunks of JN_SUB
+    uint32_t stride_grid(uint64_t rows) const {
+        return (uint32_t)std::min<uint64_t>((rows + JN_SUB - 1) / JN_SUB, (uint64_t)ctx->compute_units() * 8);
+    }
+
+    // Both sides of a partitioned node, cut with the same bit plan, and the probe partitions that
+    // are split into tasks (k_heavy_tasks).  A ShardedExec fills B and P itself, from the exchange.
+    struct CoParts {
+        Parted   B, P;
+        BufP     tasks;  // [max_tasks][3]
+        uint32_t max_tasks = 0;
+    };
+    CoParts partition_sides(JoinState& st, const JoinSpec& js, uint32_t bits) {
+        CoParts        cp;
+        const TupleSrc sb = make_src(st, st.bs(), js), sp = make_src(st, st.ps(), js);
+        cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits);
+        cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits);
+        return cp;
+    }
+    // heavy probe partitions -> task list; zeroes all 16 bytes of `counters` on the way
+    void heavy_tasks(CoParts& cp, const BufP& counters) {
+        cp.max_tasks = (uint32_t)(2 * (cp.P.n_tuples / JN_HEAVY) + 2);
+        cp.tasks = ctx->buf((uint64_t)cp.max_tasks * 12);
+        launch_heavy_tasks_zeroed(cp.B, cp.P, cp.tasks, counters, cp.max_tasks);
+    }
+    CoParts co_partition(JoinState& st, const JoinSpec& js, uint32_t bits, const BufP& counters) {
+        CoParts cp = partition_sides(st, js, bits);
+        heavy_tasks(cp, counters);
+        return cp;
+    }
+    // [0..7] out cursor (u64), [8..11] n_heavy
+    BufP zeroed_counters() {
+        BufP counters = ctx->buf(16);
+        RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
+        return counters;
+    }
+    // the fields every partitioned probe kernel's parameters hold under the same names
+    template <class Params>
+    static void set_heavy(Params& p, const CoParts& cp, const BufP& counters, uint32_t bits) {
+        p.NP = cp.B.NP;
+        p.radix_bits = bits;
+        p.heavy_tasks = cp.tasks->as<uint32_t>();
+        p.n_heavy = counters->as<uint32_t>() + 2;
+        p.heavy_grid = cp.max_tasks;
+    }
+    static void set_parts(OuterParams& op, const CoParts& cp, const BufP& counters, uint32_t bits) {
+        set_heavy(op, cp, counters, bits);
+        op.Bw = cp.B.w;
+        op.Pw = cp.P.w;
+        op.offB = cp.B.off->as<uint32_t>();
+        op.offP = cp.P.off->as<uint32_t>();
+        op.packB = cp.B.packed ? 1 : 0;
+        op.aosB = cp.B.aos3 ? 1 : 0;
+        op.packP = cp.P.packed ? 1 : 0;
+        op.aosP = cp.P.aos3 ? 1 : 0;
+    }
+
+    static OutStream out_stream(const BufP& b, int mode) { return OutStream{b ? b->as<uint8_t>() : nullptr, mode, 0}; }
+    static OutStream out_stream(const Side& s) { return out_stream(s.stream, s.stream_mode); }
+    // rows the streams of a first attempt hold when the result may exceed `rows`
+    static uint64_t first_cap(uint64_t rows) { return std::min<uint64_t>(rows + 1024, 0xfffffff0ull); }
+
+    struct Emitted {
+        uint64_t        nrows = 0;
+        BufP            key_stream;
+        int             key_mode = ST_NONE;
+        std::set<void*> finished;  // paged buffers that already got their headers
+    };
+    // The output protocol of every kind: streams for `cap` rows; the kernels count every row they
+    // produce on the device (counters[0..7]) and write only what fits; a count beyond `cap` runs
+    // the attempt once more with streams of exactly that size.  A kind whose first capacity is a
+    // bound (JoinKind::attempts == 1) never reruns.  `launch(key, cap)` enqueues one attempt; the
+    // carry streams are st.ls.stream / st.rs.stream.  Page headers of the streams the probe wrote
+    // straight into Page images are made on the device from the device-side row count, so nothing
+    // waits for the read-back.  (FULL has no such stream: both of its sides are optional, so both
+    // carries are dense records or row ids and no key stream exists; finish_paged_streams then
+    // finds nothing and no k_finish_streams is launched.)
+    template <class LaunchFn>
+    Emitted emit_with_retry(JoinState& st, const BufP& counters, uint64_t cap, LaunchFn&& launch) {
+        const JoinKind& K = *st.kind;
+        Emitted         e;
+        e.key_mode = st.need_key_stream ? stream_mode_of(st.is_root, st.KW * 4, true) : ST_NONE;
+        for (int attempt = 1;; ++attempt) {
+            e.key_stream = e.key_mode != ST_NONE ? ctx->buf(stream_bytes(e.key_mode, cap)) : BufP();
+            for (Side* s : {&st.ls, &st.rs})
+                s->stream = s->stream_mode != ST_NONE ? ctx->buf(stream_bytes(s->stream_mode, cap)) : BufP();
+            // (a kind with a single attempt has just zeroed the cursor with the rest of the counters)
+            if (K.attempts > 1) RJ_HIP(hipMemsetAsync(counters->p, 0, 8, ctx->stream));
+            launch(out_stream(e.key_stream, e.key_mode), cap);
+            e.finished.clear();
+            finish_paged_streams(st, e, counters, cap);
             unsigned long long h = 0;
             RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
             ctx->sync();
-            if (h > cap) throw_fmt(RJ_ERR_DEVICE, "%s join emitted %llu rows out of %llu", anti ? "anti" : "semi", h,
-                                   (unsigned long long)cap);
-            return join_assemble(st, js, key_stream, key_mode, h, finished, root_res);
+            e.nrows = h;
+            if (e.nrows <= cap) return e;
+            if (K.attempts == 1)
+                throw_fmt(RJ_ERR_DEVICE, "%s emitted %llu rows out of %llu", K.name, h, (unsigned long long)cap);
+            if (e.nrows > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "%s result exceeds 2^32 rows (%llu)", K.name, h);
+            if (attempt == K.attempts) throw_fmt(RJ_ERR_DEVICE, "%s output overflowed twice", K.name);
+            cap = e.nrows;  // exact size, run the probe again
         }
+    }
 
-        // Outer join (RJ_NODE_OUTER, semantics in rj.h): the build side is the OPTIONAL side, the probe
-        // side is preserved.  The inner join's rows plus one row per preserved row without a partner,
-        // whose optional-side columns are NULL.  Both sides are partitioned as an inner join's are
-        // (or not at all: broadcast); one kernel family emits both halves.  NULL travels in-band in the
-        // optional side's carry (OuterParams), so that side never uses CARRY_COLUMN.
-        Rel outer_join(Rel& left, Rel& right, const JoinSpec& js, Result* root_res) {
-            Rel&           opt = js.build_left ? left : right;
-            Rel&           pre = js.build_left ? right : left;
-            const uint64_t oattr = js.build_left ? js.left_attr : js.right_attr;
-            if (oattr < opt.cols.size() && opt.cols[oattr].type == RJ_VARCHAR)
-                throw_fmt(RJ_ERR_UNSUPPORTED, "outer join on a VARCHAR key");
-            if (pre.n == 0) return empty_rel(js, root_res);
-            JoinState st;
-            join_prepare(left, right, js, root_res != nullptr, st, nullptr, RJ_NODE_OUTER);
-            Side&     bs = st.bs();
-            Side&     ps = st.ps();
-            const int KW = st.KW;
-            for (int c : bs.need)
-                if (bs.rel->cols[c].type == RJ_VARCHAR)
-                    throw_fmt(RJ_ERR_UNSUPPORTED,
-                              "outer join: a VARCHAR column of the optional side in the output is not supported "
-                              "(child column %d)", c);
-            prepare_wide(bs);
-            prepare_wide(ps);
-            plan_carry_streams(st);
-            const bool keyless = st.type_mismatch;
-            // an empty optional side or keys of another type need no table: every row comes out padded
-            const bool bcast = (bs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && ctx->tune.bcast != 0) ||
-                               bs.rel->n == 0 || keyless;
-            const uint32_t bits = join_bits(js, bs.rel->n);
-            if (ctx->tune.diag >= 2)
-                fprintf(stderr, "[rj diag] outer join optional=%llu preserved=%llu %s bits=%u cw=%d/%d\n",
-                        (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
-                        bits, bs.CW, ps.CW);
+    // execute_hash_join + hash_join_omp (reference src/execute.cpp:43-282) on one device
+    Rel join_core(Rel& left, Rel& right, const JoinSpec& js, Result* root_res) {
+        // with an empty child the reference returns {} before looking at anything (:50)
+        if (left.n == 0 || right.n == 0) return empty_rel(js, root_res);
+        JoinState st;
+        join_prepare(left, right, js, root_res != nullptr, st, join_kind(RJ_NODE_JOIN));
+        if (st.type_mismatch) return empty_rel(js, root_res);
+        if (st.vkey) hash_varchar_keys(st);
+        prepare_wide(st.ls);
+        prepare_wide(st.rs);
+        Side&          bs = st.bs();
+        Side&          ps = st.ps();
+        const uint32_t bits = join_bits(js, bs.rel->n, js.top_bits_taken);
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] join build=%llu probe=%llu bits=%u cw=%d/%d\n",
+                    (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bits, bs.CW, ps.CW);
+        if (broadcast_form(st, js)) return join_finish(st, js, nullptr, bits, root_res);
+        CoParts cp = partition_sides(st, js, bits);
+        return join_finish(st, js, &cp, bits, root_res);
+    }
 
-            OuterParams op{};
-            op.keyless = keyless ? 1 : 0;
-            op.pad_bc = bs.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
-            op.P = make_src(st, ps, js);
-            if (!keyless) op.B = make_src(st, bs, js);
-            BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
-            RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
-            op.out_cursor = counters->as<unsigned long long>();
-            const uint32_t stride_grid = (uint32_t)std::min<uint64_t>((ps.rel->n + JN_SUB - 1) / JN_SUB,
-                                                                      (uint64_t)ctx->compute_units() * 8);
-            Parted   PB, PP;
-            BufP     tasks;
-            uint32_t max_tasks = 0;
-            if (!bcast) {
-                PB = partition(&op.B, nullptr, KW, bs.CW, bits);
-                PP = partition(&op.P, nullptr, KW, ps.CW, bits);
-                max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
-                tasks = ctx->buf((uint64_t)max_tasks * 12);
-                launch_heavy_tasks_zeroed(PB, PP, tasks, counters, max_tasks);
-                op.Bw = PB.w;
-                op.Pw = PP.w;
-                op.offB = PB.off->as<uint32_t>();
-                op.offP = PP.off->as<uint32_t>();
-                op.NP = PB.NP;
-                op.radix_bits = bits;
-                op.packB = PB.packed ? 1 : 0;
-                op.aosB = PB.aos3 ? 1 : 0;
-                op.packP = PP.packed ? 1 : 0;
-                op.aosP = PP.aos3 ? 1 : 0;
-                op.heavy_tasks = tasks->as<uint32_t>();
-                op.n_heavy = counters->as<uint32_t>() + 2;
-                op.heavy_grid = max_tasks;
+    // Build + probe of an inner join over co-partitioned tuples (cp->B / cp->P; nullptr = broadcast
+    // join straight from the children's columns), output streams, late materialisation, result pages.
+    Rel join_finish(JoinState& st, const JoinSpec& js, CoParts* cp, uint32_t bits, Result* root_res) {
+        Side &    bs = st.bs(), &ps = st.ps();
+        const int KW = st.KW;
+        // (not zeroed here: heavy_tasks() zeroes all of it, and the broadcast form uses the cursor
+        // alone, which every attempt resets)
+        BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
+        if (cp) heavy_tasks(*cp, counters);
+        plan_carry_streams(st);
+        Emitted e = emit_with_retry(st, counters, first_cap(st.cap_hint), [&](const OutStream& key, uint64_t cap) {
+            if (!cp) {
+                BcastParams bp{};
+                bp.R = make_src(st, bs, js);
+                bp.S = make_src(st, ps, js);
+                bp.key = key;
+                bp.bc = out_stream(bs);
+                bp.pc = out_stream(ps);
+                bp.out_cursor = counters->as<unsigned long long>();
+                bp.out_cap = cap;
+                launch_join_bcast(L, KW, bs.CW, ps.CW, bp, stride_grid(ps.rel->n));
+                return;
             }
-
-            // The result holds at least the preserved rows and may hold many more (dup x dup): the
-            // inner join's protocol — count on the device, run the probe once more with the exact size.
-            const int key_mode = st.need_key_stream ? stream_mode_of(st.is_root, KW * 4, true) : ST_NONE;
-            uint64_t  cap = std::min<uint64_t>(std::max(st.cap_hint, ps.rel->n) + 1024, 0xfffffff0ull);
-            BufP            key_stream;
-            uint64_t        nrows = 0;
-            std::set<void*> finished;
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                key_stream = key_mode != ST_NONE ? ctx->buf(stream_bytes(key_mode, cap)) : BufP();
-                for (Side* s : {&st.ls, &st.rs})
-                    s->stream = s->stream_mode != ST_NONE ? ctx->buf(stream_bytes(s->stream_mode, cap)) : BufP();
-                RJ_HIP(hipMemsetAsync(counters->p, 0, 8, ctx->stream));
-                op.key = OutStream{key_stream ? key_stream->as<uint8_t>() : nullptr, key_mode, 0};
-                op.bc = OutStream{bs.stream ? bs.stream->as<uint8_t>() : nullptr, bs.stream_mode, 0};
-                op.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
-                op.out_cap = cap;
-                if (bcast) {
-                    launch_outer_bcast(L, KW, bs.CW, ps.CW, op, stride_grid);
-                } else {
-                    launch_outer_join(L, KW, bs.CW, ps.CW, op, max_tasks + PB.NP);
-                    // the rows the first radix pass dropped: NULL keys, FP64 NaN keys
-                    if (op.P.key.valid || op.P.key_f64) launch_outer_nullkeys(L, KW, ps.CW, op, stride_grid);
-                }
-                finished.clear();
-                finish_paged_streams(st, key_stream, key_mode, counters, cap, finished);
-                unsigned long long h = 0;
-                RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
+            const Parted &PB = cp->B, &PP = cp->P;
+            JoinParams    jp{};
+            set_heavy(jp, *cp, counters, bits);
+            jp.R = PB.w;
+            jp.S = PP.w;
+            jp.packR = PB.packed ? 1 : 0;
+            jp.packS = PP.packed ? 1 : 0;
+            jp.aosR = PB.aos3 ? 1 : 0;
+            jp.aosS = PP.aos3 ? 1 : 0;
+            jp.offR = PB.off->as<uint32_t>();
+            jp.offS = PP.off->as<uint32_t>();
+            jp.n_pass = (uint32_t)PB.pbits.size();
+            for (size_t i = 0; i < PB.pbits.size() && i < 4; ++i) jp.pass_bits[i] = PB.pbits[i];
+            jp.key = key;
+            jp.bc = out_stream(bs);
+            jp.pc = out_stream(ps);
+            jp.out_cursor = counters->as<unsigned long long>();
+            jp.out_cap = cap;
+            BufP diag;
+            if (ctx->tune.diag) {
+                diag = ctx->buf(16 * 8);
+                RJ_HIP(hipMemsetAsync(diag->p, 0, 16 * 8, ctx->stream));
+                jp.diag = diag->as<unsigned long long>();
+            }
+            // one launch: heavy-task workgroups first, then one workgroup per `ppw` partitions
+            const uint32_t ppw = join_partitions_per_workgroup(KW, bs.CW, jp);
+            launch_join(L, KW, bs.CW, ps.CW, jp, cp->max_tasks + (PB.NP + ppw - 1) / ppw);
+            if (diag) {
+                unsigned long long hd[16];
+                RJ_HIP(hipMemcpyAsync(hd, diag->p, sizeof hd, hipMemcpyDeviceToHost, ctx->stream));
                 ctx->sync();
-                nrows = h;
-                if (nrows <= cap) break;
-                if (nrows > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "outer join result exceeds 2^32 rows (%llu)", h);
-                if (attempt == 1) throw_fmt(RJ_ERR_DEVICE, "outer join output overflowed twice");
-                cap = nrows;  // exact size, run the probe again
+                static const char* names[] = {"loads issued", "table clear", "build", "count/probe",
+                                              "prefix+barrier", "reserve", "emit"};
+                double tot = 0;
+                for (int i = 0; i < 7; ++i) tot += (double)hd[i];
+                fprintf(stderr, "[rj diag] join phases (cycles of thread 0, summed over %u workgroups):\n", PB.NP);
+                for (int i = 0; i < 7; ++i)
+                    fprintf(stderr, "[rj diag]   %-16s %6.1f %%  %8.0f cyc/wg\n", names[i],
+                            100.0 * hd[i] / tot, (double)hd[i] / PB.NP);
             }
-            return join_assemble(st, js, key_stream, key_mode, nrows, finished, root_res);
+        });
+        if (st.vkey && e.nrows) e.nrows = verify_varchar_pairs(st, e.nrows);
+        return join_assemble(st, js, e, root_res);
+    }
+
+    // Semi / anti join (RJ_NODE_SEMI / RJ_NODE_ANTI, semantics in rj.h): the build side is the
+    // filter side and carries nothing, the probe side is preserved; every preserved row that has
+    // (SEMI) or has not (ANTI) a partner comes out once, with the preserved side's columns only.
+    Rel filter_join(Rel& left, Rel& right, const JoinSpec& js, const JoinKind& K, Result* root_res) {
+        const bool   anti = K.node == RJ_NODE_ANTI;
+        Rel&         fil = js.build_left ? left : right;
+        Rel&         pre = js.build_left ? right : left;
+        const size_t lw = left.cols.size();
+        for (uint64_t o : js.out_idx)
+            if (o < lw + right.cols.size() && (o < lw) == js.build_left)
+                throw_fmt(RJ_ERR_ARG, "%s: output attr %llu names a column of the filter side", K.name,
+                          (unsigned long long)o);
+        const uint64_t fattr = js.build_left ? js.left_attr : js.right_attr;
+        if (fattr < fil.cols.size() && fil.cols[fattr].type == RJ_VARCHAR)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "%s on a VARCHAR key", K.name);
+        if (pre.n == 0 || (!anti && fil.n == 0)) return empty_rel(js, root_res);
+        JoinState st;
+        join_prepare(left, right, js, root_res != nullptr, st, K);
+        if (st.type_mismatch && !anti) return empty_rel(js, root_res);
+        Side&     fs = st.bs();
+        Side&     ps = st.ps();
+        const int KW = st.KW;
+        prepare_wide(ps);
+        plan_carry_streams(st);
+        const bool     bcast = broadcast_form(st, js);  // (an empty filter side, keys of another type: every row misses)
+        const uint32_t bits = join_bits(js, fs.rel->n);
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] %s filter=%llu preserved=%llu %s bits=%u cw=%d\n", K.name,
+                    (unsigned long long)fs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
+                    bits, ps.CW);
+
+        FilterParams fp{};
+        fp.anti = anti ? 1 : 0;
+        fp.keyless = st.type_mismatch ? 1 : 0;
+        fp.P = make_src(st, ps, js);
+        if (bcast && !fp.keyless) fp.F = make_src(st, fs, js);
+        BufP counters = zeroed_counters();
+        fp.out_cursor = counters->as<unsigned long long>();
+        CoParts cp;
+        if (!bcast) {
+            // both sides partitioned as an inner join's would be; the filter side carries nothing
+            cp = co_partition(st, js, bits, counters);
+            set_heavy(fp, cp, counters, bits);
+            fp.Fw = cp.B.w;
+            fp.Pw = cp.P.w;
+            fp.offF = cp.B.off->as<uint32_t>();
+            fp.offP = cp.P.off->as<uint32_t>();
+            fp.packP = cp.P.packed ? 1 : 0;
+            fp.aosP = cp.P.aos3 ? 1 : 0;
         }
-
-        // Full outer join (RJ_NODE_FULL, semantics in rj.h): an outer join whose probed side is
-        // optional too.  The probe kernels are the outer join's with one addition: every build tuple
-        // that matched gets its bit set in `flags` (HBM, one bit per build tuple, zeroed once per
-        // node; a rerun sets the same bits again).  A second phase in the same stream then emits the
-        // build tuples whose bit stayed clear, and the build rows the table never saw (NULL / NaN
-        // keys), with the probed side's carry padded.  NULL travels in-band in BOTH carries.
-        Rel full_join(Rel& left, Rel& right, const JoinSpec& js_in, Result* root_res) {
-            for (int side = 0; side < 2; ++side) {
-                const Rel&     r = side == 0 ? left : right;
-                const uint64_t a = side == 0 ? js_in.left_attr : js_in.right_attr;
-                if (a < r.cols.size() && r.cols[a].type == RJ_VARCHAR)
-                    throw_fmt(RJ_ERR_UNSUPPORTED, "full outer join on a VARCHAR key");
+        // the output never holds more rows than the preserved side: streams of that size, no retry
+        Emitted e = emit_with_retry(st, counters, ps.rel->n, [&](const OutStream& key, uint64_t cap) {
+            fp.key = key;
+            fp.pc = out_stream(ps);
+            fp.out_cap = cap;
+            if (bcast) {
+                launch_filter_bcast(L, KW, ps.CW, fp, stride_grid(ps.rel->n));
+            } else {
+                launch_filter_join(L, KW, ps.CW, fp, cp.max_tasks + cp.B.NP);
+                // the rows the first radix pass dropped: NULL keys, FP64 NaN keys
+                if (anti && (fp.P.key.valid || fp.P.key_f64))
+                    launch_filter_nullkeys(L, KW, ps.CW, fp, stride_grid(ps.rel->n));
             }
-            // what the node may output is a property of the plan, not of the data: a malformed node and
-            // a VARCHAR output column are refused whatever the children hold
-            auto refuse_varchar_outputs = [](JoinState& s) {
-                for (Side* sd : {&s.ls, &s.rs})
-                    for (int c : sd->need)
-                        if (sd->rel->cols[c].type == RJ_VARCHAR)
-                            throw_fmt(RJ_ERR_UNSUPPORTED,
-                                      "full outer join: a VARCHAR column in the output is not supported (%s child column %d)",
-                                      sd == &s.ls ? "left" : "right", c);
-            };
-            if (left.n == 0 && right.n == 0) {
-                JoinState chk;
-                join_prepare(left, right, js_in, root_res != nullptr, chk, nullptr, RJ_NODE_FULL);
-                refuse_varchar_outputs(chk);
-                return empty_rel(js_in, root_res);
-            }
-            // build_left is a hint: an empty probed side would leave the probe kernels without work
-            // and the partitioner without tuples, so the empty child is the one that is built
-            JoinSpec js = js_in;
-            if ((js.build_left ? right : left).n == 0) js.build_left = !js.build_left;
-            JoinState st;
-            join_prepare(left, right, js, root_res != nullptr, st, nullptr, RJ_NODE_FULL);
-            Side&     bs = st.bs();
-            Side&     ps = st.ps();
-            const int KW = st.KW;
-            refuse_varchar_outputs(st);
-            prepare_wide(bs);
-            prepare_wide(ps);
-            plan_carry_streams(st);
-            const bool keyless = st.type_mismatch;
-            const bool bcast = (bs.rel->n <= (uint64_t)JN_RMAX && js.forced_bits <= 0 && ctx->tune.bcast != 0) ||
-                               bs.rel->n == 0 || keyless;
-            const uint32_t bits = join_bits(js, bs.rel->n);
-            if (ctx->tune.diag >= 2)
-                fprintf(stderr, "[rj diag] full outer join built=%llu probed=%llu %s bits=%u cw=%d/%d\n",
-                        (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bcast ? "broadcast" : "partitioned",
-                        bits, bs.CW, ps.CW);
+        });
+        return join_assemble(st, js, e, root_res);
+    }
 
-            FullParams   fp{};
-            OuterParams& op = fp.o;
-            op.keyless = keyless ? 1 : 0;
-            op.pad_bc = bs.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
+    // Outer join (RJ_NODE_OUTER, semantics in rj.h): the build side is the OPTIONAL side, the probe
+    // side is preserved.  The inner join's rows plus one row per preserved row without a partner,
+    // whose optional-side columns are NULL.  Both sides are partitioned as an inner join's are
+    // (or not at all: broadcast); one kernel family emits both halves.  NULL travels in-band in the
+    // optional side's carry (OuterParams), so that side never uses CARRY_COLUMN.
+    Rel outer_join(Rel& left, Rel& right, const JoinSpec& js, const JoinKind& K, Result* root_res) {
+        Rel&           opt = js.build_left ? left : right;
+        Rel&           pre = js.build_left ? right : left;
+        const uint64_t oattr = js.build_left ? js.left_attr : js.right_attr;
+        if (oattr < opt.cols.size() && opt.cols[oattr].type == RJ_VARCHAR)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "%s on a VARCHAR key", K.name);
+        if (pre.n == 0) return empty_rel(js, root_res);
+        JoinState st;
+        join_prepare(left, right, js, root_res != nullptr, st, K);
+        return outer_probe(st, js, root_res);
+    }
+
+    // Full outer join (RJ_NODE_FULL, semantics in rj.h): an outer join whose probed side is
+    // optional too.  The probe kernels are the outer join's with one addition: every build tuple
+    // that matched gets its bit set in `flags` (HBM, one bit per build tuple, zeroed once per
+    // node; a rerun sets the same bits again).  A second phase in the same stream then emits the
+    // build tuples whose bit stayed clear, and the build rows the table never saw (NULL / NaN
+    // keys), with the probed side's carry padded.  NULL travels in-band in BOTH carries.
+    Rel full_join(Rel& left, Rel& right, const JoinSpec& js_in, const JoinKind& K, Result* root_res) {
+        for (int side = 0; side < 2; ++side) {
+            const Rel&     r = side == 0 ? left : right;
+            const uint64_t a = side == 0 ? js_in.left_attr : js_in.right_attr;
+            if (a < r.cols.size() && r.cols[a].type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "%s on a VARCHAR key", K.name);
+        }
+        // what the node may output is a property of the plan, not of the data: a malformed node and
+        // a VARCHAR output column are refused whatever the children hold
+        if (left.n == 0 && right.n == 0) {
+            JoinState chk;
+            join_prepare(left, right, js_in, root_res != nullptr, chk, K);
+            refuse_varchar_outputs(chk);
+            return empty_rel(js_in, root_res);
+        }
+        // build_left is a hint: an empty probed side would leave the probe kernels without work
+        // and the partitioner without tuples, so the empty child is the one that is built
+        JoinSpec js = js_in;
+        if ((js.build_left ? right : left).n == 0) js.build_left = !js.build_left;
+        JoinState st;
+        join_prepare(left, right, js, root_res != nullptr, st, K);
+        return outer_probe(st, js, root_res);
+    }
+
+    // a VARCHAR column of an optional side cannot come out
+    static void refuse_varchar_outputs(JoinState& st) {
+        for (Side* s : {&st.ls, &st.rs})
+            for (int c : s->need) {
+                if (!s->optional || s->rel->cols[c].type != RJ_VARCHAR) continue;
+                if (st.kind->probe_optional)
+                    throw_fmt(RJ_ERR_UNSUPPORTED,
+                              "full outer join: a VARCHAR column in the output is not supported (%s child column %d)",
+                              s == &st.ls ? "left" : "right", c);
+                throw_fmt(RJ_ERR_UNSUPPORTED,
+                          "outer join: a VARCHAR column of the optional side in the output is not supported "
+                          "(child column %d)", c);
+            }
+    }
+
+    // What OUTER and FULL do once the node is prepared.  FULL's parameters hold an outer join's.
+    Rel outer_probe(JoinState& st, const JoinSpec& js, Result* root_res) {
+        const bool full = st.kind->probe_optional;
+        Side&      bs = st.bs();
+        Side&      ps = st.ps();
+        const int  KW = st.KW;
+        refuse_varchar_outputs(st);
+        prepare_wide(bs);
+        prepare_wide(ps);
+        plan_carry_streams(st);
+        const bool     bcast = broadcast_form(st, js);  // (no table at all: every row comes out padded)
+        const uint32_t bits = join_bits(js, bs.rel->n);
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] %s %s=%llu %s=%llu %s bits=%u cw=%d/%d\n", st.kind->name, full ? "built" : "optional",
+                    (unsigned long long)bs.rel->n, full ? "probed" : "preserved", (unsigned long long)ps.rel->n,
+                    bcast ? "broadcast" : "partitioned", bits, bs.CW, ps.CW);
+
+        FullParams   fp{};
+        OuterParams& op = fp.o;
+        op.keyless = st.type_mismatch ? 1 : 0;
+        op.pad_bc = bs.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
+        op.P = make_src(st, ps, js);
+        // (FULL, keyless: the build side's key is never read, its carry is)
+        if (full || !op.keyless) op.B = make_src(st, bs, js);
+        BufP counters = zeroed_counters();
+        op.out_cursor = counters->as<unsigned long long>();
+        CoParts cp;
+        if (!bcast) {
+            cp = co_partition(st, js, bits, counters);
+            set_parts(op, cp, counters, bits);
+        }
+        BufP flags;
+        if (full) {
             fp.pad_pc = ps.carry_mode == CARRY_ROWIDX ? OUTER_NO_ROW : 0u;
-            op.P = make_src(st, ps, js);
-            op.B = make_src(st, bs, js);  // (keyless: its key is never read, its carry is)
-            BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
-            RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
-            op.out_cursor = counters->as<unsigned long long>();
-            const uint64_t max_grid = (uint64_t)ctx->compute_units() * 8;
-            const uint32_t stride_grid = (uint32_t)std::min<uint64_t>((ps.rel->n + JN_SUB - 1) / JN_SUB, max_grid);
-            const uint32_t build_grid = (uint32_t)std::min<uint64_t>((bs.rel->n + JN_SUB - 1) / JN_SUB, max_grid);
-            Parted   PB, PP;
-            BufP     tasks;
-            uint32_t max_tasks = 0;
-            if (!bcast) {
-                PB = partition(&op.B, nullptr, KW, bs.CW, bits);
-                PP = partition(&op.P, nullptr, KW, ps.CW, bits);
-                max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
-                tasks = ctx->buf((uint64_t)max_tasks * 12);
-                launch_heavy_tasks_zeroed(PB, PP, tasks, counters, max_tasks);
-                op.Bw = PB.w;
-                op.Pw = PP.w;
-                op.offB = PB.off->as<uint32_t>();
-                op.offP = PP.off->as<uint32_t>();
-                op.NP = PB.NP;
-                op.radix_bits = bits;
-                op.packB = PB.packed ? 1 : 0;
-                op.aosB = PB.aos3 ? 1 : 0;
-                op.packP = PP.packed ? 1 : 0;
-                op.aosP = PP.aos3 ? 1 : 0;
-                op.heavy_tasks = tasks->as<uint32_t>();
-                op.n_heavy = counters->as<uint32_t>() + 2;
-                op.heavy_grid = max_tasks;
-            }
-            // one matched bit per build tuple (partitioned: by index in PB's arrays; broadcast: by row
-            // of the built child), whole words, one spare word for the round that ends unaligned
-            const uint64_t flag_bytes = ((bcast ? (uint64_t)JN_RMAX : PB.n_tuples) / 32 + 2) * 4;
-            BufP           flags = ctx->buf(flag_bytes);
+            // one matched bit per build tuple (partitioned: by index in cp.B's arrays; broadcast: by
+            // row of the built child), whole words, one spare word for the round that ends unaligned
+            const uint64_t flag_bytes = ((bcast ? (uint64_t)JN_RMAX : cp.B.n_tuples) / 32 + 2) * 4;
+            flags = ctx->buf(flag_bytes);
             RJ_HIP(hipMemsetAsync(flags->p, 0, flag_bytes, ctx->stream));
             fp.flags = flags->as<uint32_t>();
             fp.use_flags = bcast ? 1 : 0;
-
-            // every row of both sides may come out, and dup x dup may exceed that: the inner join's
-            // protocol — count on the device, run the probe once more with the exact size
-            uint64_t cap = std::min<uint64_t>(std::max(st.cap_hint, bs.rel->n + ps.rel->n) + 1024, 0xfffffff0ull);
-            uint64_t nrows = 0;
-            std::set<void*> finished;
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                for (Side* s : {&st.ls, &st.rs})
-                    s->stream = s->stream_mode != ST_NONE ? ctx->buf(stream_bytes(s->stream_mode, cap)) : BufP();
-                RJ_HIP(hipMemsetAsync(counters->p, 0, 8, ctx->stream));
-                op.key = OutStream{nullptr, ST_NONE, 0};
-                op.bc = OutStream{bs.stream ? bs.stream->as<uint8_t>() : nullptr, bs.stream_mode, 0};
-                op.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
-                op.out_cap = cap;
-                if (bcast) {
-                    launch_full_bcast(L, KW, bs.CW, ps.CW, fp, stride_grid);
-                    // unmatched build rows and build rows without a usable key, in one sweep
-                    launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
-                } else {
-                    launch_full_join(L, KW, bs.CW, ps.CW, fp, max_tasks + PB.NP);
-                    launch_full_unmatched(L, KW, bs.CW, fp, build_grid);
-                    // the rows the first radix pass dropped (NULL keys, FP64 NaN keys), either side
-                    if (op.P.key.valid || op.P.key_f64) launch_outer_nullkeys(L, KW, ps.CW, op, stride_grid);
-                    if (op.B.key.valid || op.B.key_f64) launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
-                }
-                finished.clear();
-                unsigned long long h = 0;
-                RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
-                ctx->sync();
-                nrows = h;
-                if (nrows <= cap) break;
-                if (nrows > 0xfffffff0ull)
-                    throw_fmt(RJ_ERR_UNSUPPORTED, "full outer join result exceeds 2^32 rows (%llu)", h);
-                if (attempt == 1) throw_fmt(RJ_ERR_DEVICE, "full outer join output overflowed twice");
-                cap = nrows;  // exact size, run the probe again
-            }
-            return join_assemble(st, js, BufP(), ST_NONE, nrows, finished, root_res);
         }
-
-        // Build + probe over co-partitioned tuples (PB / PP; nullptr = broadcast join straight
-        // from the children's columns), output streams, late materialisation, result pages.
-        Rel join_finish(JoinState& st, const JoinSpec& js, const Parted* PBp, const Parted* PPp,
-                        uint32_t bits, Result* root_res) {
-            Side &         ls = st.ls, &rs = st.rs, &bs = st.bs(), &ps = st.ps();
-            const bool     is_root = st.is_root, bcast = PBp == nullptr;
-            const int      KW = st.KW;
-            const bool     need_key_stream = st.need_key_stream;
-            const uint64_t probe_n = bcast ? ps.rel->n : (uint64_t)0;
-            (void)probe_n;
-            uint32_t max_tasks = 0;
-            BufP     tasks;
-            BufP     counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
-            if (!bcast) {
-                const Parted &PB = *PBp, &PP = *PPp;
-                // heavy probe partitions -> task list
-                max_tasks = (uint32_t)(2 * (PP.n_tuples / JN_HEAVY) + 2);
-                tasks = ctx->buf((uint64_t)max_tasks * 12);
-                launch_heavy_tasks_zeroed(PB, PP, tasks, counters, max_tasks);
+        const uint32_t probe_grid = stride_grid(ps.rel->n), build_grid = stride_grid(bs.rel->n);
+        // OUTER holds at least the preserved rows, FULL may hold every row of both sides, and
+        // dup x dup may exceed either
+        const uint64_t rows0 = std::max(st.cap_hint, full ? bs.rel->n + ps.rel->n : ps.rel->n);
+        Emitted e = emit_with_retry(st, counters, first_cap(rows0), [&](const OutStream& key, uint64_t cap) {
+            op.key = key;  // (FULL: none, neither side's key column comes from a key stream)
+            op.bc = out_stream(bs);
+            op.pc = out_stream(ps);
+            op.out_cap = cap;
+            // the rows the first radix pass dropped: NULL keys, FP64 NaN keys
+            const bool probe_dropped = !bcast && (op.P.key.valid || op.P.key_f64);
+            if (!full) {
+                if (bcast)
+                    launch_outer_bcast(L, KW, bs.CW, ps.CW, op, probe_grid);
+                else
+                    launch_outer_join(L, KW, bs.CW, ps.CW, op, cp.max_tasks + cp.B.NP);
+                if (probe_dropped) launch_outer_nullkeys(L, KW, ps.CW, op, probe_grid);
+            } else if (bcast) {
+                launch_full_bcast(L, KW, bs.CW, ps.CW, fp, probe_grid);
+                // unmatched build rows and build rows without a usable key, in one sweep
+                launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
+            } else {
+                launch_full_join(L, KW, bs.CW, ps.CW, fp, cp.max_tasks + cp.B.NP);
+                launch_full_unmatched(L, KW, bs.CW, fp, build_grid);
+                if (probe_dropped) launch_outer_nullkeys(L, KW, ps.CW, op, probe_grid);
+                if (op.B.key.valid || op.B.key_f64) launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
             }
-
-            // stream destinations
-            auto stream_mode = [&](int width, bool direct_output) -> int {
-                return stream_mode_of(is_root, width, direct_output);
-            };
-            int key_mode = need_key_stream ? stream_mode(KW * 4, true) : ST_NONE;
-            plan_carry_streams(st);
-
-            uint64_t cap = st.cap_hint;
-            cap = std::min<uint64_t>(cap + 1024, 0xfffffff0ull);
-            BufP            key_stream;
-            uint64_t        nrows = 0;
-            std::set<void*> finished;  // paged buffers that already got their headers
-            for (int attempt = 0; attempt < 2; ++attempt) {
-                key_stream = key_mode != ST_NONE ? ctx->buf(stream_bytes(key_mode, cap)) : BufP();
-                for (Side* s : {&ls, &rs})
-                    s->stream = s->stream_mode != ST_NONE ? ctx->buf(stream_bytes(s->stream_mode, cap))
-                                                          : BufP();
-                RJ_HIP(hipMemsetAsync(counters->p, 0, 8, ctx->stream));
-                if (bcast) {
-                    BcastParams bp{};
-                    bp.R = make_src(st, bs, js);
-                    bp.S = make_src(st, ps, js);
-                    bp.key = OutStream{key_stream ? key_stream->as<uint8_t>() : nullptr, key_mode, 0};
-                    bp.bc = OutStream{bs.stream ? bs.stream->as<uint8_t>() : nullptr, bs.stream_mode, 0};
-                    bp.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
-                    bp.out_cursor = counters->as<unsigned long long>();
-                    bp.out_cap = cap;
-                    const uint64_t chunks = (ps.rel->n + JN_SUB - 1) / JN_SUB;
-                    launch_join_bcast(L, KW, bs.CW, ps.CW, bp,
-                                      (uint32_t)std::min<uint64_t>(chunks, (uint64_t)ctx->compute_units() * 8));
-                } else {
-                const Parted &PB = *PBp, &PP = *PPp;
-                JoinParams jp{};
-                jp.R = PB.w;
-                jp.S = PP.w;
-                jp.packR = PB.packed ? 1 : 0;
-                jp.packS = PP.packed ? 1 : 0;
-                jp.aosR = PB.aos3 ? 1 : 0;
-                jp.aosS = PP.aos3 ? 1 : 0;
-                jp.offR = PB.off->as<uint32_t>();
-                jp.offS = PP.off->as<uint32_t>();
-                jp.NP = PB.NP;
-                jp.radix_bits = bits;
-                jp.n_pass = (uint32_t)PB.pbits.size();
-                for (size_t i = 0; i < PB.pbits.size() && i < 4; ++i) jp.pass_bits[i] = PB.pbits[i];
-                jp.key = OutStream{key_stream ? key_stream->as<uint8_t>() : nullptr, key_mode, 0};
-                jp.bc = OutStream{bs.stream ? bs.stream->as<uint8_t>() : nullptr, bs.stream_mode, 0};
-                jp.pc = OutStream{ps.stream ? ps.stream->as<uint8_t>() : nullptr, ps.stream_mode, 0};
-                jp.out_cursor = counters->as<unsigned long long>();
-                jp.out_cap = cap;
-                jp.heavy_tasks = tasks->as<uint32_t>();
-                jp.n_heavy = counters->as<uint32_t>() + 2;
-                BufP diag;
-                if (ctx->tune.diag) {
-                    diag = ctx->buf(16 * 8);
-                    RJ_HIP(hipMemsetAsync(diag->p, 0, 16 * 8, ctx->stream));
-                    jp.diag = diag->as<unsigned long long>();
-                }
-                // one launch: heavy-task workgroups first, then one workgroup per partition
-                jp.heavy_grid = max_tasks;
-                const uint32_t ppw = join_partitions_per_workgroup(KW, bs.CW, jp);
-                launch_join(L, KW, bs.CW, ps.CW, jp, max_tasks + (PB.NP + ppw - 1) / ppw);
-                if (diag) {
-                    unsigned long long hd[16];
-                    RJ_HIP(hipMemcpyAsync(hd, diag->p, sizeof hd, hipMemcpyDeviceToHost, ctx->stream));
-                    ctx->sync();
-                    static const char* names[] = {"loads issued", "table clear", "build", "count/probe",
-                                                  "prefix+barrier", "reserve", "emit"};
-                    double tot = 0;
-                    for (int i = 0; i < 7; ++i) tot += (double)hd[i];
-                    fprintf(stderr, "[rj diag] join phases (cycles of thread 0, summed over %u workgroups):\n", PB.NP);
-                    for (int i = 0; i < 7; ++i)
-                        fprintf(stderr, "[rj diag]   %-16s %6.1f %%  %8.0f cyc/wg\n", names[i],
-                                100.0 * hd[i] / tot, (double)hd[i] / PB.NP);
-                    jp.diag = nullptr;
-                }
-            }
-            // Page headers of the streams the probe wrote straight into Page images: done on
-            // the device from the device-side row count, so nothing waits for the read-back
-            finished.clear();
-            finish_paged_streams(st, key_stream, key_mode, counters, cap, finished);
-            unsigned long long h = 0;
-            RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
-            nrows = h;
-            if (nrows <= cap) break;
-            if (nrows > 0xfffffff0ull)
-                throw_fmt(RJ_ERR_UNSUPPORTED, "join result exceeds 2^32 rows (%llu)", h);
-            if (attempt == 1) throw_fmt(RJ_ERR_DEVICE, "join output overflowed twice");
-            cap = nrows;  // exact size, run the probe again
-        }
-
-        if (st.vkey && nrows) nrows = verify_varchar_pairs(st, nrows);
-        return join_assemble(st, js, key_stream, key_mode, nrows, finished, root_res);
+        });
+        return join_assemble(st, js, e, root_res);
     }
 
     static int stream_mode_of(bool is_root, int width, bool direct_output) {
@@ -1458,32 +1415,31 @@ class Exec {
         }
     }
     // headers + bitmaps of the streams a probe wrote straight into Page images, from the row count
-    // on the device (counters[0]); `finished` records them
-    void finish_paged_streams(JoinState& st, const BufP& key_stream, int key_mode, const BufP& counters,
-                              uint64_t cap, std::set<void*>& finished) {
+    // on the device (counters[0]); e.finished records them
+    void finish_paged_streams(JoinState& st, Emitted& e, const BufP& counters, uint64_t cap) {
         uint8_t* fp[3];
         int      fw[3];
         uint32_t nf = 0;
         auto add = [&](const BufP& b, int mode) {
-            if (!b || (mode != ST_PAGED32 && mode != ST_PAGED64) || finished.count(b->p)) return;
+            if (!b || (mode != ST_PAGED32 && mode != ST_PAGED64) || e.finished.count(b->p)) return;
             fp[nf] = b->as<uint8_t>();
             fw[nf] = mode == ST_PAGED32 ? 4 : 8;
             ++nf;
-            finished.insert(b->p);
+            e.finished.insert(b->p);
         };
-        add(key_stream, key_mode);
+        add(e.key_stream, e.key_mode);
         add(st.ls.stream, st.ls.stream_mode);
         add(st.rs.stream, st.rs.stream_mode);
         launch_finish_streams(L, fp, fw, nf, counters->as<unsigned long long>(), cap);
     }
 
     // What the probe's streams become: wide records split into columns, row-index carries gathered,
-    // and at the root Page images (late materialisation; shared by inner and semi / anti joins).
-    Rel join_assemble(JoinState& st, const JoinSpec& js, const BufP& key_stream, int key_mode, uint64_t nrows,
-                      std::set<void*>& finished, Result* root_res) {
-        Side &       ls = st.ls, &rs = st.rs;
-        const size_t lw = st.lw;
-        const bool   is_root = st.is_root;
+    // and at the root Page images (late materialisation; shared by every kind of join).
+    Rel join_assemble(JoinState& st, const JoinSpec& js, Emitted& e, Result* root_res) {
+        Side &         ls = st.ls, &rs = st.rs;
+        const size_t   lw = st.lw;
+        const bool     is_root = st.is_root;
+        const uint64_t nrows = e.nrows;
 
         // wide carries: the emitted records -> one dense array (+ validity bytes) per column
         for (Side* s : {&ls, &rs}) {
@@ -1535,8 +1491,8 @@ class Exec {
             int  buf_mode = ST_NONE;
             BufP valid;
             if ((uint64_t)c == s.key_col && st.need_key_stream && !s.optional) {
-                buf = key_stream;
-                buf_mode = key_mode;
+                buf = e.key_stream;
+                buf_mode = e.key_mode;
             } else if (s.carry_mode == CARRY_COLUMN) {
                 buf = s.stream;
                 buf_mode = s.stream_mode;
@@ -1585,9 +1541,9 @@ class Exec {
             } else if (src.type == RJ_VARCHAR) {
                 varchar_root(buf->as<uint32_t>(), nrows, src, rc);
             } else if (buf_mode == ST_PAGED32 || buf_mode == ST_PAGED64) {
-                if (!finished.count(buf->p)) {
+                if (!e.finished.count(buf->p)) {
                     launch_finish_pages(L, buf->as<uint8_t>(), nrows, src.width);
-                    finished.insert(buf->p);
+                    e.finished.insert(buf->p);
                 }
                 rc.dev_pages = buf;
                 rc.n_pages = pages_for(nrows, src.width);
@@ -1907,14 +1863,7 @@ class ShardedExec {
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
-        JoinSpec         js;
-        js.build_left = n.build_left != 0;
-        js.left_attr = n.left_attr;
-        js.right_attr = n.right_attr;
-        js.out_idx.assign(n.out_idx, n.out_idx + n.n_out);
-        js.out_type.assign(n.out_type, n.out_type + n.n_out);
-        js.forced_bits = g_->radix_bits_override;
-        return join(L, R, js, root_res);
+        return join(L, R, join_spec(n, g_->radix_bits_override), root_res);
     }
 
     // bytes per tuple of array `a` in the partition layout, 0 = no such array
@@ -2001,7 +1950,7 @@ class ShardedExec {
             guarded(lerr[l], [&] {
                 use(l);
                 inject_failure(1, l);
-                ex_[l]->join_prepare(left[l], right[l], js, root_res != nullptr, st[l], shared_nulls);
+                ex_[l]->join_prepare(left[l], right[l], js, root_res != nullptr, st[l], join_kind(RJ_NODE_JOIN), shared_nulls);
                 for (Exec::Side* s : {&st[l].ls, &st[l].rs}) {
                     if (s->carry_mode == CARRY_ROWIDX) ok = false;  // a row index means nothing on another rank
                     if (s->carry_mode == CARRY_COLUMN && s->rel->cols[s->carry_col].kind == COL_IOTA) ok = false;
@@ -2059,9 +2008,9 @@ class ShardedExec {
             Ev                    ready, done, counted;
             ExchangePlan          plan;
             BufP                  segs;    // device copy of plan.seg_begin | seg_end | part_off
-            Parted                P;       // stage B partitions
         };
-        std::vector<SideX> bx((size_t)nl_), px((size_t)nl_);
+        std::vector<SideX>         bx((size_t)nl_), px((size_t)nl_);
+        std::vector<Exec::CoParts> parts((size_t)nl_);  // stage B partitions of both sides
         if (((size_t)FA + 1) * 4 > Context::SMALL_PINNED / 4)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded join: more than %zu stage-A partitions", Context::SMALL_PINNED / 16 - 1);
         for (int l = 0; l < nl_; ++l) {
@@ -2245,7 +2194,7 @@ class ShardedExec {
                 guarded(pending_[l], [&] {
                     use(l);
                     RJ_HIP(hipStreamWaitEvent(g_->lane(l)->stream, X.done.e, 0));
-                    X.P = stage_b(l, X, side == 0 ? st[l].bs().CW : st[l].ps().CW);
+                    (side == 0 ? parts[l].B : parts[l].P) = stage_b(l, X, side == 0 ? st[l].bs().CW : st[l].ps().CW);
                 });
             }
         for (int l = 0; l < nl_; ++l)
@@ -2253,7 +2202,7 @@ class ShardedExec {
                 use(l);
                 inject_failure(6, l);
                 st[l].cap_hint = std::max(bx[l].ws.n, px[l].ws.n);
-                out[l] = ex_[l]->join_finish(st[l], js, &bx[l].P, &px[l].P, Lbits, root_res ? (*root_res)[l] : nullptr);
+                out[l] = ex_[l]->join_finish(st[l], js, &parts[l], Lbits, root_res ? (*root_res)[l] : nullptr);
             });
         lap("stage B (passes + join)");
         // stage A's arrays were read by the exchange streams (and by peers): they may go back
