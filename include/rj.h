@@ -137,15 +137,65 @@ typedef enum rj_status {
  *   parent may join on a nullable column it produced (NULL keys drop out as always).
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.
- *   A library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").               */
+ *   A library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Aggregation (GROUP BY key with COUNT / SUM / MIN / MAX; no reference counterpart).
+ * RJ_NODE_AGG has ONE child, `left`; `right`, `right_attr` and `build_left` are ignored.  left_attr
+ *   is the child column that is grouped by.  Every output names an aggregate function and a child
+ *   column: out_idx[k] = RJ_AGG_OUT(func, column), out_type[k] = the declared RESULT type:
+ *     RJ_AGG_KEY        the group's key; column must be left_attr; the key's type; may appear 0, 1
+ *                       or several times
+ *     RJ_AGG_COUNT_STAR rows of the group; column must be 0; INT64
+ *     RJ_AGG_COUNT      non-NULL values of an INT32 / INT64 column; INT64
+ *     RJ_AGG_SUM        sum of the non-NULL values of an INT32 / INT64 column, wrapping modulo
+ *                       2^64; INT64; NULL if the group has no non-NULL value
+ *     RJ_AGG_MIN / RJ_AGG_MAX  over the non-NULL values of an INT32 / INT64 column; the column's
+ *                       type; NULL if the group has no non-NULL value
+ *   (the other kinds keep rejecting such out_idx values as out of range).
+ *   Result: one row per distinct key value of the child, in no particular order.  Rows whose key is
+ *   NULL form ONE group, whose key comes out NULL: SQL's GROUP BY, not the join's "NULL matches
+ *   nothing".  An empty child gives 0 rows with the declared column types and zero pages.
+ *   RJ_ERR_ARG: a declared type other than the table above says, an unknown function code, a
+ *   column out of range, RJ_AGG_KEY on another column than left_attr, RJ_AGG_COUNT_STAR with a
+ *   column.  Key types are INT32 and INT64; FP64 and VARCHAR keys are RJ_ERR_UNSUPPORTED, and so are
+ *   FP64 and VARCHAR aggregated columns (a floating-point sum depends on the order of the rows,
+ *   which no result of this library does).  The child may carry columns of any type that the node
+ *   does not name.  Several functions over the same column cost one carried column.
+ *   Carry limit: the DISTINCT aggregated columns travel with the key through the radix passes, plus
+ *   one word of validity bits if any of them is nullable: at most 3 words behind an INT32 key (three
+ *   INT32 columns; an INT64 and an INT32 one; two nullable INT32 ones; one nullable INT64 one; ...)
+ *   and 2 behind an INT64 key, and at most one 64-bit column next to another word.  A node that
+ *   needs more is RJ_ERR_UNSUPPORTED (the message states the limit): a row-index fallback that
+ *   gathers the columns per partition is deliberately not part of this kind, and neither is a
+ *   scalar aggregate without a key.
+ *   The node's result is an ordinary relation: the child may be any node, and a parent JOIN / SEMI /
+ *   ANTI / OUTER / FULL / AGG may use every column of it, as a key too (NULL keys drop out in joins
+ *   as always); the node may be the root.  rj_execute_sharded refuses plans that hold the kind
+ *   (RJ_ERR_UNSUPPORTED), rj_plan_shardable reports it, and rj_execute on a multi-device context
+ *   runs such a plan on its first device.  A library older than this kind rejects it with
+ *   RJ_ERR_ARG ("bad node kind").                                                              */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
     RJ_NODE_JOIN = 1,
     RJ_NODE_SEMI = 2, /* preserved rows with a partner on the filter side    */
     RJ_NODE_ANTI = 3, /* preserved rows without one                          */
     RJ_NODE_OUTER = 4, /* inner join + unmatched preserved rows, NULL-padded */
-    RJ_NODE_FULL = 5   /* inner join + unmatched rows of BOTH sides, padded  */
+    RJ_NODE_FULL = 5,  /* inner join + unmatched rows of BOTH sides, padded  */
+    RJ_NODE_AGG = 6    /* GROUP BY left_attr of the one child `left`         */
 } rj_node_kind;
+
+/* Aggregate functions of RJ_NODE_AGG and the encoding of its out_idx values. */
+typedef enum rj_agg_func {
+    RJ_AGG_KEY        = 0,
+    RJ_AGG_COUNT_STAR = 1,
+    RJ_AGG_COUNT      = 2,
+    RJ_AGG_SUM        = 3,
+    RJ_AGG_MIN        = 4,
+    RJ_AGG_MAX        = 5
+} rj_agg_func;
+#define RJ_AGG_OUT(func, col) (((uint64_t)(func) << 56) | (uint64_t)(col))
+#define RJ_AGG_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
+#define RJ_AGG_COL(x) ((uint64_t)(x) & 0x00ffffffffffffffull)
 
 typedef struct rj_node {
     int32_t         kind;          /* rj_node_kind                            */
@@ -359,15 +409,15 @@ void     rj_result_free(rj_result* r);
  * all ranks' shards is the input.  out[d] receives local device d's slice of the result (rows
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
- * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join; others return
- * RJ_ERR_UNSUPPORTED.                                                                         */
+ * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join or an
+ * aggregation; others return RJ_ERR_UNSUPPORTED.                                                                       */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join is not shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER /
- * RJ_NODE_FULL).                                                                               */
+ * join or an aggregation is not shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI /
+ * RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG).                                                 */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

@@ -339,4 +339,65 @@ struct FullParams {
     int32_t         use_flags;    // k_full_buildrows: 1 = also emit the rows whose flag is clear (broadcast)
 };
 
+// ---- Aggregation (RJ_NODE_AGG): GROUP BY the key, COUNT / SUM / MIN / MAX over the carried columns.
+// ONE relation is partitioned; a workgroup aggregates a partition (or a heavy task of one) in an
+// LDS table of AGG_CAP entries {hashed key, rows, per carried column: non-NULL count, sum, min,
+// max}.  New keys enter the table until it holds AGG_FREEZE of them at the end of a step; from then
+// on tuples of keys that are not in it are put back into the partition's own memory, behind the
+// read position, for the next round (k_agg_parts).
+constexpr int AGG_THREADS = 512;
+constexpr int AGG_SPT     = 2;                      // tuples per thread per step
+constexpr int AGG_STEP    = AGG_THREADS * AGG_SPT;  // tuples between two looks at the table's fill
+constexpr int AGG_CAP     = 1024;                   // LDS table entries (power of two)
+constexpr int AGG_FREEZE  = AGG_CAP * 5 / 8;        // no new keys once this many are in
+constexpr int AGG_WALK    = 32;                     // entries a key may sit away from its home: a walk that
+                                                    // finds them all taken by other keys turns the tuple away
+constexpr uint32_t AGG_TARGET = AGG_CAP * 3 / 8;    // mean tuples (an upper bound of the groups) per partition
+constexpr int AGG_MAX_COLS = 3;
+static_assert((AGG_CAP & (AGG_CAP - 1)) == 0 && AGG_CAP % AGG_THREADS == 0, "table entries: a power of two, whole rows of threads");
+static_assert(AGG_CAP * (12 + 28 * AGG_MAX_COLS) + 1024 <= LDS_BYTES, "the widest aggregation table does not fit the LDS");
+
+enum AggNeed : uint32_t { AGG_NEED_COUNT = 1, AGG_NEED_SUM = 2, AGG_NEED_MIN = 4, AGG_NEED_MAX = 8 };
+struct AggCol {
+    int32_t  word;       // first word of the column inside the carry
+    int32_t  width;      // 4 or 8 bytes; 32-bit values are sign-extended
+    int32_t  valid_bit;  // bit of the validity word, -1 = the column has no NULLs
+    uint32_t need;       // AggNeed bits: the accumulators some output reads
+};
+// One group's accumulators as arrays: the merge table in HBM (entry index) and the node's output
+// (row index) share the layout.  key: KW * 4 bytes per entry in the output (un-hashed), always 8
+// in the merge table (hashed).  Arrays nobody reads are nullptr (output only).
+struct AggArrays {
+    uint8_t*            key;
+    unsigned long long* rows;
+    unsigned long long* nn[AGG_MAX_COLS];
+    unsigned long long* sum[AGG_MAX_COLS];
+    long long*          mn[AGG_MAX_COLS];
+    long long*          mx[AGG_MAX_COLS];
+};
+constexpr unsigned long long AGG_NO_KEY = ~0ull;  // merge table: an entry nobody owns yet
+struct AggParams {
+    TupleSrc        src;          // k_agg_nullkey: the child's columns
+    Words           W;            // the partitioned tuples
+    const uint32_t* off;          // [NP+1]
+    uint32_t        NP;
+    int32_t         pack, aos;    // W.w[0] holds {hashed key, carry} pairs / 12-byte tuples
+    const uint32_t* heavy_tasks;  // [n][3] = {partition, begin, end} (k_heavy_tasks)
+    const uint32_t* n_heavy;
+    uint32_t        heavy_grid;   // the first heavy_grid workgroups of k_agg_parts take heavy tasks
+    int32_t         n_cols;
+    int32_t         valid_word;   // word of the carry that holds the validity bits, -1 = none
+    AggCol          col[AGG_MAX_COLS];
+    AggArrays       out;          // one row per group, out_cap rows
+    uint8_t*        out_keyvalid; // validity bytes of the key column, preset to 1; nullptr = the key has no NULLs
+    unsigned long long* out_cursor;
+    uint64_t        out_cap;
+    // merge table (heavy tasks, NULL-key rows): m_slots entries of open addressing (a power of two,
+    // or 0), then entry m_slots for the hashed key AGG_NO_KEY itself and entry m_slots + 1 for the
+    // NULL-key group; an entry is live when its `rows` is not 0
+    AggArrays       m;
+    uint32_t        m_slots;
+    uint32_t*       m_overflow;   // set when a key found no entry: the host repeats the node with a larger table
+};
+
 }  // namespace rj

@@ -336,6 +336,10 @@ class Exec {
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
         if (n.kind == RJ_NODE_SCAN) return scan(n);
+        if (n.kind == RJ_NODE_AGG) {
+            Rel child = node(n.left, nullptr, depth + 1);
+            return agg(child, n, root_res);
+        }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
         Rel             r = node(n.right, nullptr, depth + 1);
@@ -897,8 +901,10 @@ class Exec {
     // copies any column list per output row; here up to MAX_WORDS - KW carry words do the same
     // without a row index to gather through afterwards)?  Layouts: two or three 32-bit words, or
     // a 64-bit column followed by one 32-bit word; a validity word counts as a 32-bit word.
-    bool plan_wide_carry(Side& s, int KW) {
-        if (!ctx->tune.wide_carry || s.need.empty()) return false;
+    // honour_switch = false: a caller without a row-index fallback (the aggregation) plans the
+    // layout whatever the wide-carry tuning switch says
+    bool plan_wide_carry(Side& s, int KW, bool honour_switch = true) {
+        if ((honour_switch && !ctx->tune.wide_carry) || s.need.empty()) return false;
         int  words = 0, n64 = 0;
         bool any_null = false;
         for (int c : s.need) {
@@ -1385,6 +1391,293 @@ class Exec {
         return join_assemble(st, js, e, root_res);
     }
 
+    // ---------------------------------------------------------------- aggregation
+    // RJ_NODE_AGG (semantics in rj.h): GROUP BY one key column with COUNT / SUM / MIN / MAX.  ONE
+    // relation is partitioned — the key plus the distinct aggregated columns as its carry — and
+    // k_agg_parts aggregates every partition in an LDS table.  Partitions above JN_HEAVY tuples are
+    // cut into tasks whose groups meet in a merge table in HBM, as does the group of the NULL-key
+    // rows, which the first radix pass drops; k_agg_emit turns that table into rows.  The group
+    // count is bounded by the child's rows, so the output arrays never overflow: one attempt.
+    struct AggOut {
+        uint32_t func;
+        int      col;   // child column
+        int      slot;  // index among the carried columns, -1 = none (KEY, COUNT(*))
+    };
+    uint32_t agg_bits(uint64_t rows) const {
+        uint32_t bits = ctx->radix_bits_override > 0 ? (uint32_t)ctx->radix_bits_override
+                                                     : ceil_log2((rows + AGG_TARGET - 1) / AGG_TARGET);
+        return std::min<uint32_t>(std::max<uint32_t>(bits, 1), 21);
+    }
+    Rel agg(Rel& child, const rj_node& n, Result* root_res) {
+        const size_t cw = child.cols.size();
+        if (n.left_attr >= cw) throw_fmt(RJ_ERR_ARG, "aggregation: key attr out of range");
+        const DCol& kc = child.cols[n.left_attr];
+        if (kc.type != RJ_INT32 && kc.type != RJ_INT64)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "aggregation on %s key: group keys are INT32 or INT64",
+                      kc.type == RJ_FP64 ? "an FP64" : "a VARCHAR");
+        Side s;
+        s.rel = &child;
+        s.key_col = n.left_attr;
+        std::vector<AggOut> outs;
+        JoinSpec            js;  // (the declared types, for empty_rel)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint32_t func = RJ_AGG_FUNC(n.out_idx[k]);
+            const uint64_t col = RJ_AGG_COL(n.out_idx[k]);
+            const int32_t  type = n.out_type[k];
+            if (func > RJ_AGG_MAX) throw_fmt(RJ_ERR_ARG, "aggregation: unknown function code %u", func);
+            int32_t expect = RJ_INT64;
+            if (func == RJ_AGG_COUNT_STAR) {
+                if (col != 0) throw_fmt(RJ_ERR_ARG, "aggregation: COUNT(*) takes no column");
+            } else {
+                if (col >= cw) throw_fmt(RJ_ERR_ARG, "aggregation: output attr out of range");
+                const DCol& c = child.cols[col];
+                if (func == RJ_AGG_KEY) {
+                    if (col != n.left_attr) throw_fmt(RJ_ERR_ARG, "aggregation: RJ_AGG_KEY names another column than the key");
+                    expect = kc.type;
+                } else {
+                    if (c.type != RJ_INT32 && c.type != RJ_INT64)
+                        throw_fmt(RJ_ERR_UNSUPPORTED, "aggregation over %s column (child column %llu): INT32 and INT64 only",
+                                  c.type == RJ_FP64 ? "an FP64" : "a VARCHAR", (unsigned long long)col);
+                    if (func == RJ_AGG_MIN || func == RJ_AGG_MAX) expect = c.type;
+                    s.need.insert((int)col);
+                }
+            }
+            if (type != expect) throw_fmt(RJ_ERR_ARG, "aggregation: declared type differs from the function's result type");
+            outs.push_back(AggOut{func, (int)col, -1});
+            js.out_type.push_back(type);
+        }
+        // how the aggregated columns travel with the key
+        const int KW = kc.type == RJ_INT32 ? 1 : 2;
+        if (s.need.empty()) {
+            s.carry_mode = CARRY_NONE;
+            s.CW = 0;
+        } else if (s.need.size() == 1 && !s.nullable(*s.need.begin())) {
+            s.carry_mode = CARRY_COLUMN;
+            s.carry_col = *s.need.begin();
+            s.CW = child.cols[s.carry_col].width / 4;
+            s.wide_cols = {s.carry_col};
+        } else if (plan_wide_carry(s, KW, /*honour_switch=*/false)) {
+            s.carry_mode = CARRY_WIDE;
+        } else {
+            int words = 0;
+            bool any_null = false;
+            for (int c : s.need) {
+                words += child.cols[c].width / 4;
+                any_null = any_null || s.nullable(c);
+            }
+            throw_fmt(RJ_ERR_UNSUPPORTED,
+                      "aggregation: the aggregated columns take %d carry words; at most %d travel behind an %s key (every "
+                      "distinct column its width, one more word if any is nullable, at most one 64-bit column next to "
+                      "another word)",
+                      words + (any_null ? 1 : 0), MAX_WORDS - KW, KW == 1 ? "INT32" : "INT64");
+        }
+        if (child.n == 0) return empty_rel(js, root_res);
+        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        for (AggOut& o : outs)
+            for (size_t i = 0; i < s.wide_cols.size(); ++i)
+                if (o.func >= RJ_AGG_COUNT && s.wide_cols[i] == o.col) o.slot = (int)i;
+
+        AggParams ap{};
+        ap.n_cols = (int32_t)s.wide_cols.size();
+        ap.valid_word = s.valid_word;
+        bool need_key = false, need_rows = false;
+        {
+            int word = 0;
+            for (int i = 0; i < ap.n_cols; ++i) {
+                const DCol& c = child.cols[s.wide_cols[i]];
+                ap.col[i].word = word;
+                ap.col[i].width = c.width;
+                ap.col[i].valid_bit = s.valid_word >= 0 ? i : -1;
+                word += c.width / 4;
+            }
+            for (const AggOut& o : outs) {
+                need_key = need_key || o.func == RJ_AGG_KEY;
+                need_rows = need_rows || o.func == RJ_AGG_COUNT_STAR;
+                if (o.slot < 0) continue;
+                const bool nullable = s.nullable(o.col);
+                uint32_t&  need = ap.col[o.slot].need;
+                if (o.func == RJ_AGG_COUNT || nullable) need |= AGG_NEED_COUNT;
+                if (o.func == RJ_AGG_SUM) need |= AGG_NEED_SUM;
+                if (o.func == RJ_AGG_MIN) need |= AGG_NEED_MIN;
+                if (o.func == RJ_AGG_MAX) need |= AGG_NEED_MAX;
+            }
+        }
+        prepare_wide(s);
+        JoinState st;  // (integer keys, not pre-hashed)
+        const TupleSrc src = make_src(st, s, js);
+        const uint32_t bits = agg_bits(child.n);
+        const uint64_t cap = child.n + 1;  // every row its own group, and the NULL-key group
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] aggregation rows=%llu bits=%u cw=%d cols=%d\n", (unsigned long long)child.n, bits, s.CW,
+                    ap.n_cols);
+
+        // the node's output arrays: one row per group
+        struct Arrays {
+            BufP key, keyvalid, rows, nn[AGG_MAX_COLS], sum[AGG_MAX_COLS], mn[AGG_MAX_COLS], mx[AGG_MAX_COLS];
+        } O, M;
+        auto fill = [](AggArrays& a, const Arrays& b) {
+            a.key = b.key ? b.key->as<uint8_t>() : nullptr;
+            a.rows = b.rows ? b.rows->as<unsigned long long>() : nullptr;
+            for (int i = 0; i < AGG_MAX_COLS; ++i) {
+                a.nn[i] = b.nn[i] ? b.nn[i]->as<unsigned long long>() : nullptr;
+                a.sum[i] = b.sum[i] ? b.sum[i]->as<unsigned long long>() : nullptr;
+                a.mn[i] = b.mn[i] ? b.mn[i]->as<long long>() : nullptr;
+                a.mx[i] = b.mx[i] ? b.mx[i]->as<long long>() : nullptr;
+            }
+        };
+        if (need_key) O.key = ctx->buf(cap * KW * 4);
+        if (need_key && kc.valid) O.keyvalid = ctx->buf(cap);
+        if (need_rows) O.rows = ctx->buf(cap * 8);
+        for (int i = 0; i < ap.n_cols; ++i) {
+            if (ap.col[i].need & AGG_NEED_COUNT) O.nn[i] = ctx->buf(cap * 8);
+            if (ap.col[i].need & AGG_NEED_SUM) O.sum[i] = ctx->buf(cap * 8);
+            if (ap.col[i].need & AGG_NEED_MIN) O.mn[i] = ctx->buf(cap * 8);
+            if (ap.col[i].need & AGG_NEED_MAX) O.mx[i] = ctx->buf(cap * 8);
+        }
+        fill(ap.out, O);
+        ap.out_keyvalid = O.keyvalid ? O.keyvalid->as<uint8_t>() : nullptr;
+        ap.out_cap = cap;
+        ap.src = src;
+
+        uint64_t nrows = 0;
+        for (int attempt = 0;; ++attempt) {
+            // [0..7] out cursor (u64), [8..11] n_heavy, [12..15] merge table overflow
+            BufP counters = zeroed_counters();
+            Parted P = partition(&src, nullptr, KW, s.CW, bits);
+            const uint32_t max_tasks = (uint32_t)(2 * (P.n_tuples / JN_HEAVY) + 2);
+            BufP           tasks = ctx->buf((uint64_t)max_tasks * 12);
+            // (one relation: a partition is "its own build side", so every partition above JN_HEAVY is cut)
+            launch_heavy_tasks(L, P.off->as<uint32_t>(), P.off->as<uint32_t>(), P.NP, tasks->as<uint32_t>(),
+                               counters->as<uint32_t>() + 2, max_tasks);
+            // the merge table is sized from the tuples that sit in heavy partitions (an upper bound of
+            // their groups), capped at first: a partition is usually heavy because its keys repeat
+            uint32_t n_heavy = 0;
+            RJ_HIP(hipMemcpyAsync(&n_heavy, counters->as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+            n_heavy = std::min(n_heavy, max_tasks);
+            uint64_t heavy_tuples = std::min<uint64_t>(P.n_tuples, (uint64_t)n_heavy * JN_HEAVY);
+            if (attempt == 0) heavy_tuples = std::min<uint64_t>(heavy_tuples, 1u << 20);
+            const uint32_t m_slots = n_heavy ? (1u << std::min<uint32_t>(ceil_log2(2 * heavy_tuples), 31)) : 0u;
+            const uint64_t me = (uint64_t)m_slots + 2;
+            M.key = ctx->buf(me * 8);
+            M.rows = ctx->buf(me * 8);
+            for (int i = 0; i < ap.n_cols; ++i) {
+                M.nn[i] = ctx->buf(me * 8);
+                M.sum[i] = ctx->buf(me * 8);
+                M.mn[i] = ctx->buf(me * 8);
+                M.mx[i] = ctx->buf(me * 8);
+            }
+            fill(ap.m, M);
+            ap.m_slots = m_slots;
+            ap.m_overflow = counters->as<uint32_t>() + 3;
+            ap.out_cursor = counters->as<unsigned long long>();
+            ap.W = P.w;
+            ap.off = P.off->as<uint32_t>();
+            ap.NP = P.NP;
+            ap.pack = P.packed ? 1 : 0;
+            ap.aos = P.aos3 ? 1 : 0;
+            ap.heavy_tasks = tasks->as<uint32_t>();
+            ap.n_heavy = counters->as<uint32_t>() + 2;
+            ap.heavy_grid = n_heavy;
+            const uint32_t mgrid = (uint32_t)std::min<uint64_t>((me + 255) / 256, (uint64_t)ctx->compute_units() * 8);
+            if (O.keyvalid) RJ_HIP(hipMemsetAsync(O.keyvalid->p, 1, cap, ctx->stream));
+            launch_agg_merge_init(L, ap, mgrid);
+            launch_agg_parts(L, KW, s.CW, ap, n_heavy + P.NP);
+            if (kc.valid) launch_agg_nullkey(L, s.CW, ap, (uint32_t)std::min<uint64_t>((child.n + JN_THREADS - 1) / JN_THREADS,
+                                                                                      (uint64_t)ctx->compute_units() * 4));
+            launch_agg_emit(L, KW, ap, mgrid);
+            uint32_t h[4] = {0, 0, 0, 0};
+            RJ_HIP(hipMemcpyAsync(h, counters->p, 16, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+            nrows = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
+            if (!h[3]) break;
+            // more groups in heavy partitions than the capped table holds: once more (the rounds of
+            // k_agg_parts reorder a partition's memory, so from the partitioning on) with the full bound
+            if (attempt == 1) throw_fmt(RJ_ERR_DEVICE, "aggregation: the merge table overflowed twice");
+        }
+        if (nrows > cap) throw_fmt(RJ_ERR_DEVICE, "aggregation emitted %llu rows out of %llu", (unsigned long long)nrows,
+                                   (unsigned long long)cap);
+
+        // The arrays were sized for the bound (every row its own group).  A result well below it moves
+        // into arrays of its own size, so that neither this node's columns nor a parent hold on to
+        // the bound's memory.
+        if (nrows < cap / 2) {
+            auto shrink = [&](BufP& b, uint64_t width) {
+                if (!b) return;
+                BufP small = ctx->buf(std::max<uint64_t>(nrows, 1) * width);
+                RJ_HIP(hipMemcpyAsync(small->p, b->p, nrows * width, hipMemcpyDeviceToDevice, ctx->stream));
+                b = small;
+            };
+            shrink(O.key, (uint64_t)KW * 4);
+            shrink(O.keyvalid, 1);
+            shrink(O.rows, 8);
+            for (int i = 0; i < ap.n_cols; ++i) {
+                shrink(O.nn[i], 8);
+                shrink(O.sum[i], 8);
+                shrink(O.mn[i], 8);
+                shrink(O.mx[i], 8);
+            }
+        }
+
+        // ---- the output columns: accumulator arrays as they are, narrowed or with validity
+        Rel out;
+        out.n = nrows;
+        for (size_t k = 0; k < outs.size(); ++k) {
+            const AggOut& o = outs[k];
+            DCol          d;
+            d.type = js.out_type[k];
+            d.kind = COL_DENSE;
+            d.width = d.type == RJ_INT32 ? 4 : 8;
+            BufP values, valid;
+            if (o.func == RJ_AGG_KEY) {
+                values = O.key;
+                valid = O.keyvalid;
+            } else if (o.func == RJ_AGG_COUNT_STAR) {
+                values = O.rows;
+            } else if (o.func == RJ_AGG_COUNT) {
+                values = O.nn[o.slot];
+            } else {
+                const BufP& acc = o.func == RJ_AGG_SUM ? O.sum[o.slot] : (o.func == RJ_AGG_MIN ? O.mn[o.slot] : O.mx[o.slot]);
+                const bool  nullable = s.nullable(o.col);
+                values = acc;
+                if (d.width == 4) values = ctx->buf(std::max<uint64_t>(nrows, 1) * 4);
+                if (nullable) valid = ctx->buf(std::max<uint64_t>(nrows, 1));
+                if (d.width == 4 || nullable)
+                    launch_agg_column(L, acc->as<unsigned long long>(), nullable ? O.nn[o.slot]->as<unsigned long long>() : nullptr,
+                                      nrows, d.width, d.width == 4 ? values->as<uint8_t>() : nullptr,
+                                      valid ? valid->as<uint8_t>() : nullptr);
+            }
+            d.hold = values;
+            d.ptr = values->as<uint8_t>();
+            d.hold_valid = valid;
+            d.valid = valid ? valid->as<uint8_t>() : nullptr;
+            out.cols.push_back(d);
+        }
+        if (root_res) rel_to_result(out, *root_res);
+        return out;
+    }
+
+    // a relation of dense columns as a root result: Page images encoded on the device
+    void rel_to_result(const Rel& r, Result& res) {
+        res.num_rows = r.n;
+        for (const DCol& d : r.cols) {
+            ResultColumn rc;
+            rc.type = d.type;
+            if (r.n) {
+                rc.n_pages = pages_for(r.n, d.width);
+                rc.dev_pages = ctx->buf(rc.n_pages * PAGE_BYTES);
+                if (d.valid) {
+                    launch_encode_nullable(L, d.ptr, d.valid, r.n, d.width, rc.dev_pages->as<uint8_t>());
+                } else {
+                    launch_gather(L, d.ref(), nullptr, r.n,
+                                  OutStream{rc.dev_pages->as<uint8_t>(), d.width == 4 ? ST_PAGED32 : ST_PAGED64, 0}, nullptr);
+                    launch_finish_pages(L, rc.dev_pages->as<uint8_t>(), r.n, d.width);
+                }
+            }
+            res.cols.push_back(std::move(rc));
+        }
+    }
+
     static int stream_mode_of(bool is_root, int width, bool direct_output) {
         if (is_root && direct_output) return width == 4 ? ST_PAGED32 : ST_PAGED64;
         return width == 4 ? ST_DENSE32 : ST_DENSE64;
@@ -1860,6 +2153,8 @@ class ShardedExec {
                       : n.kind == RJ_NODE_ANTI  ? "anti (RJ_NODE_ANTI)"
                       : n.kind == RJ_NODE_OUTER ? "outer (RJ_NODE_OUTER)"
                                                 : "full outer (RJ_NODE_FULL)");
+        if (n.kind == RJ_NODE_AGG)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: aggregation (RJ_NODE_AGG) nodes run on one device");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -2247,6 +2542,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "a full outer join node (RJ_NODE_FULL) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_AGG) {
+        if (why) *why = "an aggregation node (RJ_NODE_AGG) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -2317,6 +2616,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_FULL)
         throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds a full outer (RJ_NODE_FULL) join node; full "
                                       "outer joins run on one device");
+    if (n.kind == RJ_NODE_AGG)
+        throw_fmt(RJ_ERR_UNSUPPORTED,
+                  "rj_execute_sharded: the plan holds an aggregation (RJ_NODE_AGG) node; aggregations run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

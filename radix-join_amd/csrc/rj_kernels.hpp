@@ -157,6 +157,20 @@ void launch_full_unmatched(const Launch& L, int key_words, int cw_built, const F
 // fp.use_flags, broadcast — the rows whose flag stayed clear, probed side padded
 void launch_full_buildrows(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid);
 
+// ---- aggregation (AggParams): key_words 1 or 2, carry_words 0..MAX_WORDS - key_words
+// the merge table's entries (ap.m_slots + 2) before anybody adds to them
+void launch_agg_merge_init(const Launch& L, const AggParams& ap, uint32_t grid);
+// grid = ap.heavy_grid + ap.NP (one workgroup per heavy task, then per partition)
+void launch_agg_parts(const Launch& L, int key_words, int carry_words, const AggParams& ap, uint32_t grid);
+// the rows the first radix pass drops (NULL key): one group, into the merge table
+void launch_agg_nullkey(const Launch& L, int carry_words, const AggParams& ap, uint32_t grid);
+// the merge table's live entries -> output rows
+void launch_agg_emit(const Launch& L, int key_words, const AggParams& ap, uint32_t grid);
+// an accumulator array as a result column: values narrowed to `width` bytes (dst, optional) and
+// validity bytes nn[i] != 0 (dst_valid, optional; nn == nullptr: all valid)
+void launch_agg_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int width,
+                       uint8_t* dst, uint8_t* dst_valid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

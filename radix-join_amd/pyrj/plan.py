@@ -49,7 +49,21 @@ class JoinNode:
 
 
 # rj_node_kind (include/rj.h)
-NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL = 0, 1, 2, 3, 4, 5
+NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG = 0, 1, 2, 3, 4, 5, 6
+# rj_agg_func and the RJ_AGG_OUT / RJ_AGG_FUNC / RJ_AGG_COL encoding of an aggregation's out_idx
+AGG_KEY, AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3, 4, 5
+
+
+def agg_out(func, col):
+    return (int(func) << 56) | int(col)
+
+
+def agg_func(x):
+    return int(x) >> 56
+
+
+def agg_col(x):
+    return int(x) & ((1 << 56) - 1)
 
 
 @dataclass
@@ -92,6 +106,15 @@ class FullOuterJoinNode:
 
 
 @dataclass
+class AggNode:
+    """Aggregation (kind NODE_AGG): GROUP BY column key_attr of the one child, one row per distinct
+    key, NULL keys one group.  The PlanNode's output_attrs hold (RJ_AGG_OUT(func, column), result
+    type) pairs (include/rj.h)."""
+    child: int
+    key_attr: int
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -130,6 +153,13 @@ class Plan:
         on it."""
         node = FullOuterJoinNode(bool(build_left), left, right, left_attr, right_attr)
         self.nodes.append(PlanNode(node, list(output_attrs)))
+        return len(self.nodes) - 1
+
+    def new_agg_node(self, child, key_attr, outputs):
+        """GROUP BY key_attr.  outputs = [(func, column, result type)] with func one of AGG_KEY ...
+        AGG_MAX; the column of AGG_COUNT_STAR is 0."""
+        oa = [(agg_out(f, c), t) for f, c, t in outputs]
+        self.nodes.append(PlanNode(AggNode(child, key_attr), oa))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -343,6 +373,10 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.build_left = 1 if n.data.build_left else 0
             nd.left, nd.right = n.data.left, n.data.right
             nd.left_attr, nd.right_attr = n.data.left_attr, n.data.right_attr
+        elif isinstance(n.data, AggNode):
+            nd.kind = NODE_AGG
+            nd.left = n.data.child
+            nd.left_attr = n.data.key_attr
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
