@@ -991,13 +991,12 @@ struct loader_needs_begin<L, std::enable_if_t<L::kNeedsBegin>> : std::true_type 
 // Counting half of the radix partition (reference counterpart: the serial
 // histogram src/execute.cpp:124-132).  LDS atomics per tuple, F global adds per group for
 // the bin totals.
+// (A hot-key test per tuple — one probe of a 4096-entry LDS set, the price of a skew bypass — cost
+// +0.17 ms here and nothing measurable in the scatters.  Taken out again;
+// profiles/r03_am_hot_probe_ab.log is the record.)
 template <class Loader>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_hist(Loader ld, PassParams pp) {
     __shared__ uint32_t s_h[PT_MAXF];
-#if RJ_PT_HOT_PROBE
-    __shared__ uint32_t s_hot[4096];
-    for (uint32_t d = threadIdx.x; d < 4096; d += PT_THREADS) s_hot[d] = 0xffffffffu - d;
-#endif
     uint32_t            seg, begin, end;
     if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
     const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
@@ -1012,9 +1011,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_hist(Loader ld, PassParams 
             ok = ld.key_tile(base, end, hk);
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; ++j) {
-#if RJ_PT_HOT_PROBE
-            if (s_hot[(hk[j] >> 9) & 4095u] == hk[j]) ok &= ~(1u << j);
-#endif
             if ((ok >> j) & 1u) atomicAdd(&s_h[pass_digit(pp, hk[j], mask)], 1u);
         }
     }
@@ -1165,41 +1161,9 @@ __global__ __launch_bounds__(PT_MAXF) void k_scan_fine(const uint32_t* fine, uin
 // bytes instead of 128 + 256 in two places), and the join reads one stream.  The tile is staged
 // in two halves by sorted position (8192 tuples = 96 KiB of LDS each), so the runs are still
 // those of the whole 16384-tuple tile.
-#ifndef RJ_PT_DIAG
-#define RJ_PT_DIAG 0
-#endif
-// Tile prefetch in the key + two-word-carry scatter (next tile's loads issued behind the second
-// half's staging): measured SLOWER at 1 B rows — pass 1 10.4-11.3 -> 12.0 ms, pass 2 9.5 -> 10.2 ms per
-// step (profiles/r03_h_scatter_tile_prefetch_ab.log): the kernels are bound by the memory system's
-// mix of reads and partial-line writes, not by a CU's load latency, and a burst of loads next to
-// the copy-out's stores only gets in their way.  Off; -DRJ_PT_PIPELINE=1 builds it for A/B.
-#ifndef RJ_PT_EXTRA_LOOKUP
-#define RJ_PT_EXTRA_LOOKUP 0
-#endif
-// (experiment: the per-tuple cost of a HOT-KEY test — one probe of a 4096-entry LDS set of hashed keys —
-// in the first pass' histogram and scatter, which a skew bypass (hot probe keys joined straight out of the
-// first pass instead of being partitioned twice) would pay for every tuple.  The set is empty here.)
-#ifndef RJ_PT_HOT_PROBE
-#define RJ_PT_HOT_PROBE 0
-#endif
-#ifndef RJ_PT_PIPELINE
-#define RJ_PT_PIPELINE 0
-#endif
-#if RJ_PT_DIAG
-#define RJ_PT_STAMP(PHASE)                                                      \
-    do {                                                                        \
-        if (pp.diag) {                                                          \
-            unsigned long long _t = __builtin_amdgcn_s_memtime();               \
-            if (threadIdx.x == 0) atomicAdd(&pp.diag[PHASE], _t - diag_t);      \
-            diag_t = _t;                                                        \
-        }                                                                       \
-    } while (0)
-#else
-#define RJ_PT_STAMP(PHASE) \
-    do {                   \
-    } while (0)
-#endif
-
+// (Prefetching the next tile's loads behind the second half's staging lost at 1 B rows, pass 1
+// 10.4-11.3 -> 12.0 ms: a burst of loads next to the copy-out's stores only gets in their way.
+// Taken out again; profiles/r03_h_scatter_tile_prefetch_ab.log is the record.)
 template <int NW, class Loader, int PAIR, bool AOS>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassParams pp, Words out) {
     static_assert(PAIR < 0 || (PAIR >= 1 && PAIR + 1 < NW), "pair = two carry words behind the key");
@@ -1210,10 +1174,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
     __shared__ uint32_t s_base[PT_MAXF];
     __shared__ uint32_t s_delta[PT_MAXF];
     __shared__ uint32_t s_wsum[PT_THREADS / 64];
-#if RJ_PT_HOT_PROBE
-    __shared__ uint32_t s_hot[4096];
-    for (uint32_t d = threadIdx.x; d < 4096; d += PT_THREADS) s_hot[d] = 0xffffffffu - d;
-#endif
     uint32_t            seg, begin, end;
     if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
     const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
@@ -1221,48 +1181,18 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
     // Thread d owns digit d's write cursor in a REGISTER: the reservation's round trip is
     // not waited for until the first tile has been loaded and ranked.
     uint32_t run = 0;  // thread d: where digit d's run of the current tile starts in the output
-#if RJ_PT_EXTRA_LOOKUP
-    uint32_t lookup = 0;
-#define RJ_PT_USE_LOOKUP()                  \
-    do {                                    \
-        asm volatile("" : "+v"(lookup));    \
-        run += lookup & 0u;                 \
-    } while (0)
-#else
-#define RJ_PT_USE_LOOKUP() \
-    do {                   \
-    } while (0)
-#endif
-#if RJ_PT_DIAG
-    unsigned long long diag_t = pp.diag ? __builtin_amdgcn_s_memtime() : 0ull;
-#endif
-
-    // (RJ_PT_PIPELINE, off — see above: the tile's registers are dead once its second half has been
-    // staged, so the NEXT tile's loads could be issued there and fly during that half's copy-out)
-    constexpr bool PIPE = NW == 3 && PAIR == 1 && RJ_PT_PIPELINE;
-    uint32_t       w[PT_ITEMS][NW];
-    uint32_t       ok_raw = 0;
-    if constexpr (PIPE) ok_raw = ld.template issue_tile<NW>(begin, end, w);
+    uint32_t w[PT_ITEMS][NW];
 
     for (uint32_t base = begin; base < end; base += PT_TILE) {
         for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) s_cnt[d] = 0;
         lds_barrier();
-        RJ_PT_STAMP(0);  // counters cleared (+ the previous tile's tail)
 
         uint32_t dr[PT_ITEMS];  // digit << 16 | rank, 0xffffffff = no tuple
         // every load of the tile is issued before the first rank is taken
-        uint32_t ok;
-        if constexpr (PIPE)
-            ok = ld.template finish_tile<NW>(base, end, ok_raw, w);
-        else
-            ok = ld.template load_tile<NW>(base, end, w);
-        RJ_PT_STAMP(1);  // loads issued (+ hashing, which waits for the key loads)
+        const uint32_t ok = ld.template load_tile<NW>(base, end, w);
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; ++j) {
             dr[j] = 0xffffffffu;
-#if RJ_PT_HOT_PROBE
-            if (s_hot[(w[j][0] >> 9) & 4095u] == w[j][0]) ok &= ~(1u << j);
-#endif
             if ((ok >> j) & 1u) {
                 uint32_t d = pass_digit(pp, w[j][0], mask);
                 uint32_t r = atomicAdd(&s_cnt[d], 1u);
@@ -1270,7 +1200,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
             }
         }
         lds_barrier();
-        RJ_PT_STAMP(2);  // ranked (LDS atomics) + barrier
 
         // PT_THREADS >= PT_MAXF: thread d scans digit d
         // Thread d reserves digit d's range of this tile with one global atomic; its round
@@ -1279,21 +1208,11 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
         if (c) {
             run = atomicAdd(&pp.cursor[(((size_t)seg * F + threadIdx.x) << pp.xcd_log2) |
                                        (blockIdx.x & ((1u << pp.xcd_log2) - 1u))], c);
-#if RJ_PT_EXTRA_LOOKUP
-            // (experiment: what a SECOND dependent global round trip per digit and tile would cost — the
-            // chunk-table lookup of a first pass that reserves from chunk lists instead of a histogram's
-            // exact ranges; reads a word of the (by now read-only) bin totals at an index that depends on the
-            // reservation and folds nothing into it.  Reading the cursor array itself, which every
-            // workgroup's atomics keep hot, tripled the first scatter: a chunk table must not share lines
-            // with the cursors)
-            lookup = __builtin_nontemporal_load(&pp.hist[((size_t)(run >> 16) % ((size_t)F << pp.xcd_log2))]);
-#endif
         }
         uint32_t total;
         uint32_t ex = block_excl_scan(c, s_wsum, total);
         if (threadIdx.x < F) s_base[threadIdx.x] = ex;
         lds_barrier();
-        RJ_PT_STAMP(3);  // reservation issued + digit scan
 
         // LDS position of every tuple, computed once for all word arrays
 #pragma unroll
@@ -1308,7 +1227,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
             constexpr uint32_t HALF = PT_TILE / 2;
             uint2* const       s_p = s_stage2;                                      // [HALF] carries
             uint32_t* const    s_k = reinterpret_cast<uint32_t*>(s_stage2 + HALF);  // [HALF] keys
-            RJ_PT_USE_LOOKUP();
             if (threadIdx.x < F) s_delta[threadIdx.x] = run - ex;  // global index = delta + sorted position
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -1321,10 +1239,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
                     }
                 }
                 lds_barrier();
-                RJ_PT_STAMP(4);  // (AOS) half staged (waits for the carry loads)
-                if constexpr (PIPE) {
-                    if (h == 1 && base + PT_TILE < end) ok_raw = ld.template issue_tile<NW>(base + PT_TILE, end, w);
-                }
 #pragma unroll
                 for (int k = 0; k < PT_ITEMS / 2; ++k) {
                     const uint32_t i = k * PT_THREADS + threadIdx.x, gi = h * HALF + i;
@@ -1345,7 +1259,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
                     }
                 }
                 lds_barrier();
-                RJ_PT_STAMP(5);  // (AOS) half copied out (stores issued)
             }
             continue;
         }
@@ -1355,10 +1268,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; ++j)
             if (dr[j] != 0xffffffffu) s_stage[dr[j]] = w[j][0];
-        RJ_PT_USE_LOOKUP();
         if (threadIdx.x < F) s_delta[threadIdx.x] = run - ex;  // global index = delta + LDS position
         lds_barrier();
-        RJ_PT_STAMP(4);  // word 0 staged
         uint32_t dest[PT_ITEMS];
 #pragma unroll
         for (int k = 0; k < PT_ITEMS; ++k) {
@@ -1371,7 +1282,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
             }
         }
         lds_barrier();
-        RJ_PT_STAMP(5);  // word 0 copied out (stores issued)
 #pragma unroll
         for (int a = 1; a < NW; ++a) {
             if constexpr (PAIR >= 0) {
@@ -1382,7 +1292,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
                         if (dr[j] != 0xffffffffu)
                             s_stage2[dr[j]] = make_uint2(w[j][a], w[j][a + 1 < NW ? a + 1 : a]);
                     lds_barrier();
-                    RJ_PT_STAMP(6);  // carry pair staged (waits for the carry loads)
                     uint2* dst2 = reinterpret_cast<uint2*>(out.w[a]);
 #pragma unroll
                     for (int k = 0; k < PT_ITEMS; ++k) {
@@ -1390,7 +1299,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
                         if (i < total) dst2[dest[k]] = s_stage2[i];
                     }
                     lds_barrier();
-                    RJ_PT_STAMP(7);  // carry pair copied out (stores issued)
                     continue;
                 }
             }
@@ -1505,6 +1413,60 @@ __global__ void k_heavy_tasks(const uint32_t* offR, const uint32_t* offS, uint32
         // bounds in 64 bits: a partition ending within JN_HEAVY of 2^32 must not wrap
         tasks[3 * k + 1] = (uint32_t)((uint64_t)sb + (uint64_t)t * JN_HEAVY);
         tasks[3 * k + 2] = (uint32_t)min((uint64_t)se, (uint64_t)sb + (uint64_t)(t + 1) * JN_HEAVY);
+    }
+}
+
+// ============================================= tuples of a partitioned relation
+// One tuple of a partitioned relation (the layouts partition() writes: 12-byte tuples, 8-byte
+// pairs, or word arrays whose last two carry words are one pair array).
+template <int KW, int CW>
+__device__ __forceinline__ void part_tuple(const Words& W, int pack, int aos, uint32_t idx, uint32_t (&t)[KW + CW]) {
+    constexpr int NW = KW + CW;
+    if constexpr (KW == 1 && CW == 2) {
+        if (aos) {
+            const uint32_t* p = W.w[0] + (size_t)idx * 3u;
+            t[0] = p[0];
+            t[1] = p[1];
+            t[2] = p[2];
+            return;
+        }
+    }
+    if constexpr (KW == 1 && CW == 1) {
+        if (pack) {
+            const uint2 v = reinterpret_cast<const uint2*>(W.w[0])[idx];
+            t[0] = v.x;
+            t[1] = v.y;
+            return;
+        }
+    }
+    constexpr int NA = CW >= 2 ? NW - 2 : NW;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) t[a] = W.w[a][idx];
+    if constexpr (CW >= 2) {
+        const uint2 v = reinterpret_cast<const uint2*>(W.w[NA])[idx];
+        t[NA] = v.x;
+        t[NA + 1] = v.y;
+    }
+}
+
+// The carry words behind the key of such a tuple (words the shape does not have: zero).
+template <int KW, int CW>
+__device__ __forceinline__ void tuple_carry(const uint32_t (&t)[KW + CW], uint32_t& c0, uint32_t& c1, uint32_t& c2) {
+    constexpr int W = KW + CW;
+    c0 = CW >= 1 ? t[KW < W ? KW : 0] : 0u;
+    c1 = CW >= 2 ? t[KW + 1 < W ? KW + 1 : 0] : 0u;
+    c2 = CW == 3 ? t[W - 1] : 0u;
+}
+
+// A hashed key (lo, hi: KW words) back to the key the source column held.
+template <int KW>
+__device__ __forceinline__ void unhash_key(uint32_t lo, uint32_t hi, uint32_t& k0, uint32_t& k1) {
+    if constexpr (KW == 1) {
+        k0 = unfmix32(lo);
+    } else {
+        const uint64_t k64 = unfmix64((uint64_t)lo | ((uint64_t)hi << 32));
+        k0 = (uint32_t)k64;
+        k1 = (uint32_t)(k64 >> 32);
     }
 }
 
@@ -1840,14 +1802,8 @@ __global__ __launch_bounds__(jn_threads(TG ? 2 : KW + CWR), jn_min_waves(TG ? 2 
             continue;
         }
         if (!haveR) load_build(cur.rbeg, min((uint32_t)JN_RMAX, cur.rend - cur.rbeg));
-        // TGLATE (experiment): the tagged variant loads its first probe sub-chunk only after the
-        // build, when the build tuples' registers are free (peak live registers: 24 + 24 words)
-#ifndef RJ_TG_LATE
-#define RJ_TG_LATE 0
-#endif
-        constexpr bool late_probe = TG && RJ_TG_LATE;
-        if (!haveS && !late_probe) load_probe(cur.sbeg, min((uint32_t)SUB, cur.send - cur.sbeg));
-        uint32_t sw_pos = late_probe ? 0xffffffffu : cur.sbeg;  // which probe sub-chunk sw holds
+        if (!haveS) load_probe(cur.sbeg, min((uint32_t)SUB, cur.send - cur.sbeg));
+        uint32_t sw_pos = cur.sbeg;  // which probe sub-chunk sw holds
         RJ_STAMP(0);  // loads issued
 
         // The low radix bits every hashed key of partition q shares, rebuilt from q
@@ -2025,14 +1981,7 @@ __global__ __launch_bounds__(jn_threads(TG ? 2 : KW + CWR), jn_min_waves(TG ? 2 
                         if (m[j] == 0) continue;
                         uint64_t row = obase + pre[j];
                         uint32_t klo, khi = 0;
-                        if (KW == 1) {
-                            klo = unfmix32(sw[j][0]);
-                        } else {
-                            uint64_t k64 =
-                                unfmix64((uint64_t)sw[j][0] | ((uint64_t)sw[j][KW - 1] << 32));
-                            klo = (uint32_t)k64;
-                            khi = (uint32_t)(k64 >> 32);
-                        }
+                        unhash_key<KW>(sw[j][0], sw[j][KW - 1], klo, khi);
                         const uint32_t p0 = CWS >= 1 ? sw[j][KW < SW ? KW : 0] : 0u;
                         const uint32_t p1 = CWS >= 2 ? sw[j][KW + 1 < SW ? KW + 1 : 0] : 0u;
                         const uint32_t p2 = CWS == 3 ? sw[j][SW - 1] : 0u;
@@ -2268,13 +2217,7 @@ __global__ __launch_bounds__(JN_THREADS) void k_join_bcast(BcastParams bp) {
                 const uint32_t srow = (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x);
                 uint64_t       row = obase + pre[j];
                 uint32_t       k0, k1 = 0;
-                if (KW == 1) {
-                    k0 = unfmix32(klo[j]);
-                } else {
-                    uint64_t k64 = unfmix64((uint64_t)klo[j] | ((uint64_t)khi[j] << 32));
-                    k0 = (uint32_t)k64;
-                    k1 = (uint32_t)(k64 >> 32);
-                }
+                unhash_key<KW>(klo[j], khi[j], k0, k1);
                 uint32_t p0, p1, p2;
                 src_carry<CWS>(bp.S, srow, p0, p1, p2);
                 uint32_t b = klo[j] & BMASK;
@@ -2403,13 +2346,7 @@ __device__ __forceinline__ void filter_emit(const FilterParams& fp, const bool (
         if (!e[j] || row >= fp.out_cap) continue;
         if (fp.key.mode != ST_NONE) {
             uint32_t k0, k1 = 0;
-            if constexpr (KW == 1) {
-                k0 = unfmix32(klo[j]);
-            } else {
-                const uint64_t k64 = unfmix64((uint64_t)klo[j] | ((uint64_t)khi[j] << 32));
-                k0 = (uint32_t)k64;
-                k1 = (uint32_t)(k64 >> 32);
-            }
+            unhash_key<KW>(klo[j], khi[j], k0, k1);
             stream_store(fp.key, row, k0, k1);
         }
         if (fp.pc.mode != ST_NONE) {
@@ -2555,31 +2492,7 @@ __global__ __launch_bounds__(JN_THREADS) void k_filter_join(FilterParams fp) {
         for (int j = 0; j < SPT; ++j) {
             // (items past the chunk re-read its last tuple; they are masked off)
             const uint32_t idx = sc + min((uint32_t)(j * TH + threadIdx.x), sn - 1u);
-            if constexpr (KW == 1 && CWS == 2) {
-                if (fp.aosP) {
-                    const uint32_t* p = fp.Pw.w[0] + (size_t)idx * 3u;
-                    sw[j][0] = p[0];
-                    sw[j][1] = p[1];
-                    sw[j][2] = p[2];
-                    continue;
-                }
-            }
-            if constexpr (KW == 1 && CWS == 1) {
-                if (fp.packP) {
-                    const uint2 t = reinterpret_cast<const uint2*>(fp.Pw.w[0])[idx];
-                    sw[j][0] = t.x;
-                    sw[j][1] = t.y;
-                    continue;
-                }
-            }
-            constexpr int NA = CWS >= 2 ? KW + CWS - 2 : SW;  // plain word arrays; the last two carry words are a pair array
-#pragma unroll
-            for (int a = 0; a < NA; ++a) sw[j][a] = fp.Pw.w[a][idx];
-            if constexpr (CWS >= 2) {
-                const uint2 t = reinterpret_cast<const uint2*>(fp.Pw.w[NA])[idx];
-                sw[j][NA] = t.x;
-                sw[j][NA + 1] = t.y;
-            }
+            part_tuple<KW, CWS>(fp.Pw, fp.packP, fp.aosP, idx, sw[j]);
         }
     };
 
@@ -2608,9 +2521,7 @@ __global__ __launch_bounds__(JN_THREADS) void k_filter_join(FilterParams fp) {
             e[j] = (uint32_t)(j * TH + threadIdx.x) < sn && (fp.anti ? !hit[j] : hit[j]);
         }
         filter_emit<KW, SPT>(fp, e, klo, khi, s_wtot, &s_obase, [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-            p0 = CWS >= 1 ? sw[j][KW < SW ? KW : 0] : 0u;
-            p1 = CWS >= 2 ? sw[j][KW + 1 < SW ? KW + 1 : 0] : 0u;
-            p2 = CWS == 3 ? sw[j][SW - 1] : 0u;
+            tuple_carry<KW, CWS>(sw[j], p0, p1, p2);
         });
     }
 }
@@ -2672,38 +2583,6 @@ struct OuterTable {
         return eq & ((1u << min(c, 4u)) - 1u);
     }
 };
-
-// One tuple of a partitioned relation (the layouts partition() writes: 12-byte tuples, 8-byte
-// pairs, or word arrays whose last two carry words are one pair array).
-template <int KW, int CW>
-__device__ __forceinline__ void part_tuple(const Words& W, int pack, int aos, uint32_t idx, uint32_t (&t)[KW + CW]) {
-    constexpr int NW = KW + CW;
-    if constexpr (KW == 1 && CW == 2) {
-        if (aos) {
-            const uint32_t* p = W.w[0] + (size_t)idx * 3u;
-            t[0] = p[0];
-            t[1] = p[1];
-            t[2] = p[2];
-            return;
-        }
-    }
-    if constexpr (KW == 1 && CW == 1) {
-        if (pack) {
-            const uint2 v = reinterpret_cast<const uint2*>(W.w[0])[idx];
-            t[0] = v.x;
-            t[1] = v.y;
-            return;
-        }
-    }
-    constexpr int NA = CW >= 2 ? NW - 2 : NW;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) t[a] = W.w[a][idx];
-    if constexpr (CW >= 2) {
-        const uint2 v = reinterpret_cast<const uint2*>(W.w[NA])[idx];
-        t[NA] = v.x;
-        t[NA + 1] = v.y;
-    }
-}
 
 // Probe SPT items per thread against the table and emit: every match of an item with probe[j]
 // set, and one padded row for an item with padrow[j] set that has no match now and had none
@@ -2789,15 +2668,7 @@ __device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTab
             if (cnt[j] == 0) continue;
             uint64_t row = obase + pre[j];
             uint32_t k0 = 0, k1 = 0;
-            if (!FULL && op.key.mode != ST_NONE) {
-                if constexpr (KW == 1) {
-                    k0 = unfmix32(klo[j]);
-                } else {
-                    const uint64_t k64 = unfmix64((uint64_t)klo[j] | ((uint64_t)khi[j] << 32));
-                    k0 = (uint32_t)k64;
-                    k1 = (uint32_t)(k64 >> 32);
-                }
-            }
+            if (!FULL && op.key.mode != ST_NONE) unhash_key<KW>(klo[j], khi[j], k0, k1);
             uint32_t p0 = 0, p1 = 0, p2 = 0;
             if constexpr (CWP >= 1) pcarry(j, p0, p1, p2);
             if (m[j] == 0) {  // no partner in any round: the padded row
@@ -2979,8 +2850,9 @@ __global__ __launch_bounds__(JN_THREADS) void k_full_unmatched(FullParams fp) {
             if constexpr (CWB >= 1) {
                 uint32_t t[BW];
                 part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), t);
-                stream_store(op.bc, row, t[KW < BW ? KW : 0], CWB >= 2 ? t[KW + 1 < BW ? KW + 1 : 0] : 0u,
-                             CWB == 3 ? t[BW - 1] : 0u);
+                uint32_t b0, b1, b2;
+                tuple_carry<KW, CWB>(t, b0, b1, b2);
+                stream_store(op.bc, row, b0, b1, b2);
             }
             stream_store(op.pc, row, fp.pad_pc, 0u, 0u);
         }
@@ -3606,6 +3478,34 @@ __global__ __launch_bounds__(256) void k_agg_column(const unsigned long long* sr
         if (_le != hipSuccess) launch_failed(NAME, hipGetErrorString(_le), false);             \
     } while (0)
 
+// The one shape rule of the tuple kernels: one or two key words, zero to three carry words,
+// KW + CW <= MAX_WORDS.  for_shape turns run-time word counts into compile-time ones: it walks the
+// shapes in the order (KW, CW) and calls f(int_c<KW>, int_c<CW>) for the match, so a launcher
+// instantiates exactly the kernels of the rule; any other count is an unsupported launch.
+template <int N>
+using int_c = std::integral_constant<int, N>;
+
+template <int KW = 1, int CW = 0, class F>
+static void for_shape(const char* name, int kw, int cw, F&& f) {
+    if constexpr (KW > 2) {
+        launch_failed(name, "no kernel for this key/carry word count", true);
+    } else {
+        if constexpr (KW + CW <= MAX_WORDS)
+            if (kw == KW && cw == CW) return f(int_c<KW>{}, int_c<CW>{});
+        for_shape<(CW < 3 ? KW : KW + 1), (CW < 3 ? CW + 1 : 0)>(name, kw, cw, f);
+    }
+}
+
+// two carries behind the same key: f(int_c<KW>, int_c<CWA>, int_c<CWB>)
+template <class F>
+static void for_shape2(const char* name, int kw, int cwa, int cwb, F&& f) {
+    for_shape(name, kw, cwa, [&](auto KW, auto CWA) {
+        for_shape(name, kw, cwb, [&](auto KW2, auto CWB) {
+            if constexpr (decltype(KW2)::value == decltype(KW)::value) f(KW, CWA, CWB);
+        });
+    });
+}
+
 void launch_page_headers(const Launch& L, const uint8_t* pages, uint32_t n_pages, uint32_t rows_full,
                          uint32_t* page_rows, unsigned long long* flags) {
     if (!n_pages) return;
@@ -3732,15 +3632,12 @@ void launch_pass_scatter_src(const Launch& L, const TupleSrc& src, int key_words
         }
         return;
     }
-    switch (key_words * 10 + carry_words) {
-    case 10: scatter_src_t<1, 0>(L, src, pp, n_groups, out); break;
-    case 11: scatter_src_t<1, 1>(L, src, pp, n_groups, out); break;
-    case 12: scatter_src_t<1, 2>(L, src, pp, n_groups, out); break;
-    case 20: scatter_src_t<2, 0>(L, src, pp, n_groups, out); break;
-    case 21: scatter_src_t<2, 1>(L, src, pp, n_groups, out); break;
-    case 22: scatter_src_t<2, 2>(L, src, pp, n_groups, out); break;
-    default: launch_failed("pass1_scatter", "no kernel for this key/carry word count", true);
-    }
+    for_shape("pass1_scatter", key_words, carry_words, [&](auto KW, auto CW) {
+        if constexpr (CW <= 2)  // (three carry words travel only as a wide carry, above)
+            scatter_src_t<KW, CW>(L, src, pp, n_groups, out);
+        else
+            launch_failed("pass1_scatter", "no kernel for this key/carry word count", true);
+    });
 }
 
 void launch_pass_hist_dense(const Launch& L, const Words& in, const PassParams& pp,
@@ -3855,11 +3752,8 @@ void launch_heavy_tasks(const Launch& L, const uint32_t* offR, const uint32_t* o
 }
 
 // tagged table (see k_join): one key word + two-word build carry, >= 14 radix bits
-#ifndef RJ_TG_ENABLE
-#define RJ_TG_ENABLE 1
-#endif
 static bool join_tagged(int key_words, int cw_build, const JoinParams& jp) {
-    return RJ_TG_ENABLE && key_words == 1 && cw_build == 2 && jp.radix_bits >= 14 && jp.radix_bits <= 31;
+    return key_words == 1 && cw_build == 2 && jp.radix_bits >= 14 && jp.radix_bits <= 31;
 }
 
 template <int KW, int CWR, int CWS, int PK>
@@ -3917,18 +3811,15 @@ static void join_t(const Launch& L, const JoinParams& jp, uint32_t grid) {
                         (KW == 1 && CWR == 2 ? 4 : 0) | (KW == 1 && CWS == 2 ? 8 : 0);
     const int     pk = (jp.packR ? 1 : 0) | (jp.packS ? 2 : 0) | (jp.aosR ? 4 : 0) | (jp.aosS ? 8 : 0);
     if (pk & ~CAN) launch_failed("join_build_probe", "tuple layout flags do not fit the key/carry widths", true);
-#define RJ_JOIN_PK(V)                 \
-    if constexpr ((CAN & (V)) == (V)) \
-        if (pk == (V)) return join_pk<KW, CWR, CWS, (V)>(L, jp, grid);
-    RJ_JOIN_PK(1)
-    RJ_JOIN_PK(2)
-    RJ_JOIN_PK(3)
-    RJ_JOIN_PK(4)
-    RJ_JOIN_PK(8)
-    RJ_JOIN_PK(12)
-    RJ_JOIN_PK(6)
-    RJ_JOIN_PK(9)
-#undef RJ_JOIN_PK
+    auto packed = [&](auto... V) {  // the first layout V that is this join's: its kernel
+        auto one = [&](auto v) {
+            if constexpr ((CAN & v) == v)
+                if (pk == v) return join_pk<KW, CWR, CWS, v>(L, jp, grid), true;
+            return false;
+        };
+        return (... || one(V));
+    };
+    if (packed(int_c<1>{}, int_c<2>{}, int_c<3>{}, int_c<4>{}, int_c<8>{}, int_c<12>{}, int_c<6>{}, int_c<9>{})) return;
     if (pk != 0) launch_failed("join_build_probe", "no kernel for this tuple layout", true);
     join_pk<KW, CWR, CWS, 0>(L, jp, grid);
 }
@@ -3940,178 +3831,93 @@ uint32_t join_partitions_per_workgroup(int key_words, int cw_build, const JoinPa
 void launch_join(const Launch& L, int key_words, int cw_build, int cw_probe, const JoinParams& jp,
                  uint32_t grid) {
     if (!grid) return;
-    switch (key_words * 100 + cw_build * 10 + cw_probe) {
-    case 100: join_t<1, 0, 0>(L, jp, grid); break;
-    case 101: join_t<1, 0, 1>(L, jp, grid); break;
-    case 102: join_t<1, 0, 2>(L, jp, grid); break;
-    case 110: join_t<1, 1, 0>(L, jp, grid); break;
-    case 111: join_t<1, 1, 1>(L, jp, grid); break;
-    case 112: join_t<1, 1, 2>(L, jp, grid); break;
-    case 120: join_t<1, 2, 0>(L, jp, grid); break;
-    case 121: join_t<1, 2, 1>(L, jp, grid); break;
-    case 122: join_t<1, 2, 2>(L, jp, grid); break;
-    case 103: join_t<1, 0, 3>(L, jp, grid); break;  // three-word (wide) carries
-    case 113: join_t<1, 1, 3>(L, jp, grid); break;
-    case 123: join_t<1, 2, 3>(L, jp, grid); break;
-    case 130: join_t<1, 3, 0>(L, jp, grid); break;
-    case 131: join_t<1, 3, 1>(L, jp, grid); break;
-    case 132: join_t<1, 3, 2>(L, jp, grid); break;
-    case 133: join_t<1, 3, 3>(L, jp, grid); break;
-    case 200: join_t<2, 0, 0>(L, jp, grid); break;
-    case 201: join_t<2, 0, 1>(L, jp, grid); break;
-    case 202: join_t<2, 0, 2>(L, jp, grid); break;
-    case 210: join_t<2, 1, 0>(L, jp, grid); break;
-    case 211: join_t<2, 1, 1>(L, jp, grid); break;
-    case 212: join_t<2, 1, 2>(L, jp, grid); break;
-    case 220: join_t<2, 2, 0>(L, jp, grid); break;
-    case 221: join_t<2, 2, 1>(L, jp, grid); break;
-    case 222: join_t<2, 2, 2>(L, jp, grid); break;
-    default: launch_failed("join_build_probe", "no kernel for this key/carry word count", true);
-    }
-}
-
-template <int KW, int CWR, int CWS>
-static void join_bcast_t(const Launch& L, const BcastParams& bp, uint32_t grid) {
-    RJ_KLAUNCH(L, "join_broadcast", (k_join_bcast<KW, CWR, CWS>), grid, JN_THREADS, bp);
+    for_shape2("join_build_probe", key_words, cw_build, cw_probe,
+               [&](auto KW, auto CWR, auto CWS) { join_t<KW, CWR, CWS>(L, jp, grid); });
 }
 
 void launch_join_bcast(const Launch& L, int key_words, int cw_build, int cw_probe,
                        const BcastParams& bp, uint32_t grid) {
     if (!grid) return;
-    switch (key_words * 100 + cw_build * 10 + cw_probe) {
-    case 100: join_bcast_t<1, 0, 0>(L, bp, grid); break;
-    case 101: join_bcast_t<1, 0, 1>(L, bp, grid); break;
-    case 102: join_bcast_t<1, 0, 2>(L, bp, grid); break;
-    case 110: join_bcast_t<1, 1, 0>(L, bp, grid); break;
-    case 111: join_bcast_t<1, 1, 1>(L, bp, grid); break;
-    case 112: join_bcast_t<1, 1, 2>(L, bp, grid); break;
-    case 120: join_bcast_t<1, 2, 0>(L, bp, grid); break;
-    case 121: join_bcast_t<1, 2, 1>(L, bp, grid); break;
-    case 122: join_bcast_t<1, 2, 2>(L, bp, grid); break;
-    case 103: join_bcast_t<1, 0, 3>(L, bp, grid); break;
-    case 113: join_bcast_t<1, 1, 3>(L, bp, grid); break;
-    case 123: join_bcast_t<1, 2, 3>(L, bp, grid); break;
-    case 130: join_bcast_t<1, 3, 0>(L, bp, grid); break;
-    case 131: join_bcast_t<1, 3, 1>(L, bp, grid); break;
-    case 132: join_bcast_t<1, 3, 2>(L, bp, grid); break;
-    case 133: join_bcast_t<1, 3, 3>(L, bp, grid); break;
-    case 200: join_bcast_t<2, 0, 0>(L, bp, grid); break;
-    case 201: join_bcast_t<2, 0, 1>(L, bp, grid); break;
-    case 202: join_bcast_t<2, 0, 2>(L, bp, grid); break;
-    case 210: join_bcast_t<2, 1, 0>(L, bp, grid); break;
-    case 211: join_bcast_t<2, 1, 1>(L, bp, grid); break;
-    case 212: join_bcast_t<2, 1, 2>(L, bp, grid); break;
-    case 220: join_bcast_t<2, 2, 0>(L, bp, grid); break;
-    case 221: join_bcast_t<2, 2, 1>(L, bp, grid); break;
-    case 222: join_bcast_t<2, 2, 2>(L, bp, grid); break;
-    default: launch_failed("join_broadcast", "no kernel for this key/carry word count", true);
-    }
+    for_shape2("join_broadcast", key_words, cw_build, cw_probe, [&](auto KW, auto CWR, auto CWS) {
+        RJ_KLAUNCH(L, "join_broadcast", (k_join_bcast<KW, CWR, CWS>), grid, JN_THREADS, bp);
+    });
 }
 
-// semi / anti joins: KW 1 with 0..3 preserved carry words, KW 2 with 0..2
-#define RJ_FILTER_DISPATCH(NAME, KERNEL)                                                              \
-    if (!grid) return;                                                                                \
-    switch (key_words * 10 + cw_preserved) {                                                          \
-    case 10: RJ_KLAUNCH(L, NAME, (KERNEL<1, 0>), grid, JN_THREADS, fp); break;                        \
-    case 11: RJ_KLAUNCH(L, NAME, (KERNEL<1, 1>), grid, JN_THREADS, fp); break;                        \
-    case 12: RJ_KLAUNCH(L, NAME, (KERNEL<1, 2>), grid, JN_THREADS, fp); break;                        \
-    case 13: RJ_KLAUNCH(L, NAME, (KERNEL<1, 3>), grid, JN_THREADS, fp); break;                        \
-    case 20: RJ_KLAUNCH(L, NAME, (KERNEL<2, 0>), grid, JN_THREADS, fp); break;                        \
-    case 21: RJ_KLAUNCH(L, NAME, (KERNEL<2, 1>), grid, JN_THREADS, fp); break;                        \
-    case 22: RJ_KLAUNCH(L, NAME, (KERNEL<2, 2>), grid, JN_THREADS, fp); break;                        \
-    default: launch_failed(NAME, "no kernel for this key/carry word count", true);                    \
-    }
-
+// semi / anti joins: the preserved side's carry
 void launch_filter_bcast(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid) {
-    RJ_FILTER_DISPATCH("filter_broadcast", k_filter_bcast)
+    if (!grid) return;
+    for_shape("filter_broadcast", key_words, cw_preserved, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "filter_broadcast", (k_filter_bcast<KW, CW>), grid, JN_THREADS, fp);
+    });
 }
 
 void launch_filter_join(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid) {
-    RJ_FILTER_DISPATCH("filter_probe", k_filter_join)
+    if (!grid) return;
+    for_shape("filter_probe", key_words, cw_preserved, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "filter_probe", (k_filter_join<KW, CW>), grid, JN_THREADS, fp);
+    });
 }
 
 void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid) {
-    RJ_FILTER_DISPATCH("filter_nullkeys", k_filter_nullkeys)
+    if (!grid) return;
+    for_shape("filter_nullkeys", key_words, cw_preserved, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "filter_nullkeys", (k_filter_nullkeys<KW, CW>), grid, JN_THREADS, fp);
+    });
 }
-#undef RJ_FILTER_DISPATCH
 
-// outer joins: KW 1 with 0..3 optional and 0..3 preserved carry words, KW 2 with 0..2 of each
-#define RJ_OUTER_ROW(NAME, KERNEL, KW, CWB, C0)                                                       \
-    case C0 + 0: RJ_KLAUNCH(L, NAME, (KERNEL<KW, CWB, 0>), grid, JN_THREADS, op); break;              \
-    case C0 + 1: RJ_KLAUNCH(L, NAME, (KERNEL<KW, CWB, 1>), grid, JN_THREADS, op); break;              \
-    case C0 + 2: RJ_KLAUNCH(L, NAME, (KERNEL<KW, CWB, 2>), grid, JN_THREADS, op); break;
-#define RJ_OUTER_DISPATCH(NAME, KERNEL)                                                               \
-    if (!grid) return;                                                                                \
-    switch (key_words * 100 + cw_optional * 10 + cw_preserved) {                                      \
-        RJ_OUTER_ROW(NAME, KERNEL, 1, 0, 100)                                                         \
-    case 103: RJ_KLAUNCH(L, NAME, (KERNEL<1, 0, 3>), grid, JN_THREADS, op); break;                    \
-        RJ_OUTER_ROW(NAME, KERNEL, 1, 1, 110)                                                         \
-    case 113: RJ_KLAUNCH(L, NAME, (KERNEL<1, 1, 3>), grid, JN_THREADS, op); break;                    \
-        RJ_OUTER_ROW(NAME, KERNEL, 1, 2, 120)                                                         \
-    case 123: RJ_KLAUNCH(L, NAME, (KERNEL<1, 2, 3>), grid, JN_THREADS, op); break;                    \
-        RJ_OUTER_ROW(NAME, KERNEL, 1, 3, 130)                                                         \
-    case 133: RJ_KLAUNCH(L, NAME, (KERNEL<1, 3, 3>), grid, JN_THREADS, op); break;                    \
-        RJ_OUTER_ROW(NAME, KERNEL, 2, 0, 200)                                                         \
-        RJ_OUTER_ROW(NAME, KERNEL, 2, 1, 210)                                                         \
-        RJ_OUTER_ROW(NAME, KERNEL, 2, 2, 220)                                                         \
-    default: launch_failed(NAME, "no kernel for this key/carry word count", true);                    \
-    }
-
+// outer joins: the optional and the preserved side's carries
 void launch_outer_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
                         uint32_t grid) {
-    RJ_OUTER_DISPATCH("outer_broadcast", k_outer_bcast)
+    if (!grid) return;
+    for_shape2("outer_broadcast", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
+        RJ_KLAUNCH(L, "outer_broadcast", (k_outer_bcast<KW, CWB, CWP>), grid, JN_THREADS, op);
+    });
 }
 
 void launch_outer_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
                        uint32_t grid) {
-    RJ_OUTER_DISPATCH("outer_probe", k_outer_join)
+    if (!grid) return;
+    for_shape2("outer_probe", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
+        RJ_KLAUNCH(L, "outer_probe", (k_outer_join<KW, CWB, CWP>), grid, JN_THREADS, op);
+    });
 }
 
-// full outer joins: the outer join's 25 shapes, both carries optional
+// full outer joins: the outer join's shapes, both carries optional
 void launch_full_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& op,
                        uint32_t grid) {
-    RJ_OUTER_DISPATCH("full_broadcast", k_full_bcast)
+    if (!grid) return;
+    for_shape2("full_broadcast", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
+        RJ_KLAUNCH(L, "full_broadcast", (k_full_bcast<KW, CWB, CWP>), grid, JN_THREADS, op);
+    });
 }
 
 void launch_full_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& op,
                       uint32_t grid) {
-    RJ_OUTER_DISPATCH("full_probe", k_full_join)
+    if (!grid) return;
+    for_shape2("full_probe", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
+        RJ_KLAUNCH(L, "full_probe", (k_full_join<KW, CWB, CWP>), grid, JN_THREADS, op);
+    });
 }
-#undef RJ_OUTER_DISPATCH
-#undef RJ_OUTER_ROW
 
-#define RJ_FULL_BUILD_DISPATCH(NAME, KERNEL)                                                          \
-    if (!grid) return;                                                                                \
-    switch (key_words * 10 + cw_built) {                                                              \
-    case 10: RJ_KLAUNCH(L, NAME, (KERNEL<1, 0>), grid, JN_THREADS, fp); break;                        \
-    case 11: RJ_KLAUNCH(L, NAME, (KERNEL<1, 1>), grid, JN_THREADS, fp); break;                        \
-    case 12: RJ_KLAUNCH(L, NAME, (KERNEL<1, 2>), grid, JN_THREADS, fp); break;                        \
-    case 13: RJ_KLAUNCH(L, NAME, (KERNEL<1, 3>), grid, JN_THREADS, fp); break;                        \
-    case 20: RJ_KLAUNCH(L, NAME, (KERNEL<2, 0>), grid, JN_THREADS, fp); break;                        \
-    case 21: RJ_KLAUNCH(L, NAME, (KERNEL<2, 1>), grid, JN_THREADS, fp); break;                        \
-    case 22: RJ_KLAUNCH(L, NAME, (KERNEL<2, 2>), grid, JN_THREADS, fp); break;                        \
-    default: launch_failed(NAME, "no kernel for this key/carry word count", true);                    \
-    }
 void launch_full_unmatched(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid) {
-    RJ_FULL_BUILD_DISPATCH("full_unmatched", k_full_unmatched)
+    if (!grid) return;
+    for_shape("full_unmatched", key_words, cw_built, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "full_unmatched", (k_full_unmatched<KW, CW>), grid, JN_THREADS, fp);
+    });
 }
+
 void launch_full_buildrows(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid) {
-    RJ_FULL_BUILD_DISPATCH("full_buildrows", k_full_buildrows)
+    if (!grid) return;
+    for_shape("full_buildrows", key_words, cw_built, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "full_buildrows", (k_full_buildrows<KW, CW>), grid, JN_THREADS, fp);
+    });
 }
-#undef RJ_FULL_BUILD_DISPATCH
 
 void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, const OuterParams& op, uint32_t grid) {
     if (!grid) return;
-    switch (key_words * 10 + cw_preserved) {
-    case 10: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 0>), grid, JN_THREADS, op); break;
-    case 11: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 1>), grid, JN_THREADS, op); break;
-    case 12: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 2>), grid, JN_THREADS, op); break;
-    case 13: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<1, 3>), grid, JN_THREADS, op); break;
-    case 20: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<2, 0>), grid, JN_THREADS, op); break;
-    case 21: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<2, 1>), grid, JN_THREADS, op); break;
-    case 22: RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<2, 2>), grid, JN_THREADS, op); break;
-    default: launch_failed("outer_nullkeys", "no kernel for this key/carry word count", true);
-    }
+    for_shape("outer_nullkeys", key_words, cw_preserved, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<KW, CW>), grid, JN_THREADS, op);
+    });
 }
 
 void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
@@ -4193,26 +3999,15 @@ void launch_agg_merge_init(const Launch& L, const AggParams& ap, uint32_t grid) 
 }
 void launch_agg_parts(const Launch& L, int key_words, int carry_words, const AggParams& ap, uint32_t grid) {
     if (!grid) return;
-    switch (key_words * 10 + carry_words) {
-    case 10: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<1, 0>), grid, AGG_THREADS, ap); break;
-    case 11: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<1, 1>), grid, AGG_THREADS, ap); break;
-    case 12: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<1, 2>), grid, AGG_THREADS, ap); break;
-    case 13: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<1, 3>), grid, AGG_THREADS, ap); break;
-    case 20: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<2, 0>), grid, AGG_THREADS, ap); break;
-    case 21: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<2, 1>), grid, AGG_THREADS, ap); break;
-    case 22: RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<2, 2>), grid, AGG_THREADS, ap); break;
-    default: launch_failed("agg_parts", "no kernel for this key/carry word count", true);
-    }
+    for_shape("agg_parts", key_words, carry_words, [&](auto KW, auto CW) {
+        RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<KW, CW>), grid, AGG_THREADS, ap);
+    });
 }
 void launch_agg_nullkey(const Launch& L, int carry_words, const AggParams& ap, uint32_t grid) {
     if (!grid) return;
-    switch (carry_words) {
-    case 0: RJ_KLAUNCH(L, "agg_nullkey", (k_agg_nullkey<0>), grid, JN_THREADS, ap); break;
-    case 1: RJ_KLAUNCH(L, "agg_nullkey", (k_agg_nullkey<1>), grid, JN_THREADS, ap); break;
-    case 2: RJ_KLAUNCH(L, "agg_nullkey", (k_agg_nullkey<2>), grid, JN_THREADS, ap); break;
-    case 3: RJ_KLAUNCH(L, "agg_nullkey", (k_agg_nullkey<3>), grid, JN_THREADS, ap); break;
-    default: launch_failed("agg_nullkey", "no kernel for this carry word count", true);
-    }
+    for_shape("agg_nullkey", 1, carry_words, [&](auto, auto CW) {  // (no key: the carries of a one-word key)
+        RJ_KLAUNCH(L, "agg_nullkey", (k_agg_nullkey<CW>), grid, JN_THREADS, ap);
+    });
 }
 void launch_agg_emit(const Launch& L, int key_words, const AggParams& ap, uint32_t grid) {
     if (key_words == 1)

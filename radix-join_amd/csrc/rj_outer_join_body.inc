@@ -90,15 +90,9 @@
                 [&](uint32_t ref, uint32_t& b0, uint32_t& b1, uint32_t& b2) {
                     uint32_t t[BW];
                     part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, ref, t);
-                    b0 = CWB >= 1 ? t[KW < BW ? KW : 0] : 0u;
-                    b1 = CWB >= 2 ? t[KW + 1 < BW ? KW + 1 : 0] : 0u;
-                    b2 = CWB == 3 ? t[BW - 1] : 0u;
+                    tuple_carry<KW, CWB>(t, b0, b1, b2);
                 },
-                [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-                    p0 = CWP >= 1 ? sw[j][KW < SW ? KW : 0] : 0u;
-                    p1 = CWP >= 2 ? sw[j][KW + 1 < SW ? KW + 1 : 0] : 0u;
-                    p2 = CWP == 3 ? sw[j][SW - 1] : 0u;
-                },
+                [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) { tuple_carry<KW, CWP>(sw[j], p0, p1, p2); },
                 s_flag, flag_base);
             if (last) break;
             end = build_round(end);
