@@ -344,6 +344,7 @@ __global__ __launch_bounds__(256) void k_vc_encode(const uint8_t* pages, uint32_
 #define RJ_VLAUNCH(L, NAME, KERNEL, GRID, BLOCK, ...)                                          \
     do {                                                                                       \
         hipEvent_t _ev0 = nullptr, _ev1 = nullptr;                                             \
+        if ((L).logged) (L).logged((L).self, reinterpret_cast<const void*>(KERNEL));           \
         if ((L).timed && (L).timed((L).self, NAME, &_ev0, &_ev1))                              \
             hipExtLaunchKernelGGL(KERNEL, dim3(GRID), dim3(BLOCK), 0, (L).stream, _ev0, _ev1,  \
                                   0, __VA_ARGS__);                                             \
@@ -382,7 +383,8 @@ void launch_vc_compact(const Launch& L, const uint8_t* keep, const uint32_t* bid
 }
 
 // RJ_CTX_PREWARM: one harmless launch, so that HIP loads this translation unit's code object when
-// the context is built (zeroed[0..64) must be zero: a `keep` mask of zeros compacts nothing)
+// the context is built (zeroed[0..64) must be zero: a `keep` mask of zeros compacts nothing).
+// With the launch log on, this launch is reported as k_vc_compact like any other.
 void prewarm_varchar_dev(const Launch& L, uint32_t* zeroed) {
     RJ_VLAUNCH(L, "prewarm", k_vc_compact, 1, 256, reinterpret_cast<const uint8_t*>(zeroed), zeroed, zeroed, 1u, zeroed,
                zeroed, reinterpret_cast<unsigned long long*>(zeroed));

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import _oracle
+import _pagecheck
 from pyrj import capi
 from pyrj import plan as pl
 
@@ -111,6 +112,15 @@ def random_plan(seed, keyable=KEYABLE, key_p=(0.6, 0.25, 0.15)):
     return p
 
 
+def check(got, want):
+    """row count, column types, every result column by the strict reader (tests/_pagecheck.py, which must
+    decode what pyrj.pages decodes), and the sorted row multiset"""
+    assert got.num_rows == want.num_rows
+    assert [c.type for c in got.columns] == [c.type for c in want.columns]
+    assert _pagecheck.same_as(_pagecheck.check_table(got), pl.decode_table(got))
+    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+
+
 # RJ_FUZZ_SEEDS="first:count" widens the sweep for soak runs (default: seeds 0..199)
 _FIRST, _COUNT = (int(x) for x in os.environ.get("RJ_FUZZ_SEEDS", "0:200").split(":"))
 
@@ -122,9 +132,7 @@ def test_random_plan(ctx, seed):
     if want.num_rows > 400_000:
         pytest.skip("result too large to sort in a unit test")
     got = capi.execute(p, ctx)
-    assert got.num_rows == want.num_rows
-    assert [c.type for c in got.columns] == [c.type for c in want.columns]
-    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+    check(got, want)
 
 
 # The same random plans under forced radix plans: small inputs never reach the multi-pass
@@ -144,8 +152,7 @@ def test_random_plan_forced_radix(seed, bits):
         got = capi.execute(p, c)
     finally:
         c.destroy()
-    assert got.num_rows == want.num_rows
-    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+    check(got, want)
 
 
 # ... and with the XCD-aware output placement of the big passes forced on (it normally starts at
@@ -170,8 +177,7 @@ def test_random_plan_forced_radix_xcd_placement(seed, bits):
         got = capi.execute(p, c)
     finally:
         c.destroy()
-    assert got.num_rows == want.num_rows
-    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+    check(got, want)
 
 
 # Payload columns travel with the key when they fit the carry words (CARRY_WIDE, the default since
@@ -193,8 +199,7 @@ def test_random_plan_row_index_carries(seed, bits):
         got = capi.execute(p, c)
     finally:
         c.destroy()
-    assert got.num_rows == want.num_rows
-    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+    check(got, want)
 
 
 # VARCHAR join keys (reference hash_join_omp<std::string>) in the mix: the same generator with
@@ -208,9 +213,7 @@ def test_random_plan_with_varchar_keys(ctx, seed):
     if want.num_rows > 400_000:
         pytest.skip("result too large to sort in a unit test")
     got = capi.execute(p, ctx)
-    assert got.num_rows == want.num_rows
-    assert [c.type for c in got.columns] == [c.type for c in want.columns]
-    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+    check(got, want)
 
 
 @pytest.mark.parametrize("seed", range(50_000, 50_020))
@@ -224,5 +227,4 @@ def test_random_plan_with_varchar_keys_forced_radix(seed):
         got = capi.execute(p, c)
     finally:
         c.destroy()
-    assert got.num_rows == want.num_rows
-    assert pl.canonical_rows(got) == pl.canonical_rows(want)
+    check(got, want)

@@ -18,6 +18,7 @@ import os
 import pytest
 
 import _aggref
+import _pagecheck
 import _plangen
 import test_gpu_kernel_matrix as km
 from pyrj import capi
@@ -61,6 +62,8 @@ def same(got, seed, size="small", what=""):
     want = case(seed, size)[1]
     assert got.num_rows == want.num_rows, (seed, what, got.num_rows, want.num_rows)
     assert [c.type for c in got.columns] == [c.type for c in want.columns], (seed, what)
+    # every result column by the strict reader (tests/_pagecheck.py), which must decode what pyrj.pages decodes
+    assert _pagecheck.same_as(_pagecheck.check_table(got), pl.decode_table(got)), (seed, what)
     if want.num_rows <= 50_000 or any(c.type == pl.VARCHAR for c in want.columns):
         assert pl.canonical_rows(got) == want_rows(seed, size), (seed, what)
     else:

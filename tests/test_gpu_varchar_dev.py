@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import _oracle
+import _pagecheck
 from pyrj import capi, job
 from pyrj import pages as pg
 from pyrj import plan as pl
@@ -62,6 +63,9 @@ def check(ctx, plan):
     assert got.num_rows == want.num_rows
     assert [c.type for c in got.columns] == [c.type for c in want.columns]
     assert pl.sorted_rows(got) == pl.sorted_rows(want)
+    # the device encoder's layout differs from the oracle's, but it is held to the page format: every
+    # column by the strict reader, which must decode what pyrj.pages decodes
+    assert _pagecheck.same_as(_pagecheck.check_table(got), pl.decode_table(got))
     return got
 
 
