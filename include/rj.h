@@ -489,6 +489,10 @@ int  rj_debug_launch_log(rj_context* ctx, int on);
  * handle without a dynamic symbol: "+0x<offset from the library's base>"), NUL-
  * terminated and truncated to cap bytes; *need = bytes the whole text takes.     */
 int  rj_debug_launch_read(rj_context* ctx, char* buf, uint64_t cap, uint64_t* need);
+/* Block cache (tests): out[0] = bytes in use, out[1] = bytes cached, out[2] = fills done
+ * and out[3] = bytes filled under RJ_DEBUG_POISON (both 0 when the knob is off).  A
+ * group context reports the sum over its devices.                                   */
+int  rj_debug_pool(rj_context* ctx, uint64_t out[4]);
 
 /* Device properties the host side reports next to its numbers. */
 typedef struct rj_device_info {

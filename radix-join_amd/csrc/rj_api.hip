@@ -73,6 +73,7 @@ int rj_context_create(rj_context** out, const rj_config* cfg) {
             c->prof.stream = c->stream;
             c->radix_bits_override = cfg ? cfg->radix_bits : 0;
             c->tune.from_env();
+            c->pool.set_poison(c.get(), c->tune.debug_poison);
             if (!c->radix_bits_override && c->tune.radix_bits > 0) c->radix_bits_override = c->tune.radix_bits;
             return c;
         };
@@ -203,6 +204,19 @@ int rj_debug_launch_read(rj_context* ctx, char* buf, uint64_t cap, uint64_t* nee
             buf[n] = 0;
         }
     });
+}
+
+int rj_debug_pool(rj_context* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return RJ_ERR_ARG;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    for (int l = 0; l < ctx->n_lanes(); ++l) {  // a group context: every device's block cache
+        const DevPool& p = ctx->lane(l)->pool;
+        out[0] += p.bytes_in_use();
+        out[1] += p.bytes_cached();
+        out[2] += p.n_fills();
+        out[3] += p.bytes_filled();
+    }
+    return RJ_OK;
 }
 
 uint64_t rj_table_num_rows(const rj_table* t) { return t ? t->num_rows : 0; }

@@ -42,6 +42,8 @@ void Tuning::from_env() {
     bringup_timeout_ms = env_int("RJ_BRINGUP_TIMEOUT_MS", bringup_timeout_ms);
     debug_shard_fail = env_int("RJ_DEBUG_SHARD_FAIL", debug_shard_fail);
     debug_shard_fail_rank = env_int("RJ_DEBUG_SHARD_FAIL_RANK", debug_shard_fail_rank);
+    if (const char* v = getenv("RJ_DEBUG_POISON"))  // decimal or 0x...: 0x15A reads better than 346
+        debug_poison = (int)strtol(v, nullptr, 0) & 0x1ff;
 }
 
 // ---------------------------------------------------------------- DevPool --
@@ -61,6 +63,10 @@ void* DevPool::alloc(size_t bytes) {
         if (best < 0 || b.size < blocks_[best].size) best = (int)i;
     }
     if (best >= 0) {
+        if (poison_) {  // (before the block changes hands: a failed fill leaves the cache as it was)
+            hipError_t e = fill(blocks_[best].p, blocks_[best].size);
+            if (e != hipSuccess) throw_fmt(RJ_ERR_DEVICE, "RJ_DEBUG_POISON: fill on alloc failed: %s", hipGetErrorString(e));
+        }
         blocks_[best].free = false;
         in_use_ += blocks_[best].size;
         cached_ -= blocks_[best].size;
@@ -81,15 +87,44 @@ void* DevPool::alloc(size_t bytes) {
     }
     ++n_malloc;
     malloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (poison_) {
+        hipError_t f = fill(p, need);
+        if (f != hipSuccess) {
+            (void)hipFree(p);
+            throw_fmt(RJ_ERR_DEVICE, "RJ_DEBUG_POISON: fill on alloc failed: %s", hipGetErrorString(f));
+        }
+    }
     blocks_.push_back({p, need, false});
     in_use_ += need;
     return p;
+}
+
+// Debug mode only.  The fill starts when every stream of the context is idle and is complete when
+// this returns, with the context's device current for its duration; it never throws (Buf::~Buf).
+hipError_t DevPool::fill(void* p, size_t bytes) {
+    Context* c = owner_;
+    int      prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    hipError_t e = prev == c->device ? hipSuccess : hipSetDevice(c->device);
+    for (hipStream_t s : {c->stream, c->aux, c->copy_stream})
+        if (e == hipSuccess && s) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemsetAsync(p, poison_ & 0xff, bytes, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) {
+        n_fill_.fetch_add(1, std::memory_order_relaxed);
+        fill_bytes_.fetch_add(bytes, std::memory_order_relaxed);
+    } else {
+        (void)hipGetLastError();
+    }
+    if (prev >= 0 && prev != c->device) (void)hipSetDevice(prev);
+    return e;
 }
 
 void DevPool::release(void* p) {
     if (!p) return;
     for (Block& b : blocks_)
         if (b.p == p && !b.free) {
+            if (poison_ & 0x100) (void)fill(b.p, b.size);  // (a failed fill is dropped: release never throws)
             b.free = true;
             in_use_ -= b.size;
             cached_ += b.size;
@@ -223,12 +258,16 @@ void* Context::staging(size_t bytes) {
         pinned_bytes = 0;
         RJ_HIP(hipHostMalloc(&pinned, bytes, hipHostMallocDefault));
         pinned_bytes = bytes;
+        if (pool.poison()) memset(pinned, pool.poison() & 0xff, bytes);
     }
     return pinned;
 }
 
 void* Context::small_pinned() {
-    if (!pinned_small) RJ_HIP(hipHostMalloc(&pinned_small, SMALL_PINNED, hipHostMallocDefault));
+    if (!pinned_small) {
+        RJ_HIP(hipHostMalloc(&pinned_small, SMALL_PINNED, hipHostMallocDefault));
+        if (pool.poison()) memset(pinned_small, pool.poison() & 0xff, SMALL_PINNED);
+    }
     return pinned_small;
 }
 
@@ -285,6 +324,7 @@ void* Context::upload_staging(size_t bytes) {
         pinned_up_bytes = 0;
         RJ_HIP(hipHostMalloc(&pinned_up, bytes, hipHostMallocDefault));
         pinned_up_bytes = bytes;
+        if (pool.poison()) memset(pinned_up, pool.poison() & 0xff, bytes);
     }
     return pinned_up;
 }
@@ -295,6 +335,7 @@ Context::~Context() {
     for (Context* p : peers) delete static_cast<rj_context*>(p);
     peers.clear();
     (void)hipSetDevice(device);
+    pool.set_poison(this, 0);  // the streams go now: nothing released from here on is filled
     if (stream) (void)hipStreamSynchronize(stream);
     if (aux) {
         (void)hipStreamSynchronize(aux);

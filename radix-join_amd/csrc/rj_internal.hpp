@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +21,8 @@
 #include "rj_kernels.hpp"
 
 namespace rj {
+
+struct Context;
 
 struct Error : std::runtime_error {
     int code;
@@ -52,6 +55,13 @@ class DevPool {
    public:
     void* alloc(size_t bytes);
     void  release(void* p);
+    // RJ_DEBUG_POISON (Tuning::debug_poison): every block is filled over its whole rounded size
+    // when it is handed out, and with bit 8 again when it comes back.  0 = off: one integer test
+    // per alloc and per release.
+    void     set_poison(Context* owner, int mode) { owner_ = owner, poison_ = mode; }
+    int      poison() const { return poison_; }
+    uint64_t n_fills() const { return n_fill_.load(std::memory_order_relaxed); }
+    uint64_t bytes_filled() const { return fill_bytes_.load(std::memory_order_relaxed); }
     void  trim();  // hipFree everything that is not in use
     ~DevPool();
     size_t bytes_in_use() const { return in_use_; }
@@ -68,9 +78,11 @@ class DevPool {
     };
     std::vector<Block> blocks_;
     size_t             in_use_ = 0, cached_ = 0;
+    Context*           owner_ = nullptr;
+    int                poison_ = 0;
+    std::atomic<uint64_t> n_fill_{0}, fill_bytes_{0};
+    hipError_t         fill(void* p, size_t bytes);  // debug mode only: synchronises the context
 };
-
-struct Context;
 
 // RAII device buffer drawn from the context's cache.
 struct Buf {
@@ -224,6 +236,8 @@ struct Tuning {
     // sharded join — 1: while preparing, 2: in stage A, 3: allocating its receive buffers, 5: in a scan below it, 6: building / probing what arrived; 4: it does not
     // fail but stalls (its probe-side slices are not ready for 7 s: the exchange's bounded wait expires)
     int debug_shard_fail = 0, debug_shard_fail_rank = 0;
+    int debug_poison = 0;  // RJ_DEBUG_POISON (tests): the block cache fills what it hands out — bits 0-7 the byte,
+                           // bit 8: and again what it takes back; pinned staging is filled once (DESIGN.md "Block cache")
     void from_env();
 };
 

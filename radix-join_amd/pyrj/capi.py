@@ -141,6 +141,7 @@ EXPORTS = [
     "rj_profile_reset",
     "rj_debug_launch_log",
     "rj_debug_launch_read",
+    "rj_debug_pool",
     "rj_device_query",
 ]
 
@@ -262,6 +263,8 @@ def load():
     L.rj_debug_launch_log.restype = C.c_int
     L.rj_debug_launch_read.argtypes = [vp, C.c_char_p, u64, C.POINTER(u64)]
     L.rj_debug_launch_read.restype = C.c_int
+    L.rj_debug_pool.argtypes = [vp, C.POINTER(u64)]
+    L.rj_debug_pool.restype = C.c_int
     L.rj_device_query.argtypes = [vp, C.POINTER(rj_device_info)]
     L.rj_device_query.restype = C.c_int
     _LIB = L
@@ -521,6 +524,13 @@ class Context:
 
     def profile_reset(self):
         self.L.rj_profile_reset(self.h)
+
+    # -- block cache (tests: leaks, and what RJ_DEBUG_POISON did)
+    def pool(self) -> dict:
+        """Bytes in use / cached in the HBM block cache, fills done and bytes filled (RJ_DEBUG_POISON)."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.L.rj_debug_pool(self.h, out))
+        return {"in_use": out[0], "cached": out[1], "fills": out[2], "filled_bytes": out[3]}
 
     # -- launch log (tests: which kernel template instantiations ran)
     def launch_log(self, on=True):
