@@ -173,7 +173,39 @@ typedef enum rj_status {
  *   as always); the node may be the root.  rj_execute_sharded refuses plans that hold the kind
  *   (RJ_ERR_UNSUPPORTED), rj_plan_shardable reports it, and rj_execute on a multi-device context
  *   runs such a plan on its first device.  A library older than this kind rejects it with
- *   RJ_ERR_ARG ("bad node kind").                                                              */
+ *   RJ_ERR_ARG ("bad node kind").
+ *
+ * Selection (WHERE / HAVING / projection over any relation; no reference counterpart).
+ * RJ_NODE_SELECT has ONE child, `left`; `build_left`, `base_table_id` and `left_attr` are ignored.
+ *   out_idx / out_type work as a scan's do, with the child's output columns in place of the base
+ *   table's: entries index the child's outputs, in any order, repeated or not; a declared type that
+ *   differs from the child column's is RJ_ERR_ARG; a VARCHAR child column passes through as row ids,
+ *   as through a join.
+ *   The predicate is a postfix program of rj_filter_op (below, at rj_table_from_csv).  rj_node cannot
+ *   grow, so two of its integer fields carry the program: `right` = the number of ops, `right_attr` =
+ *   (uint64_t)(uintptr_t) of a `const rj_filter_op*` that stays valid during the call — read them with
+ *   RJ_SELECT_N_OPS(node) / RJ_SELECT_OPS(node).  rj_filter_op::column indexes the CHILD's outputs; a
+ *   predicate column need not be an output column.  right == 0 keeps every row (a pure projection;
+ *   the pointer may then be NULL).
+ *   Semantics: exactly those of rj_table_from_csv's filter (see there: a comparison is false on NULL,
+ *   RJ_F_NOT flips the bit, an INT32 column compares with (int32_t)ivalue, an FP64 column IEEE-wise
+ *   with the double whose bits are ivalue), with RJ_F_IS_NULL / RJ_F_IS_NOT_NULL on INT32, INT64 and
+ *   FP64 columns, plus the column comparisons RJ_F_COL_EQ .. RJ_F_COL_GEQ, which only this node takes.
+ *   Result: the multiset of child rows for which the program leaves 1, in no particular order; a
+ *   column's nullability is the child column's.  An empty child, or a predicate that keeps nothing,
+ *   gives 0 rows with the declared column types and zero pages.
+ *   RJ_ERR_UNSUPPORTED: any leaf on a VARCHAR column (comparison, column comparison, LIKE, IS NULL:
+ *   a VARCHAR value travels as a row id, its pages are not read here); more than 64 ops.
+ *   RJ_ERR_ARG: RJ_F_HOST_BITMAP (the rows of an intermediate relation have no numbering a caller
+ *   could see); a column out of range; a column comparison of two different types; LIKE on a
+ *   fixed-width column; an unknown opcode; a malformed program (the stack depth is at least 1 after
+ *   every op, at most 60 — which the 64-op limit keeps below 33 anyway —, and exactly 1 at the end); right != 0 with a NULL pointer.  The node is
+ *   checked before its child's rows are looked at: an empty child does not hide an error.
+ *   The node's result is an ordinary relation: the child may be any node, a parent of any kind may use
+ *   every column of it, as a key too, and the node may be the root.  rj_execute_sharded refuses plans
+ *   that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable reports it, and rj_execute on a
+ *   multi-device context runs such a plan on its first device.  A library older than this kind
+ *   rejects it with RJ_ERR_ARG ("bad node kind").                                              */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
     RJ_NODE_JOIN = 1,
@@ -181,7 +213,8 @@ typedef enum rj_node_kind {
     RJ_NODE_ANTI = 3, /* preserved rows without one                          */
     RJ_NODE_OUTER = 4, /* inner join + unmatched preserved rows, NULL-padded */
     RJ_NODE_FULL = 5,  /* inner join + unmatched rows of BOTH sides, padded  */
-    RJ_NODE_AGG = 6    /* GROUP BY left_attr of the one child `left`         */
+    RJ_NODE_AGG = 6,   /* GROUP BY left_attr of the one child `left`         */
+    RJ_NODE_SELECT = 7 /* rows of the one child `left` that pass a predicate */
 } rj_node_kind;
 
 /* Aggregate functions of RJ_NODE_AGG and the encoding of its out_idx values. */
@@ -207,6 +240,10 @@ typedef struct rj_node {
     const uint64_t* out_idx;       /* [n_out] */
     const int32_t*  out_type;      /* [n_out] rj_dtype */
 } rj_node;
+
+/* The predicate of an RJ_NODE_SELECT node (`node`: a const rj_node*), carried in integer fields. */
+#define RJ_SELECT_N_OPS(node) ((node)->right)
+#define RJ_SELECT_OPS(node) ((const rj_filter_op*)(uintptr_t)(node)->right_attr)
 
 /* One Column (include/plan.h:60-100): `pages[i]` points at an 8192-byte Page. */
 typedef struct rj_column {
@@ -340,17 +377,23 @@ typedef enum rj_filter_opcode {
     RJ_F_IS_NULL = 6, RJ_F_IS_NOT_NULL = 7,                   /* any column                                   */
     RJ_F_HOST_BITMAP = 8,
     RJ_F_AND = 9, RJ_F_OR = 10, RJ_F_NOT = 11,
-    RJ_F_LIKE = 12, RJ_F_NOT_LIKE = 13  /* VARCHAR column LIKE / NOT LIKE the ivalue bytes at `bytes` ('%' any run,
+    RJ_F_LIKE = 12, RJ_F_NOT_LIKE = 13, /* VARCHAR column LIKE / NOT LIKE the ivalue bytes at `bytes` ('%' any run,
                                            '_' any one character) — what the reference asks RE2 for
                                            (statement.h:118-161: '%' -> ".*", '_' -> ".", full match, UTF-8, '.'
                                            never matches a newline); false on NULL, both of them
                                            (inner_column.h:518-562); at most 63 pattern characters         */
+    RJ_F_COL_EQ = 14, RJ_F_COL_NEQ = 15, RJ_F_COL_LT = 16, RJ_F_COL_GT = 17, RJ_F_COL_LEQ = 18, RJ_F_COL_GEQ = 19
+                                        /* RJ_NODE_SELECT only (rj_table_from_csv: "bad filter opcode"): column <op>
+                                           column.  `column` is the left operand, `ivalue` the right operand's column
+                                           index; both INT32, both INT64 or both FP64; false if either side is NULL;
+                                           FP64 compares IEEE-wise                                                  */
 } rj_filter_opcode;
 
 typedef struct rj_filter_op {
     int32_t        op;          /* rj_filter_opcode */
     int32_t        column;      /* leaves */
-    int64_t        ivalue;      /* comparison leaves: the literal, or the length of a string literal */
+    int64_t        ivalue;      /* comparison leaves: the literal, or the length of a string literal;
+                                   RJ_F_COL_*: the right operand's column index                      */
     const uint8_t* bytes;       /* RJ_F_HOST_BITMAP: (rows + 7) / 8 bytes, rows = records of the CSV;
                                    string comparison: the literal's bytes                            */
 } rj_filter_op;
@@ -416,8 +459,8 @@ int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* ta
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join or an aggregation is not shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI /
- * RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG).                                                 */
+ * join, an aggregation or a selection is not shardable; the reason names the kind (RJ_NODE_SEMI /
+ * RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG / RJ_NODE_SELECT).                  */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

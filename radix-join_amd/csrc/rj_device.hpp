@@ -396,4 +396,38 @@ struct AggParams {
     uint32_t*       m_overflow;   // set when a key found no entry: the host repeats the node with a larger table
 };
 
+// ---- Selection (RJ_NODE_SELECT): a postfix predicate program over a relation's columns; the row ids
+// of the rows it keeps are compacted into one array (k_select), which the output columns are then
+// gathered through.  A workgroup owns tiles of SEL_TILE consecutive rows: wave w of it evaluates rows
+// [w * SEL_TILE / 4, (w + 1) * SEL_TILE / 4) of the tile, 64 consecutive ones per item.
+constexpr int SEL_THREADS = 256;
+constexpr int SEL_TILE = 8192;                        // rows per output reservation (one global atomic)
+constexpr int SEL_ITEMS = SEL_TILE / SEL_THREADS;     // rows per thread per tile
+constexpr int SEL_BATCH = 4;                          // ... of which a thread evaluates this many together
+constexpr int SEL_MAX_OPS = 64;
+static_assert(SEL_TILE % 256 == 0 && SEL_TILE % SEL_THREADS == 0 && SEL_ITEMS <= 32 && SEL_ITEMS % SEL_BATCH == 0,
+              "whole rows of threads; one keep bit per item; whole batches");
+
+enum SelKind : int32_t {
+    SEL_LIT = 0,      // column a <cmp> literal
+    SEL_COL = 1,      // column a <cmp> column b
+    SEL_IS_NULL = 2,
+    SEL_NOT_NULL = 3,
+    SEL_AND = 4,
+    SEL_OR = 5,
+    SEL_NOT = 6
+};
+struct SelectOp {
+    int32_t kind;    // SelKind
+    int32_t cmp;     // 0..5 = EQ, NEQ, LT, GT, LEQ, GEQ (the order of rj_filter_opcode)
+    int32_t f64;     // the operands are doubles (compared IEEE-wise), else integers of a.width bytes
+    int32_t pad;
+    int64_t literal; // SEL_LIT: the literal (an INT32 column's already cut to 32 bits and sign-extended; FP64: the bits)
+    ColRef  a, b;
+};
+// One small device buffer per node; every thread reads ops[k] at the same k, so the loads are scalar.
+struct SelectProg {
+    SelectOp ops[SEL_MAX_OPS];
+};
+
 }  // namespace rj

@@ -340,6 +340,10 @@ class Exec {
             Rel child = node(n.left, nullptr, depth + 1);
             return agg(child, n, root_res);
         }
+        if (n.kind == RJ_NODE_SELECT) {
+            Rel child = node(n.left, nullptr, depth + 1);
+            return select(child, n, root_res);
+        }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
         Rel             r = node(n.right, nullptr, depth + 1);
@@ -1634,25 +1638,205 @@ class Exec {
         return out;
     }
 
-    // a relation of dense columns as a root result: Page images encoded on the device
+    // ---------------------------------------------------------------- selection
+    // RJ_NODE_SELECT (semantics in rj.h): WHERE / HAVING / projection over the one child.  The program
+    // is checked and translated into SelectProg (one ColRef per operand), k_select compacts the ids of
+    // the rows it keeps, and every distinct output column is gathered through that list — at the root
+    // straight into Page images.  One host sync: the row count.
+    //
+    // The checks of a program, in the order of the ops (the depth rules are table_from_csv's).
+    static void select_program(const Rel& child, const rj_filter_op* ops, uint64_t n_ops, SelectProg& prog) {
+        const size_t cw = child.cols.size();
+        auto column = [&](int64_t c, const char* what) -> const DCol& {
+            if (c < 0 || (uint64_t)c >= cw) throw_fmt(RJ_ERR_ARG, "select: %s out of range", what);
+            const DCol& d = child.cols[(size_t)c];
+            if (d.type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "select: predicate on a VARCHAR column (child column %lld): a VARCHAR value travels "
+                                              "as a row id, its pages are not read here", (long long)c);
+            return d;
+        };
+        int depth = 0;
+        for (uint64_t k = 0; k < n_ops; ++k) {
+            const rj_filter_op& o = ops[k];
+            SelectOp&           d = prog.ops[k];
+            d = SelectOp{};
+            if (o.op == RJ_F_AND || o.op == RJ_F_OR) {
+                d.kind = o.op == RJ_F_AND ? SEL_AND : SEL_OR;
+                depth -= 1;
+            } else if (o.op == RJ_F_NOT) {
+                d.kind = SEL_NOT;
+            } else if (o.op == RJ_F_HOST_BITMAP) {
+                throw_fmt(RJ_ERR_ARG, "select: RJ_F_HOST_BITMAP leaf (the rows of an intermediate relation have no numbering "
+                                      "a caller could see)");
+            } else if (o.op == RJ_F_LIKE || o.op == RJ_F_NOT_LIKE) {
+                (void)column(o.column, "predicate column");
+                throw_fmt(RJ_ERR_ARG, "select: LIKE wants a VARCHAR column");
+            } else if ((o.op >= RJ_F_EQ && o.op <= RJ_F_IS_NOT_NULL) || (o.op >= RJ_F_COL_EQ && o.op <= RJ_F_COL_GEQ)) {
+                const DCol& a = column(o.column, "predicate column");
+                d.a = a.ref();
+                d.f64 = a.type == RJ_FP64;
+                if (o.op == RJ_F_IS_NULL || o.op == RJ_F_IS_NOT_NULL) {
+                    d.kind = o.op == RJ_F_IS_NULL ? SEL_IS_NULL : SEL_NOT_NULL;
+                } else if (o.op <= RJ_F_GEQ) {
+                    d.kind = SEL_LIT;
+                    d.cmp = o.op - RJ_F_EQ;
+                    d.literal = a.type == RJ_INT32 ? (int64_t)(int32_t)o.ivalue : o.ivalue;
+                } else {
+                    const DCol& b = column(o.ivalue, "right operand column");
+                    if (a.type != b.type)
+                        throw_fmt(RJ_ERR_ARG, "select: column comparison of different types (child columns %d and %lld)", o.column,
+                                  (long long)o.ivalue);
+                    d.kind = SEL_COL;
+                    d.cmp = o.op - RJ_F_COL_EQ;
+                    d.b = b.ref();
+                }
+                depth += 1;
+            } else {
+                throw_fmt(RJ_ERR_ARG, "select: bad filter opcode %d", o.op);
+            }
+            if (depth < 1 || depth > 60) throw_fmt(RJ_ERR_ARG, "select: malformed filter program");
+        }
+        if (n_ops && depth != 1) throw_fmt(RJ_ERR_ARG, "select: malformed filter program");
+    }
+
+    Rel select(Rel& child, const rj_node& n, Result* root_res) {
+        const size_t cw = child.cols.size();
+        JoinSpec     js;  // (the declared types, for empty_rel)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            if (n.out_idx[k] >= cw) throw_fmt(RJ_ERR_ARG, "select: output attr out of range");
+            if (child.cols[n.out_idx[k]].type != n.out_type[k])
+                throw_fmt(RJ_ERR_ARG, "select: declared type differs from the child column's type");
+            js.out_type.push_back(n.out_type[k]);
+        }
+        const uint64_t      n_ops = RJ_SELECT_N_OPS(&n);
+        const rj_filter_op* ops = RJ_SELECT_OPS(&n);
+        if (n_ops > (uint64_t)SEL_MAX_OPS) throw_fmt(RJ_ERR_UNSUPPORTED, "select: filter longer than %d operations", SEL_MAX_OPS);
+        if (n_ops && !ops) throw_fmt(RJ_ERR_ARG, "select: %llu filter operations but a NULL program pointer", (unsigned long long)n_ops);
+        std::unique_ptr<SelectProg> prog(new SelectProg());
+        select_program(child, ops, n_ops, *prog);
+        if (child.n == 0) return empty_rel(js, root_res);
+        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+
+        // ---- the rows that pass: ids[0 .. nrows); no program = every row, and no list at all
+        uint64_t nrows = child.n;
+        BufP     ids;
+        if (n_ops) {
+            BufP dprog = ctx->buf(sizeof(SelectProg));
+            ids = ctx->buf(child.n * 4);
+            BufP               counters = zeroed_counters();  // [0..7] the cursor
+            const uint64_t     tiles = (child.n + SEL_TILE - 1) / SEL_TILE;
+            unsigned long long h = 0;
+            try {
+                RJ_HIP(hipMemcpyAsync(dprog->p, prog.get(), sizeof(SelectProg), hipMemcpyHostToDevice, ctx->stream));
+                launch_select(L, dprog->as<SelectProg>(), (uint32_t)n_ops, (uint32_t)child.n, ids->as<uint32_t>(),
+                              counters->as<unsigned long long>(),
+                              (uint32_t)std::min<uint64_t>(tiles, (uint64_t)ctx->compute_units() * 8));
+                RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
+                ctx->sync();
+            } catch (...) {
+                // `prog` and `h` are the ends of copies that may still be queued: they outlive them
+                (void)hipStreamSynchronize(ctx->stream);
+                throw;
+            }
+            nrows = h;
+            if (nrows > child.n) throw_fmt(RJ_ERR_DEVICE, "select kept %llu rows out of %llu", (unsigned long long)nrows,
+                                           (unsigned long long)child.n);
+            if (nrows == 0) return empty_rel(js, root_res);
+            if (nrows < child.n / 2) {  // (as the aggregation's arrays: nobody holds on to the bound's memory)
+                BufP small = ctx->buf(nrows * 4);
+                RJ_HIP(hipMemcpyAsync(small->p, ids->p, nrows * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                ids = small;
+            }
+        }
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] select rows=%llu ops=%llu kept=%llu\n", (unsigned long long)child.n, (unsigned long long)n_ops,
+                    (unsigned long long)nrows);
+
+        // ---- the output columns; a child column named several times is materialised once
+        const bool               is_root = root_res != nullptr;
+        const uint32_t*          idx = ids ? ids->as<uint32_t>() : nullptr;
+        std::map<uint64_t, DCol> made;
+        std::map<uint64_t, ResultColumn> made_rc;
+        Rel out;
+        out.n = nrows;
+        if (is_root) root_res->num_rows = nrows;
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint64_t c = n.out_idx[k];
+            const DCol&    src = child.cols[c];
+            if (!made.count(c)) {
+                DCol d = src;  // (type, width, VARCHAR provenance; without a program the column itself)
+                if (idx && src.kind == COL_IOTA) {
+                    d.kind = COL_DENSE;  // row ids of the base table ARE the list
+                    d.hold = ids;
+                    d.ptr = ids->as<uint8_t>();
+                    d.tcol = nullptr;
+                } else if (idx) {
+                    // a root column without NULLs goes straight into its Page images
+                    const bool to_pages = is_root && src.type != RJ_VARCHAR && src.valid == nullptr;
+                    const int  mode = to_pages ? (src.width == 4 ? ST_PAGED32 : ST_PAGED64) : (src.width == 4 ? ST_DENSE32 : ST_DENSE64);
+                    d.kind = to_pages ? COL_PAGED : COL_DENSE;
+                    d.tcol = nullptr;
+                    d.hold = ctx->buf(stream_bytes(mode, nrows));
+                    d.ptr = d.hold->as<uint8_t>();
+                    d.hold_valid = src.valid ? ctx->buf(nrows) : BufP();
+                    d.valid = d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr;
+                    launch_gather(L, src.ref(), idx, nrows, OutStream{d.hold->as<uint8_t>(), mode, 0},
+                                  d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
+                    if (to_pages) launch_finish_pages(L, d.hold->as<uint8_t>(), nrows, src.width);
+                }
+                made[c] = d;
+            }
+            const DCol& d = made.at(c);
+            if (!is_root) {
+                out.cols.push_back(d);
+                continue;
+            }
+            if (!made_rc.count(c)) {
+                ResultColumn rc;
+                if (d.type == RJ_VARCHAR) {
+                    rc.type = d.type;
+                    BufP rowids = d.hold;
+                    if (d.kind == COL_IOTA) {  // (a projection only: every row of the base table, in order)
+                        rowids = ctx->buf(nrows * 4);
+                        launch_gather(L, d.ref(), nullptr, nrows, OutStream{rowids->as<uint8_t>(), ST_DENSE32, 0}, nullptr);
+                    }
+                    varchar_root(rowids ? rowids->as<uint32_t>() : reinterpret_cast<const uint32_t*>(d.ptr), nrows, d, rc);
+                } else if (idx && d.kind == COL_PAGED) {  // gathered into Page images above
+                    rc.type = d.type;
+                    rc.dev_pages = d.hold;
+                    rc.n_pages = pages_for(nrows, d.width);
+                } else {
+                    rc = col_to_result(d, nrows);
+                }
+                made_rc[c] = std::move(rc);
+            }
+            root_res->cols.push_back(made_rc.at(c));
+        }
+        return out;
+    }
+
+    // a fixed-width column (paged, or dense with or without validity) as a root result column: Page
+    // images encoded on the device
+    ResultColumn col_to_result(const DCol& d, uint64_t rows) {
+        ResultColumn rc;
+        rc.type = d.type;
+        if (rows) {
+            rc.n_pages = pages_for(rows, d.width);
+            rc.dev_pages = ctx->buf(rc.n_pages * PAGE_BYTES);
+            if (d.valid) {
+                launch_encode_nullable(L, d.ptr, d.valid, rows, d.width, rc.dev_pages->as<uint8_t>());
+            } else {
+                launch_gather(L, d.ref(), nullptr, rows,
+                              OutStream{rc.dev_pages->as<uint8_t>(), d.width == 4 ? ST_PAGED32 : ST_PAGED64, 0}, nullptr);
+                launch_finish_pages(L, rc.dev_pages->as<uint8_t>(), rows, d.width);
+            }
+        }
+        return rc;
+    }
+    // a relation of dense columns as a root result
     void rel_to_result(const Rel& r, Result& res) {
         res.num_rows = r.n;
-        for (const DCol& d : r.cols) {
-            ResultColumn rc;
-            rc.type = d.type;
-            if (r.n) {
-                rc.n_pages = pages_for(r.n, d.width);
-                rc.dev_pages = ctx->buf(rc.n_pages * PAGE_BYTES);
-                if (d.valid) {
-                    launch_encode_nullable(L, d.ptr, d.valid, r.n, d.width, rc.dev_pages->as<uint8_t>());
-                } else {
-                    launch_gather(L, d.ref(), nullptr, r.n,
-                                  OutStream{rc.dev_pages->as<uint8_t>(), d.width == 4 ? ST_PAGED32 : ST_PAGED64, 0}, nullptr);
-                    launch_finish_pages(L, rc.dev_pages->as<uint8_t>(), r.n, d.width);
-                }
-            }
-            res.cols.push_back(std::move(rc));
-        }
+        for (const DCol& d : r.cols) res.cols.push_back(col_to_result(d, r.n));
     }
 
     static int stream_mode_of(bool is_root, int width, bool direct_output) {
@@ -2132,6 +2316,8 @@ class ShardedExec {
                                                 : "full outer (RJ_NODE_FULL)");
         if (n.kind == RJ_NODE_AGG)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: aggregation (RJ_NODE_AGG) nodes run on one device");
+        if (n.kind == RJ_NODE_SELECT)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: selection (RJ_NODE_SELECT) nodes run on one device");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -2523,6 +2709,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "an aggregation node (RJ_NODE_AGG) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_SELECT) {
+        if (why) *why = "a selection node (RJ_NODE_SELECT) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -2596,6 +2786,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_AGG)
         throw_fmt(RJ_ERR_UNSUPPORTED,
                   "rj_execute_sharded: the plan holds an aggregation (RJ_NODE_AGG) node; aggregations run on one device");
+    if (n.kind == RJ_NODE_SELECT)
+        throw_fmt(RJ_ERR_UNSUPPORTED,
+                  "rj_execute_sharded: the plan holds a selection (RJ_NODE_SELECT) node; selections run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

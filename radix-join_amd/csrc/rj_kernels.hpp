@@ -171,6 +171,13 @@ void launch_agg_emit(const Launch& L, int key_words, const AggParams& ap, uint32
 void launch_agg_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int width,
                        uint8_t* dst, uint8_t* dst_valid);
 
+// ---- selection (RJ_NODE_SELECT): the rows of [0, n_rows) for which the program (a device copy of
+// SelectProg, n_ops of its ops) leaves 1 -> their row ids in out_ids (room for n_rows), ascending
+// within every tile of SEL_TILE rows; *cursor (zeroed) += their number.  `grid` workgroups stride
+// over the tiles.
+void launch_select(const Launch& L, const SelectProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t* out_ids,
+                   unsigned long long* cursor, uint32_t grid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

@@ -61,7 +61,9 @@ class rj_filter_op(C.Structure):
 
 # rj_filter_opcode (include/rj.h): a filter is a postfix program, e.g.
 #   [("LT", 2, 1990), ("IS_NULL", 4), ("NOT",), ("AND",), ("BITMAP", np.packbits(mask, bitorder="little")), ("OR",)]
-F_OPS = {"EQ": 0, "NEQ": 1, "LT": 2, "GT": 3, "LEQ": 4, "GEQ": 5, "IS_NULL": 6, "IS_NOT_NULL": 7, "BITMAP": 8, "AND": 9, "OR": 10, "NOT": 11, "LIKE": 12, "NOT_LIKE": 13}
+F_OPS = {"EQ": 0, "NEQ": 1, "LT": 2, "GT": 3, "LEQ": 4, "GEQ": 5, "IS_NULL": 6, "IS_NOT_NULL": 7, "BITMAP": 8, "AND": 9, "OR": 10, "NOT": 11, "LIKE": 12, "NOT_LIKE": 13,
+         # RJ_NODE_SELECT only: (op, column, other column)
+         "COL_EQ": 14, "COL_NEQ": 15, "COL_LT": 16, "COL_GT": 17, "COL_LEQ": 18, "COL_GEQ": 19}
 
 
 def filter_to_c(prog):
@@ -82,6 +84,8 @@ def filter_to_c(prog):
             arr[k].column, arr[k].ivalue = int(term[1]), int(term[2])
         elif op in (6, 7):
             arr[k].column = int(term[1])
+        elif 14 <= op <= 19:
+            arr[k].column, arr[k].ivalue = int(term[1]), int(term[2])
         elif op == 8:
             bm = np.ascontiguousarray(term[1], dtype=np.uint8)
             keep.append(bm)

@@ -49,7 +49,7 @@ class JoinNode:
 
 
 # rj_node_kind (include/rj.h)
-NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG = 0, 1, 2, 3, 4, 5, 6
+NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG, NODE_SELECT = 0, 1, 2, 3, 4, 5, 6, 7
 # rj_agg_func and the RJ_AGG_OUT / RJ_AGG_FUNC / RJ_AGG_COL encoding of an aggregation's out_idx
 AGG_KEY, AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3, 4, 5
 
@@ -115,6 +115,17 @@ class AggNode:
 
 
 @dataclass
+class SelectNode:
+    """Selection (kind NODE_SELECT): the rows of the one child for which `program` leaves 1; the
+    PlanNode's output_attrs index the child's outputs as a scan's index its base table.  program is
+    a postfix filter in the tuple form capi.filter_to_c takes (capi.F_OPS), its columns the child's
+    outputs; a column comparison is (op, column, other column).  An empty program keeps every row
+    (include/rj.h)."""
+    child: int
+    program: list
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -160,6 +171,11 @@ class Plan:
         AGG_MAX; the column of AGG_COUNT_STAR is 0."""
         oa = [(agg_out(f, c), t) for f, c, t in outputs]
         self.nodes.append(PlanNode(AggNode(child, key_attr), oa))
+        return len(self.nodes) - 1
+
+    def new_select_node(self, child, program, output_attrs):
+        """WHERE / HAVING / projection: the child's rows that pass `program` (see SelectNode)."""
+        self.nodes.append(PlanNode(SelectNode(child, list(program or [])), list(output_attrs)))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -377,6 +393,15 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.kind = NODE_AGG
             nd.left = n.data.child
             nd.left_attr = n.data.key_attr
+        elif isinstance(n.data, SelectNode):
+            from . import capi  # (capi imports this module)
+
+            ops, n_ops, lits = capi.filter_to_c(n.data.program)
+            keep += [ops, lits]
+            nd.kind = NODE_SELECT
+            nd.left = n.data.child
+            nd.right = n_ops  # RJ_SELECT_N_OPS / RJ_SELECT_OPS: the struct cannot grow
+            nd.right_attr = C.addressof(ops) if n_ops else 0
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
