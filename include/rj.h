@@ -416,7 +416,13 @@ int      rj_table_copy_pages(rj_context* ctx, const rj_table* t, uint64_t col, v
  *   on the device and fetched with rj_result_copy_pages.
  * rj_execute_resident: same plan semantics, inputs already in HBM
  *   (plan->inputs ignored; tables[i] ↔ plan.inputs[i]).  With
- *   RJ_EXEC_KEEP_ON_DEVICE the fixed-width result pages stay in HBM.         */
+ *   RJ_EXEC_KEEP_ON_DEVICE the fixed-width result pages stay in HBM.
+ * A plan whose root is a scan: the pages of every result column add up to the table's
+ *   num_rows rows, whatever the input's pages add up to (rows the input's pages do not
+ *   cover are NULL, NULL rows they carry past num_rows are dropped).  A fixed-width
+ *   column of full pages without NULLs, and a VARCHAR column whose pages hold exactly
+ *   num_rows rows, come back as the input's own page images; any other column is
+ *   decoded and encoded again.  The root scan of a table without rows has no pages.  */
 typedef struct rj_result rj_result;
 
 enum { RJ_EXEC_KEEP_ON_DEVICE = 1 };

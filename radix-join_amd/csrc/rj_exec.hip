@@ -301,7 +301,11 @@ class Exec {
         return r;
     }
 
-    // A plan whose root is a Scan: the result pages are the input pages.
+    // A plan whose root is a Scan.  The result's pages have to add up to num_rows rows, which the
+    // input's pages need not: they may cover fewer rows (the rest is NULL) or carry NULL rows past the
+    // end (reference src/build_table.cpp:326-343 reads both).  So only a regular fixed-width column,
+    // and a VARCHAR column whose pages hold exactly num_rows rows, hand their input pages out; any
+    // other column is decoded and encoded again, as the reference does with every column.
     void root_scan(const rj_node& n, Result& res) {
         const Table* t = table_of(n);
         res.num_rows = t->num_rows;
@@ -313,17 +317,30 @@ class Exec {
                 throw_fmt(RJ_ERR_ARG, "scan: declared type differs from the column's type");
             ResultColumn rc;
             rc.type = tc.type;
-            rc.n_pages = tc.n_pages;
             if (tc.skipped) throw_fmt(RJ_ERR_ARG, "column was not uploaded");
-            if (tc.type == RJ_VARCHAR) {
-                rc.n_pages = tc.vc_pages.size();
-                rc.host_pages.resize(rc.n_pages * PAGE_BYTES);
-                for (uint64_t pg = 0; pg < rc.n_pages; ++pg)
-                    memcpy(rc.host_pages.data() + pg * PAGE_BYTES, tc.vc_pages[pg], PAGE_BYTES);
-            } else if (tc.n_pages) {
+            if (t->num_rows == 0) {
+                // no rows: a typed column with zero pages
+            } else if (tc.type == RJ_VARCHAR) {
+                if (vc_directory((int)n.base_table_id, (int)c, t).back() == t->num_rows) {
+                    rc.n_pages = tc.vc_pages.size();
+                    rc.host_pages.resize(rc.n_pages * PAGE_BYTES);
+                    for (uint64_t pg = 0; pg < rc.n_pages; ++pg)
+                        memcpy(rc.host_pages.data() + pg * PAGE_BYTES, tc.vc_pages[pg], PAGE_BYTES);
+                } else {  // the gather + encode of a join's root, over every row id in order
+                    DCol d = table_col(t, (int)c);
+                    d.vc_table = (int)n.base_table_id;
+                    d.vc_col = (int)c;
+                    BufP rowids = ctx->buf(t->num_rows * 4);
+                    launch_gather(L, d.ref(), nullptr, t->num_rows, OutStream{rowids->as<uint8_t>(), ST_DENSE32, 0}, nullptr);
+                    varchar_root(rowids->as<uint32_t>(), t->num_rows, d, rc);
+                }
+            } else if (tc.regular) {
+                rc.n_pages = tc.n_pages;
                 rc.dev_pages = ctx->buf(tc.n_pages * PAGE_BYTES);
                 RJ_HIP(hipMemcpyAsync(rc.dev_pages->p, tc.dev_pages, tc.n_pages * PAGE_BYTES,
                                       hipMemcpyDeviceToDevice, ctx->stream));
+            } else {  // K1, then the page writer of columns with NULLs
+                rc = col_to_result(table_col(t, (int)c), t->num_rows);
             }
             res.cols.push_back(std::move(rc));
         }
@@ -2025,6 +2042,20 @@ class Exec {
         return out;
     }
 
+    // The page directory (rows before each page) of VARCHAR column vc_col of table vc_table, built on
+    // first use; a column whose pages the reference refuses leaves no entry behind.
+    const std::vector<uint64_t>& vc_directory(int vc_table, int vc_col, const Table* t) {
+        auto key = std::make_pair(vc_table, vc_col);
+        auto it = vc_dir_.find(key);
+        if (it == vc_dir_.end()) {
+            const TableColumn&    tc = t->cols[vc_col];
+            std::vector<uint64_t> dir;
+            varchar_dir_build(tc.vc_pages.data(), tc.vc_pages.size(), t->num_rows, dir);
+            it = vc_dir_.emplace(key, std::move(dir)).first;
+        }
+        return it->second;
+    }
+
     // The VARCHAR pages of a base column + their row directory in HBM (uploaded once per table).
     struct VcDev {
         const uint8_t*  pages;
@@ -2037,19 +2068,14 @@ class Exec {
         const TableColumn& tc = t->cols[vc_col];
         if (tc.vc_pages.size() > 0xfffffff0ull || t->num_rows > 0xfffffff0ull)
             throw_fmt(RJ_ERR_UNSUPPORTED, "VARCHAR column too large for the device path");
-        auto key = std::make_pair(vc_table, vc_col);
-        auto it = vc_dir_.find(key);
-        if (it == vc_dir_.end()) {
-            it = vc_dir_.emplace(key, std::vector<uint64_t>()).first;
-            varchar_dir_build(tc.vc_pages.data(), tc.vc_pages.size(), t->num_rows, it->second);
-        }
+        const std::vector<uint64_t>& dir = vc_directory(vc_table, vc_col, t);
         const uint32_t npg = (uint32_t)tc.vc_pages.size();
         if (!tc.vc_dev) {  // (a table ingested on the device brings its pages along: rj_ingest.hip)
             tc.vc_dev = ctx->buf(std::max<uint64_t>(npg, 1) * PAGE_BYTES);
             upload_host_pages(ctx, tc.vc_pages.data(), npg, tc.vc_dev->as<uint8_t>());
         }
         if (!tc.vc_dev_dir) {
-            std::vector<uint32_t> dir32(it->second.begin(), it->second.end());
+            std::vector<uint32_t> dir32(dir.begin(), dir.end());
             tc.vc_dev_dir = ctx->buf(dir32.size() * 4);
             RJ_HIP(hipMemcpyAsync(tc.vc_dev_dir->p, dir32.data(), dir32.size() * 4, hipMemcpyHostToDevice,
                                   ctx->stream));
@@ -2131,7 +2157,6 @@ class Exec {
         const TableColumn& tc = t->cols[src.vc_col];
         const bool diag = ctx->tune.diag >= 2;
         auto       tv0 = std::chrono::steady_clock::now();
-        auto       key = std::make_pair(src.vc_table, src.vc_col);
         if (ctx->tune.varchar_dev_rows > 0 && n >= (uint64_t)ctx->tune.varchar_dev_rows &&
             tc.vc_pages.size() <= 0xfffffff0ull && t->num_rows <= 0xfffffff0ull) {
             // ---- large result: gather + encode on the device (rj_varchar_dev.hip)
@@ -2167,13 +2192,9 @@ class Exec {
         RJ_HIP(hipMemcpyAsync(ids.data(), dev_rowids, n * 4, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sync();
         auto tv1 = std::chrono::steady_clock::now();
-        auto it = vc_dir_.find(key);
-        if (it == vc_dir_.end()) {
-            it = vc_dir_.emplace(key, std::vector<uint64_t>()).first;
-            varchar_dir_build(tc.vc_pages.data(), tc.vc_pages.size(), t->num_rows, it->second);
-        }
+        const std::vector<uint64_t>& dir = vc_directory(src.vc_table, src.vc_col, t);
         auto tv2 = std::chrono::steady_clock::now();
-        varchar_gather_encode(tc.vc_pages.data(), tc.vc_pages.size(), it->second, ids.data(), n,
+        varchar_gather_encode(tc.vc_pages.data(), tc.vc_pages.size(), dir, ids.data(), n,
                               rc.host_pages, rc.n_pages);
         if (diag) {
             auto tv3 = std::chrono::steady_clock::now();

@@ -337,6 +337,7 @@ def test_short_pages_and_irregular_inputs():
     cols = table(rng, 20_000, I64, I32, groups=300, key_nulls=0, val_nulls=0)
     p = agg_plan(cols, ALL)
     # every page cut down to 600 rows: the column is no longer "regular" and goes through the page decode
+    # (every other legal layout under an aggregation: tests/test_gpu_layouts.py)
     t = p.inputs[0]
     for ci, (dt, v) in enumerate(cols):
         chunks = [pg.pack_fixed(v[i:i + 600], None, dt) for i in range(0, v.shape[0], 600)]

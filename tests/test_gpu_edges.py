@@ -61,7 +61,7 @@ def test_self_join_same_pages_twice(ctx):
 
 def test_short_irregular_pages_go_through_page_decode(ctx):
     """non-NULL columns whose pages are NOT full (a legal layout other producers may emit):
-    not addressable in place, so K1 decodes them"""
+    not addressable in place, so K1 decodes them (every other legal layout: tests/test_gpu_layouts.py)"""
     rng = np.random.default_rng(2)
     n = 30_000
     k = rng.integers(0, 9000, n).astype(np.int32)
