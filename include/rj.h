@@ -205,7 +205,44 @@ typedef enum rj_status {
  *   every column of it, as a key too, and the node may be the root.  rj_execute_sharded refuses plans
  *   that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable reports it, and rj_execute on a
  *   multi-device context runs such a plan on its first device.  A library older than this kind
- *   rejects it with RJ_ERR_ARG ("bad node kind").                                              */
+ *   rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Sort (ORDER BY ... [LIMIT n [OFFSET m]] over any relation; no reference counterpart).
+ * RJ_NODE_SORT has ONE child, `left`; `build_left` is ignored.
+ *   out_idx / out_type work exactly as RJ_NODE_SELECT's: entries index the child's outputs, in any
+ *   order, repeated or not; a declared type that differs from the child column's is RJ_ERR_ARG; a
+ *   VARCHAR child column passes through as row ids.
+ *   rj_node cannot grow, so its integer fields carry the rest — read them with the macros below:
+ *   RJ_SORT_N_KEYS(node) = `right`, RJ_SORT_KEYS(node) = `right_attr` as a `const rj_sort_key*` that
+ *   stays valid during the call, RJ_SORT_LIMIT(node) = `left_attr` (RJ_SORT_NO_LIMIT = UINT64_MAX: no
+ *   LIMIT), RJ_SORT_OFFSET(node) = `base_table_id`.  rj_sort_key::column indexes the CHILD's outputs;
+ *   a key column need not be an output column and may repeat.  rj_sort_key::flags is a set of
+ *   RJ_SORT_DESC and RJ_SORT_NULLS_FIRST; the default is ascending with NULLs last, and where NULLs go
+ *   does not depend on the direction.
+ *   Semantics: the child's rows ordered lexicographically by the keys, the first key most
+ *   significant.  INT32 / INT64 compare by value.  FP64 compares numerically by PostgreSQL's rules:
+ *   -0.0 and +0.0 are equal; every NaN (any sign, any payload) equals every other NaN and is greater
+ *   than +inf.  Only the comparison canonicalises: a value that is output keeps its own bits.
+ *   Result: rows [offset, offset + limit) of that order (offset + limit does not overflow: it
+ *   saturates); offset >= the child's rows, or limit == 0, gives 0 rows with the declared column
+ *   types and zero pages, as an empty child does.  n_keys == 0 is a plain LIMIT / OFFSET over the
+ *   child's row order.  A column's nullability is the child column's.
+ *   Ties: the sort is stable with respect to the order the child's rows have on the device.  For a
+ *   SCAN child that is the table's row order, so the result order is fully determined.  For any other
+ *   child the order within a group of equal keys is unspecified, and so is which members of a tie
+ *   group a LIMIT / OFFSET boundary keeps.
+ *   The row order of the result is promised ONLY when the node is the plan's root (for every column
+ *   type, VARCHAR and nullable columns included).  Below another node the result is an ordinary
+ *   relation, the multiset of the slice (top-k in a subquery); a non-root node with neither limit
+ *   nor offset changes nothing and, once validated, passes its child through.
+ *   RJ_ERR_ARG: a key column or output column out of range; flag bits other than the two defined
+ *   ones; n_keys != 0 with a NULL pointer; a declared-type mismatch.  RJ_ERR_UNSUPPORTED: a VARCHAR
+ *   key column (it travels as a row id); more than RJ_SORT_MAX_KEYS keys; more than 2^32 - 16 child
+ *   rows.  The node is checked before its child's rows are looked at: an empty child does not hide
+ *   an error.
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
+ *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").                 */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
     RJ_NODE_JOIN = 1,
@@ -214,7 +251,8 @@ typedef enum rj_node_kind {
     RJ_NODE_OUTER = 4, /* inner join + unmatched preserved rows, NULL-padded */
     RJ_NODE_FULL = 5,  /* inner join + unmatched rows of BOTH sides, padded  */
     RJ_NODE_AGG = 6,   /* GROUP BY left_attr of the one child `left`         */
-    RJ_NODE_SELECT = 7 /* rows of the one child `left` that pass a predicate */
+    RJ_NODE_SELECT = 7, /* rows of the one child `left` that pass a predicate */
+    RJ_NODE_SORT = 8    /* ORDER BY / LIMIT / OFFSET over the one child `left` */
 } rj_node_kind;
 
 /* Aggregate functions of RJ_NODE_AGG and the encoding of its out_idx values. */
@@ -244,6 +282,20 @@ typedef struct rj_node {
 /* The predicate of an RJ_NODE_SELECT node (`node`: a const rj_node*), carried in integer fields. */
 #define RJ_SELECT_N_OPS(node) ((node)->right)
 #define RJ_SELECT_OPS(node) ((const rj_filter_op*)(uintptr_t)(node)->right_attr)
+
+/* The keys, limit and offset of an RJ_NODE_SORT node (`node`: a const rj_node*). */
+typedef struct rj_sort_key {
+    int32_t column; /* index into the child's outputs */
+    int32_t flags;  /* RJ_SORT_DESC | RJ_SORT_NULLS_FIRST */
+} rj_sort_key;
+#define RJ_SORT_DESC 1
+#define RJ_SORT_NULLS_FIRST 2
+#define RJ_SORT_MAX_KEYS 8
+#define RJ_SORT_NO_LIMIT UINT64_MAX
+#define RJ_SORT_N_KEYS(node) ((node)->right)
+#define RJ_SORT_KEYS(node) ((const rj_sort_key*)(uintptr_t)(node)->right_attr)
+#define RJ_SORT_LIMIT(node) ((node)->left_attr)
+#define RJ_SORT_OFFSET(node) ((node)->base_table_id)
 
 /* One Column (include/plan.h:60-100): `pages[i]` points at an 8192-byte Page. */
 typedef struct rj_column {
@@ -406,6 +458,16 @@ int rj_table_from_csv(rj_context* ctx, const char* text, uint64_t n_bytes, uint6
  * tests): 0 = *bits holds the double, 1 = out of range ("parse float error"), 2 = left to
  * std::from_chars.                                                                             */
 int rj_debug_parse_fp64(const char* field, uint64_t n, uint64_t* bits);
+
+/* The order-preserving key encoding of RJ_NODE_SORT, run on the host (the kernels share the code):
+ * for a value of `type` (RJ_INT32 / RJ_INT64 / RJ_FP64; `bits` = its bits, an INT32's in the low
+ * word) under `flags` (RJ_SORT_DESC | RJ_SORT_NULLS_FIRST), row a sorts before row b exactly when
+ * (null_digit, key) of a is below that of b as a pair of unsigned numbers, and they tie when the
+ * pairs are equal.  INT32: bits ^ 2^31 (a 32-bit key); INT64: bits ^ 2^63; FP64: -0.0 becomes +0.0
+ * and every NaN one NaN above +inf, then bits ^ (sign ? ~0 : 2^63); RJ_SORT_DESC: the bitwise NOT of
+ * those bits.  null_digit: the NULL flag oriented by RJ_SORT_NULLS_FIRST; a NULL's key is 0.
+ * Needs neither a context nor a GPU.  RJ_ERR_ARG: another type, other flag bits, a NULL pointer.  */
+int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, uint64_t* key, uint32_t* null_digit);
 uint64_t rj_table_num_rows(const rj_table* t);
 uint64_t rj_table_col_pages(const rj_table* t, uint64_t col);
 int      rj_table_copy_pages(rj_context* ctx, const rj_table* t, uint64_t col, void* const* dst, uint64_t n_dst);
@@ -465,8 +527,9 @@ int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* ta
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join, an aggregation or a selection is not shardable; the reason names the kind (RJ_NODE_SEMI /
- * RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG / RJ_NODE_SELECT).                  */
+ * join, an aggregation, a selection or a sort is not shardable; the reason names the kind
+ * (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG / RJ_NODE_SELECT /
+ * RJ_NODE_SORT).                                                                                 */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

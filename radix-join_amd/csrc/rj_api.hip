@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "rj_internal.hpp"
+#include "rj_sortkey.hpp"
 #include "rj_xplan.hpp"
 
 using namespace rj;
@@ -179,6 +180,14 @@ int rj_table_from_csv(rj_context* ctx, const char* text, uint64_t n_bytes, uint6
 int rj_debug_parse_fp64(const char* field, uint64_t n, uint64_t* bits) {
     if (!bits || (n && !field)) return RJ_ERR_ARG;
     return rj::parse_fp64_host(field, n, bits);
+}
+
+int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, uint64_t* key, uint32_t* null_digit) {
+    if (!key || !null_digit || (flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST))) return RJ_ERR_ARG;
+    if (type != RJ_INT32 && type != RJ_INT64 && type != RJ_FP64) return RJ_ERR_ARG;
+    *key = is_null ? 0 : rj::sort_key_bits(bits, type == RJ_INT32 ? 4 : 8, type == RJ_FP64, (flags & RJ_SORT_DESC) != 0);
+    *null_digit = rj::sort_null_digit(is_null != 0, (flags & RJ_SORT_NULLS_FIRST) != 0);
+    return RJ_OK;
 }
 
 int rj_debug_launch_log(rj_context* ctx, int on) {

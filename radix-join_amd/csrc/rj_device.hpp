@@ -430,4 +430,24 @@ struct SelectProg {
     SelectOp ops[SEL_MAX_OPS];
 };
 
+// ---- Sort (RJ_NODE_SORT): a stable LSD radix sort of {encoded key, row id} pairs, one key column at
+// a time from the last to the first, 8 bits per pass.  A workgroup owns one tile of SORT_TILE
+// consecutive rows: wave w of it holds rows [w * SORT_TILE / 4, (w + 1) * SORT_TILE / 4) of the tile,
+// 64 consecutive ones per item, so that "earlier row" is (wave, item, lane) order.
+constexpr int SORT_THREADS = 256;
+constexpr int SORT_TILE = 4096;                          // rows per workgroup and per column of the tile x digit table
+constexpr int SORT_ITEMS = SORT_TILE / SORT_THREADS;     // rows per thread
+constexpr int SORT_RADIX = 256;                          // bins per pass
+constexpr int SORT_NULL_DIGIT = 8;                       // row of the histogram that counts the NULL flag (bins 0 and 1)
+constexpr int SORT_HIST_WORDS = (SORT_NULL_DIGIT + 1) * SORT_RADIX;  // per key column: [digit position][bin]
+constexpr int SORT_MAX_KEYS = 8;                         // RJ_SORT_MAX_KEYS
+static_assert(SORT_THREADS == SORT_RADIX && SORT_TILE % SORT_THREADS == 0 && SORT_TILE <= 65536,
+              "thread d owns bin d; whole rows of threads; ranks inside a tile are 16 bits");
+// what a pass takes its digit from
+enum SortMode : int32_t {
+    SORT_KEY32 = 0,  // (key >> shift) & 255 of 32-bit keys
+    SORT_KEY64 = 1,  // ... of 64-bit keys
+    SORT_FLAG = 2    // the NULL flag of the row the id names (no keys travel: the column's last pass)
+};
+
 }  // namespace rj

@@ -361,6 +361,10 @@ class Exec {
             Rel child = node(n.left, nullptr, depth + 1);
             return select(child, n, root_res);
         }
+        if (n.kind == RJ_NODE_SORT) {
+            Rel child = node(n.left, nullptr, depth + 1);
+            return sort(child, n, root_res);
+        }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
         Rel             r = node(n.right, nullptr, depth + 1);
@@ -1769,9 +1773,15 @@ class Exec {
             fprintf(stderr, "[rj diag] select rows=%llu ops=%llu kept=%llu\n", (unsigned long long)child.n, (unsigned long long)n_ops,
                     (unsigned long long)nrows);
 
+        return emit_rows(child, n, ids, ids ? ids->as<uint32_t>() : nullptr, nrows, root_res);
+    }
+
+    // The tail of a selection and of a sort: output row i is row idx[i] of `child` (nrows of them; idx
+    // points into `ids`, in this order; nullptr = the child's own rows, all of them).  Every distinct
+    // output column is gathered once — at the root straight into Page images.
+    Rel emit_rows(const Rel& child, const rj_node& n, const BufP& ids, const uint32_t* idx, uint64_t nrows, Result* root_res) {
         // ---- the output columns; a child column named several times is materialised once
         const bool               is_root = root_res != nullptr;
-        const uint32_t*          idx = ids ? ids->as<uint32_t>() : nullptr;
         std::map<uint64_t, DCol> made;
         std::map<uint64_t, ResultColumn> made_rc;
         Rel out;
@@ -1785,7 +1795,7 @@ class Exec {
                 if (idx && src.kind == COL_IOTA) {
                     d.kind = COL_DENSE;  // row ids of the base table ARE the list
                     d.hold = ids;
-                    d.ptr = ids->as<uint8_t>();
+                    d.ptr = reinterpret_cast<const uint8_t*>(idx);
                     d.tcol = nullptr;
                 } else if (idx) {
                     // a root column without NULLs goes straight into its Page images
@@ -1812,12 +1822,14 @@ class Exec {
                 ResultColumn rc;
                 if (d.type == RJ_VARCHAR) {
                     rc.type = d.type;
-                    BufP rowids = d.hold;
+                    BufP            rowids;
+                    const uint32_t* rows = reinterpret_cast<const uint32_t*>(d.ptr);  // (`idx` itself may start inside `ids`)
                     if (d.kind == COL_IOTA) {  // (a projection only: every row of the base table, in order)
                         rowids = ctx->buf(nrows * 4);
                         launch_gather(L, d.ref(), nullptr, nrows, OutStream{rowids->as<uint8_t>(), ST_DENSE32, 0}, nullptr);
+                        rows = rowids->as<uint32_t>();
                     }
-                    varchar_root(rowids ? rowids->as<uint32_t>() : reinterpret_cast<const uint32_t*>(d.ptr), nrows, d, rc);
+                    varchar_root(rows, nrows, d, rc);
                 } else if (idx && d.kind == COL_PAGED) {  // gathered into Page images above
                     rc.type = d.type;
                     rc.dev_pages = d.hold;
@@ -1830,6 +1842,112 @@ class Exec {
             root_res->cols.push_back(made_rc.at(c));
         }
         return out;
+    }
+
+    // ---------------------------------------------------------------------- sort
+    // RJ_NODE_SORT (semantics in rj.h): ORDER BY / LIMIT / OFFSET over the one child.  A stable LSD radix
+    // sort of {encoded key, row id}: the key columns from the last to the first, each encoded through
+    // the permutation the columns behind it left (sort_column), so that stability gives the
+    // lexicographic order.  Only the rows of the slice are gathered afterwards (emit_rows).  One host
+    // sync per key column: its digit histograms, which say what passes it needs.
+    //
+    // One key column: `perm` (n ids, or none = the child's own order) -> the order with this column as
+    // the most significant key.  A pass whose digit has ONE non-empty bin over all rows is not
+    // launched; a column without any pass leaves `perm` as it is.
+    void sort_column(const DCol& c, int32_t flags, uint32_t n, BufP& perm) {
+        const int      W = c.width;
+        const uint32_t n_tiles = n / SORT_TILE + (n % SORT_TILE != 0);
+        BufP           keys = ctx->buf((uint64_t)n * W);
+        BufP           hist = ctx->buf(SORT_HIST_WORDS * 4);
+        std::vector<uint32_t> h(SORT_HIST_WORDS);
+        try {
+            RJ_HIP(hipMemsetAsync(hist->p, 0, SORT_HIST_WORDS * 4, ctx->stream));
+            const uint32_t chunks = n / SORT_THREADS + (n % SORT_THREADS != 0);
+            launch_sort_encode(L, c.ref(), perm ? perm->as<uint32_t>() : nullptr, n, c.type == RJ_FP64, flags, keys->as<uint8_t>(),
+                               hist->as<uint32_t>(), std::min<uint32_t>(chunks, (uint32_t)ctx->compute_units() * 8));
+            RJ_HIP(hipMemcpyAsync(h.data(), hist->p, SORT_HIST_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);  // `h` is the end of a copy that may still be queued
+            throw;
+        }
+        std::vector<int> passes;  // digit positions with more than one non-empty bin, the NULL digit last
+        for (int p = 0; p <= SORT_NULL_DIGIT; ++p) {
+            if (p >= W && p != SORT_NULL_DIGIT) continue;
+            int bins = 0;
+            for (int b = 0; b < SORT_RADIX; ++b) bins += h[(size_t)p * SORT_RADIX + b] != 0;
+            if (bins > 1) passes.push_back(p);
+        }
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] sort column rows=%u width=%d flags=%d passes=%zu\n", n, W, flags, passes.size());
+        if (passes.empty()) return;
+        BufP table = ctx->buf((uint64_t)SORT_RADIX * n_tiles * 4);
+        BufP keys2, ids_in = perm, spare;  // (ids_in: none = positions)
+        for (size_t q = 0; q < passes.size(); ++q) {
+            const int  p = passes[q];
+            const bool flag = p == SORT_NULL_DIGIT;
+            // the keys travel only as far as a later pass reads them
+            const bool keys_on = !flag && q + 1 < passes.size() && passes[q + 1] != SORT_NULL_DIGIT;
+            if (keys_on && !keys2) keys2 = ctx->buf((uint64_t)n * W);
+            BufP           ids_out = spare ? spare : ctx->buf((uint64_t)n * 4);
+            const int      mode = flag ? SORT_FLAG : (W == 4 ? SORT_KEY32 : SORT_KEY64);
+            const uint32_t null_digit = (flags & RJ_SORT_NULLS_FIRST) ? 0u : 1u, shift = flag ? 0u : 8u * (uint32_t)p;
+            const uint32_t* in = ids_in ? ids_in->as<uint32_t>() : nullptr;
+            launch_sort_count(L, mode, keys->as<uint8_t>(), in, c.valid, null_digit, n, shift, table->as<uint32_t>());
+            launch_sort_scan(L, hist->as<uint32_t>() + (size_t)p * SORT_RADIX, n, table->as<uint32_t>());
+            launch_sort_scatter(L, mode, keys->as<uint8_t>(), in, c.valid, null_digit, n, shift, table->as<uint32_t>(),
+                                keys_on ? keys2->as<uint8_t>() : nullptr, ids_out->as<uint32_t>());
+            spare = ids_in;
+            ids_in = ids_out;
+            if (keys_on) std::swap(keys, keys2);
+        }
+        perm = ids_in;
+    }
+
+    Rel sort(Rel& child, const rj_node& n, Result* root_res) {
+        const size_t cw = child.cols.size();
+        JoinSpec     js;  // (the declared types, for empty_rel)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            if (n.out_idx[k] >= cw) throw_fmt(RJ_ERR_ARG, "sort: output attr out of range");
+            if (child.cols[n.out_idx[k]].type != n.out_type[k])
+                throw_fmt(RJ_ERR_ARG, "sort: declared type differs from the child column's type");
+            js.out_type.push_back(n.out_type[k]);
+        }
+        const uint64_t     n_keys = RJ_SORT_N_KEYS(&n), limit = RJ_SORT_LIMIT(&n), offset = RJ_SORT_OFFSET(&n);
+        const rj_sort_key* keys = RJ_SORT_KEYS(&n);
+        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "sort: more than %d keys", SORT_MAX_KEYS);
+        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "sort: %llu keys but a NULL key pointer", (unsigned long long)n_keys);
+        for (uint64_t k = 0; k < n_keys; ++k) {
+            if (keys[k].column < 0 || (uint64_t)keys[k].column >= cw) throw_fmt(RJ_ERR_ARG, "sort: key column out of range");
+            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "sort: unknown key flags %d", keys[k].flags);
+            if (child.cols[(size_t)keys[k].column].type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "sort: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
+                                              "are not read here", keys[k].column);
+        }
+        if (child.n == 0) return empty_rel(js, root_res);
+        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        // the slice [begin, begin + count): offset + limit is never formed
+        const uint64_t begin = std::min<uint64_t>(offset, child.n), count = std::min<uint64_t>(limit, child.n - begin);
+        if (count == 0) return empty_rel(js, root_res);
+        const bool whole = count == child.n;
+        // below another node the order is nobody's business: without a slice the child passes through
+        BufP perm;
+        if (root_res || !whole) {
+            for (uint64_t k = n_keys; k-- > 0;) {
+                bool shadowed = false;  // behind the same column nothing is left to order: rows that tie on it tie again
+                for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
+                if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, (uint32_t)child.n, perm);
+            }
+        }
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] sort rows=%llu keys=%llu begin=%llu count=%llu permuted=%d\n", (unsigned long long)child.n,
+                    (unsigned long long)n_keys, (unsigned long long)begin, (unsigned long long)count, perm ? 1 : 0);
+        if (!perm && !whole) {  // no pass moved a row: the slice is a run of positions
+            perm = ctx->buf(count * 4);
+            launch_sort_iota(L, perm->as<uint32_t>(), (uint32_t)begin, (uint32_t)count);
+            return emit_rows(child, n, perm, perm->as<uint32_t>(), count, root_res);
+        }
+        return emit_rows(child, n, perm, perm ? perm->as<uint32_t>() + begin : nullptr, count, root_res);
     }
 
     // a fixed-width column (paged, or dense with or without validity) as a root result column: Page
@@ -2339,6 +2457,8 @@ class ShardedExec {
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: aggregation (RJ_NODE_AGG) nodes run on one device");
         if (n.kind == RJ_NODE_SELECT)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: selection (RJ_NODE_SELECT) nodes run on one device");
+        if (n.kind == RJ_NODE_SORT)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: sort (RJ_NODE_SORT) nodes run on one device");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -2734,6 +2854,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "a selection node (RJ_NODE_SELECT) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_SORT) {
+        if (why) *why = "a sort node (RJ_NODE_SORT) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -2810,6 +2934,8 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_SELECT)
         throw_fmt(RJ_ERR_UNSUPPORTED,
                   "rj_execute_sharded: the plan holds a selection (RJ_NODE_SELECT) node; selections run on one device");
+    if (n.kind == RJ_NODE_SORT)
+        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds a sort (RJ_NODE_SORT) node; sorts run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

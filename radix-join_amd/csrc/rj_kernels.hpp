@@ -178,6 +178,26 @@ void launch_agg_column(const Launch& L, const unsigned long long* src, const uns
 void launch_select(const Launch& L, const SelectProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t* out_ids,
                    unsigned long long* cursor, uint32_t grid);
 
+// ---- sort (RJ_NODE_SORT): a stable LSD radix sort of {key, row id}, SORT_RADIX bins per pass, tiles of
+// SORT_TILE rows (rj_device.hpp).  n_tiles = ceil(n_rows / SORT_TILE) everywhere.
+// One key column read through `perm` (row i of the current order = row perm[i]; nullptr = i) -> keys_out
+// (n_rows keys of col.width bytes) and hist (SORT_HIST_WORDS, zeroed) += the counts of every digit
+// position; flags = RJ_SORT_DESC | RJ_SORT_NULLS_FIRST.  `grid` workgroups stride over the rows.
+void launch_sort_encode(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, bool f64, int32_t flags,
+                        uint8_t* keys_out, uint32_t* hist, uint32_t grid);
+// One pass (mode: SortMode; SORT_FLAG reads valid[id] and gives a NULL row the digit null_digit):
+// table[SORT_RADIX][n_tiles] = rows per digit and tile ...
+void launch_sort_count(const Launch& L, int mode, const uint8_t* keys, const uint32_t* ids, const uint8_t* valid, uint32_t null_digit,
+                       uint32_t n_rows, uint32_t shift, uint32_t* table);
+// ... -> where they start in the output (hist: the SORT_RADIX totals of this digit position) ...
+void launch_sort_scan(const Launch& L, const uint32_t* hist, uint32_t n_rows, uint32_t* table);
+// ... and the rows moved there, stably.  ids_in == nullptr: id = position; keys_out == nullptr: ids only.
+void launch_sort_scatter(const Launch& L, int mode, const uint8_t* keys_in, const uint32_t* ids_in, const uint8_t* valid,
+                         uint32_t null_digit, uint32_t n_rows, uint32_t shift, const uint32_t* table, uint8_t* keys_out,
+                         uint32_t* ids_out);
+// out[i] = base + i, i < n
+void launch_sort_iota(const Launch& L, uint32_t* out, uint32_t base, uint32_t n);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

@@ -126,6 +126,7 @@ EXPORTS = [
     "rj_table_release",
     "rj_table_from_csv",
     "rj_debug_parse_fp64",
+    "rj_debug_sort_key",
     "rj_table_num_rows",
     "rj_table_col_pages",
     "rj_table_copy_pages",
@@ -611,6 +612,20 @@ def parse_fp64(field: bytes):
     bits = C.c_uint64(0)
     st = L.rj_debug_parse_fp64(field, len(field), C.byref(bits))
     return int(st), int(bits.value)
+
+
+def sort_key(dtype: int, flags: int, bits: int, is_null: bool = False):
+    """rj_debug_sort_key: the sort's order-preserving key encoding on the host.  bits: the value's bits
+    as an unsigned number (an INT32's in the low word).  -> (null_digit, key): a row sorts before
+    another exactly when its pair is the smaller one."""
+    L = load()
+    L.rj_debug_sort_key.restype = C.c_int
+    L.rj_debug_sort_key.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    key, nd = C.c_uint64(0), C.c_uint32(0)
+    rc = L.rj_debug_sort_key(dtype, flags, bits, 1 if is_null else 0, C.byref(key), C.byref(nd))
+    if rc != 0:
+        raise RjError(rc, "rj_debug_sort_key: bad type or flags")
+    return int(nd.value), int(key.value)
 
 
 def make_comm_id() -> bytes:

@@ -50,6 +50,10 @@ class JoinNode:
 
 # rj_node_kind (include/rj.h)
 NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG, NODE_SELECT = 0, 1, 2, 3, 4, 5, 6, 7
+NODE_SORT = 8
+# rj_sort_key::flags, RJ_SORT_NO_LIMIT
+SORT_DESC, SORT_NULLS_FIRST = 1, 2
+SORT_NO_LIMIT = 2**64 - 1
 # rj_agg_func and the RJ_AGG_OUT / RJ_AGG_FUNC / RJ_AGG_COL encoding of an aggregation's out_idx
 AGG_KEY, AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3, 4, 5
 
@@ -126,6 +130,19 @@ class SelectNode:
 
 
 @dataclass
+class SortNode:
+    """Sort (kind NODE_SORT): ORDER BY keys [LIMIT limit [OFFSET offset]] over the one child; the
+    PlanNode's output_attrs index the child's outputs as a selection's do.  keys = [(column, flags)],
+    the first most significant, column an output of the child, flags a set of SORT_DESC and
+    SORT_NULLS_FIRST (default: ascending, NULLs last).  limit None = no LIMIT.  The row order of the
+    result is promised only at the plan's root (include/rj.h)."""
+    child: int
+    keys: list
+    limit: object = None
+    offset: int = 0
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -176,6 +193,12 @@ class Plan:
     def new_select_node(self, child, program, output_attrs):
         """WHERE / HAVING / projection: the child's rows that pass `program` (see SelectNode)."""
         self.nodes.append(PlanNode(SelectNode(child, list(program or [])), list(output_attrs)))
+        return len(self.nodes) - 1
+
+    def new_sort_node(self, child, keys, output_attrs, limit=None, offset=0):
+        """ORDER BY / LIMIT / OFFSET: rows [offset, offset + limit) of the child ordered by `keys`
+        (see SortNode)."""
+        self.nodes.append(PlanNode(SortNode(child, [tuple(k) for k in keys], limit, offset), list(output_attrs)))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -325,6 +348,10 @@ class rj_node(C.Structure):
     ]
 
 
+class rj_sort_key(C.Structure):
+    _fields_ = [("column", C.c_int32), ("flags", C.c_int32)]
+
+
 class rj_column(C.Structure):
     _fields_ = [("type", C.c_int32), ("n_pages", C.c_uint64), ("pages", C.POINTER(C.c_void_p))]
 
@@ -402,6 +429,18 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.left = n.data.child
             nd.right = n_ops  # RJ_SELECT_N_OPS / RJ_SELECT_OPS: the struct cannot grow
             nd.right_attr = C.addressof(ops) if n_ops else 0
+        elif isinstance(n.data, SortNode):
+            nk = len(n.data.keys)
+            karr = (rj_sort_key * max(1, nk))()
+            for j, (col, flags) in enumerate(n.data.keys):
+                karr[j].column, karr[j].flags = int(col), int(flags)
+            keep.append(karr)
+            nd.kind = NODE_SORT
+            nd.left = n.data.child
+            nd.right = nk  # RJ_SORT_N_KEYS / RJ_SORT_KEYS / RJ_SORT_LIMIT / RJ_SORT_OFFSET: the struct cannot grow
+            nd.right_attr = C.addressof(karr) if nk else 0
+            nd.left_attr = SORT_NO_LIMIT if n.data.limit is None else int(n.data.limit)
+            nd.base_table_id = int(n.data.offset)
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
