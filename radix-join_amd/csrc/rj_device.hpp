@@ -96,11 +96,17 @@ static_assert(PT_CAPBITS >= PT_MAXBITS && PT_CAPBITS <= 10, "fan-out capacity");
 constexpr int PT_FINEBITS = 15;                   // fine (two-digit) histogram: 2^15 bins = 128 KiB of LDS
 constexpr int LDS_BYTES  = 160 * 1024;            // per CU (and the most one workgroup may declare)
 static_assert(PT_THREADS >= PT_MAXF, "thread d scans digit d");
-// static LDS of the partition kernels: staging tile of 8-byte pairs + three digit arrays + wave sums
-static_assert(PT_TILE * 8 + 3 * PT_MAXF * 4 + (PT_THREADS / 64) * 4 <= LDS_BYTES,
+// Dummy rank counters behind the real ones (s_cnt[PT_MAXF + lane % PT_DUMMY]): where the scatter's
+// branch-free ranking sends the items that hold no tuple.  Never cleared, scanned or read.
+constexpr int PT_DUMMY   = 32;
+// static LDS of the partition kernels: staging tile of 8-byte pairs + three digit arrays + dummy counters + wave sums
+static_assert(PT_TILE * 8 + (3 * PT_MAXF + PT_DUMMY) * 4 + (PT_THREADS / 64) * 4 <= LDS_BYTES,
               "scatter tile does not fit the 160 KiB of LDS");
 static_assert((4 << PT_FINEBITS) <= LDS_BYTES, "fine histogram does not fit the LDS");
-static_assert(PT_TILE <= 65536, "ranks are packed into 16 bits");
+// a rank (< PT_TILE) is kept in PT_RANK_MASK's bits, two ranks or two LDS positions (< PT_TILE; 0xffff
+// for an item without a tuple) per register
+constexpr uint32_t PT_RANK_MASK = PT_TILE <= 16384 ? 0x3fffu : 0x7fffu;
+static_assert(PT_TILE <= 32768 && PT_ITEMS % 2 == 0, "ranks and LDS positions are packed two per register");
 static_assert(PT_ITEMS % 4 == 0 && PT_ITEMS <= 32, "full tiles are loaded as 16-byte vectors; one mask bit per item");
 
 struct PassParams {

@@ -524,7 +524,7 @@ class Exec {
         } chunk_ev;
         const bool chunk_second = ctx->tune.mall_chunk > 0 && passes == 2 && !fine && !shape && !ws && !external && P.packed &&
                                   !packed_side && ctx->tune.xcd_split && n >= (uint64_t)ctx->tune.xcd_min_rows;
-        // RJ_TUNE_BLOCKED_MID: between the passes of a packed plan the pairs lie in blocks of 16 keys + 16 carries
+        // RJ_TUNE_BLOCKED_MID: between the passes of a packed plan the pairs lie in blocks of 256 keys + 256 carries
         // (BlockedLoader), so that the next pass' histogram reads 4 instead of 8 bytes per tuple
         const bool blocked_mid = ctx->tune.blocked_mid != 0 && P.packed && passes >= 2 && !fine && !shape && !ws && !external &&
                                  !packed_side && !chunk_second;

@@ -22,6 +22,16 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// threadIdx.x as a value the compiler cannot see through.  What is derived from it inside a loop is
+// computed there: derived from threadIdx.x itself, a tile loop's per-lane indices and offsets (a few
+// dozen of them in the scatter kernels) are hoisted out of the loop and occupy registers, or spill,
+// through the phases that need every register for loads in flight.
+__device__ __forceinline__ uint32_t tile_tid() {
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
 // Exclusive scan of one value per thread across the workgroup (blockDim.x a
 // multiple of 64, at most 1024).  s_wsum needs blockDim.x/64 words.  Contains
 // one barrier; the caller must sync again before reusing s_wsum.

@@ -581,10 +581,10 @@ struct PackedLoader {
     }
 };
 
-// {hashed key, carry} pairs BETWEEN the passes of a packed plan, blocked: tuple g lives in block g / 64 —
-// 128 words: the 64 keys, then the 64 carries — so that the next pass' histogram reads the key halves
-// only (two of every four 128-byte lines: 4 instead of 8 bytes per tuple; with 16-tuple blocks it still
-// pulled every line) while a scatter writes a run of consecutive tuples into ONE array.
+// {hashed key, carry} pairs BETWEEN the passes of a packed plan, blocked: tuple g lives in block g / 256 —
+// 512 words: the 256 keys, then the 256 carries — so that the next pass' histogram reads the key halves
+// only (4 instead of 8 bytes per tuple; with 16-tuple blocks it still pulled every line) while a
+// scatter writes a run of consecutive tuples into ONE array.
 struct BlockedLoader {
     const uint32_t* in;
     RJ_TRIVIAL_ISSUE_FINISH
@@ -650,9 +650,10 @@ struct SrcLoader {
     // Row of item j.  Full tiles use the vector mapping (four consecutive rows per thread
     // and 16-byte load; ROWS32 % 4 == 0 and tiles start at multiples of 4, so the four rows
     // share a page), partial tiles the strided one with clamped indices.
-    __device__ __forceinline__ static uint32_t item_row(bool vec, uint32_t base, int j) {
-        return vec ? base + ((j / 4) * PT_THREADS + threadIdx.x) * 4 + (j % 4)
-                   : base + j * PT_THREADS + threadIdx.x;
+    // (tid: threadIdx.x, or the scatter kernels' tile_tid())
+    __device__ __forceinline__ static uint32_t item_row(bool vec, uint32_t base, int j, uint32_t tid = threadIdx.x) {
+        return vec ? base + ((j / 4) * PT_THREADS + tid) * 4 + (j % 4)
+                   : base + j * PT_THREADS + tid;
     }
 
     // 32-bit column -> one word per item
@@ -666,7 +667,7 @@ struct SrcLoader {
     // a tile in flight at once the 64-bit form spilled to scratch.
     template <bool NT = false>
     __device__ __forceinline__ static void load_col32(const ColRef& c, bool vec, uint32_t base,
-                                                      uint32_t end, uint32_t (&out)[PT_ITEMS]) {
+                                                      uint32_t end, uint32_t (&out)[PT_ITEMS], uint32_t tid = threadIdx.x) {
         const bool     paged = c.kind == COL_PAGED;
         const uint32_t ub = __builtin_amdgcn_readfirstlane(base);
         const uint32_t p0 = ub / ROWS32, s0 = ub - p0 * ROWS32;  // page / slot of the tile's first row
@@ -680,7 +681,7 @@ struct SrcLoader {
         if (vec) {
 #pragma unroll
             for (int v = 0; v < PT_ITEMS / 4; ++v) {
-                const u32x4a* q = reinterpret_cast<const u32x4a*>(tp + off((v * PT_THREADS + threadIdx.x) * 4u));
+                const u32x4a* q = reinterpret_cast<const u32x4a*>(tp + off((v * PT_THREADS + tid) * 4u));
                 u32x4a        x;
                 if constexpr (NT)
                     x = __builtin_nontemporal_load(q);
@@ -693,13 +694,13 @@ struct SrcLoader {
             const uint32_t last = end - 1u - ub;
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j)
-                out[j] = *reinterpret_cast<const uint32_t*>(tp + off(min((uint32_t)(j * PT_THREADS + threadIdx.x), last)));
+                out[j] = *reinterpret_cast<const uint32_t*>(tp + off(min((uint32_t)(j * PT_THREADS + tid), last)));
         }
     }
     template <bool NT = false>
     __device__ __forceinline__ static void load_col64(const ColRef& c, bool vec, uint32_t base,
                                                       uint32_t end, uint32_t (&lo)[PT_ITEMS],
-                                                      uint32_t (&hi)[PT_ITEMS]) {
+                                                      uint32_t (&hi)[PT_ITEMS], uint32_t tid = threadIdx.x) {
         const bool     paged = c.kind == COL_PAGED;
         const uint32_t ub = __builtin_amdgcn_readfirstlane(base);
         const uint32_t p0 = ub / ROWS64, s0 = ub - p0 * ROWS64;
@@ -708,7 +709,7 @@ struct SrcLoader {
         const uint32_t bias = paged ? s0 * 8u + HDR64 : 0u, per_page = paged ? PAGE_BYTES - ROWS64 * 8u : 0u;
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; ++j) {
-            const uint32_t rel = min(item_row(vec, 0u, j), last);
+            const uint32_t rel = min(item_row(vec, 0u, j, tid), last);
             const uint32_t o = rel * 8u + bias + ((s0 + rel) / ROWS64) * per_page;  // (see load_col32)
             const uint64_t* a = reinterpret_cast<const uint64_t*>(tp + o);
             uint64_t        v;
@@ -722,12 +723,12 @@ struct SrcLoader {
     }
     // a 32-bit column of any kind (a base table's row-id column included)
     __device__ __forceinline__ static void load_col32_any(const ColRef& c, bool vec, uint32_t base, uint32_t end,
-                                                          uint32_t (&out)[PT_ITEMS]) {
+                                                          uint32_t (&out)[PT_ITEMS], uint32_t tid = threadIdx.x) {
         if (c.kind == COL_IOTA) {
 #pragma unroll
-            for (int j = 0; j < PT_ITEMS; ++j) out[j] = item_row(vec, base, j);
+            for (int j = 0; j < PT_ITEMS; ++j) out[j] = item_row(vec, base, j, tid);
         } else {
-            load_col32(c, vec, base, end, out);
+            load_col32(c, vec, base, end, out, tid);
         }
     }
 
@@ -735,28 +736,28 @@ struct SrcLoader {
     template <bool NT = false>
     __device__ __forceinline__ uint32_t raw_keys(bool vec, uint32_t base, uint32_t end,
                                                  uint32_t (&lo)[PT_ITEMS],
-                                                 uint32_t (&hi)[PT_ITEMS]) const {
+                                                 uint32_t (&hi)[PT_ITEMS], uint32_t tid = threadIdx.x) const {
         if constexpr (KW == 1) {
-            load_col32<NT>(s.key, vec, base, end, lo);
+            load_col32<NT>(s.key, vec, base, end, lo, tid);
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j) hi[j] = 0;
         } else {
-            load_col64<NT>(s.key, vec, base, end, lo, hi);
+            load_col64<NT>(s.key, vec, base, end, lo, hi, tid);
         }
         if (vec) return PT_ALL_ITEMS;
         uint32_t ok = 0;
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; ++j)
-            ok |= (uint32_t)(base + j * PT_THREADS + threadIdx.x < end) << j;
+            ok |= (uint32_t)(base + j * PT_THREADS + tid < end) << j;
         return ok;
     }
     __device__ __forceinline__ uint32_t drop_invalid(bool vec, uint32_t base, uint32_t end,
-                                                     uint32_t ok) const {
+                                                     uint32_t ok, uint32_t tid = threadIdx.x) const {
         const uint8_t* vp = s.key.valid;
         if (vp) {  // uniform: the column was decoded by K1 and carries validity bytes
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j)
-                if (!vp[min(item_row(vec, base, j), end - 1u)]) ok &= ~(1u << j);
+                if (!vp[min(item_row(vec, base, j, tid), end - 1u)]) ok &= ~(1u << j);
         }
         return ok;
     }
@@ -813,48 +814,54 @@ struct SrcLoader {
         static_assert(NW == KW + CW, "word count");
         const bool vec = base + PT_TILE <= end;
         uint32_t   lo[PT_ITEMS], hi[PT_ITEMS];
-        uint32_t   ok = raw_keys(vec, base, end, lo, hi);
+        // (an opaque thread index: the per-lane rows and offsets are formed anew for every tile instead of
+        // being kept in registers, or spilled, from tile to tile)
+        const uint32_t tid = tile_tid();
+        uint32_t       ok = raw_keys(vec, base, end, lo, hi, tid);
         if constexpr (WIDE == WIDE_32S) {
             uint32_t c0[PT_ITEMS];
-            load_col32_any(s.carry, vec, base, end, c0);
+            load_col32_any(s.carry, vec, base, end, c0, tid);
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j) w[j][KW] = c0[j];
-            load_col32_any(s.carry2, vec, base, end, c0);
+            load_col32_any(s.carry2, vec, base, end, c0, tid);
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j) w[j][KW + 1] = c0[j];
             if constexpr (CW == 3) {
-                load_col32_any(s.carry3, vec, base, end, c0);
+                load_col32_any(s.carry3, vec, base, end, c0, tid);
 #pragma unroll
                 for (int j = 0; j < PT_ITEMS; ++j) w[j][KW + 2] = c0[j];
             }
         } else if constexpr (WIDE == WIDE_64_32) {
             uint32_t c0[PT_ITEMS], c1[PT_ITEMS];
-            load_col64(s.carry, vec, base, end, c0, c1);
+            load_col64(s.carry, vec, base, end, c0, c1, tid);
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j) {
                 w[j][KW] = c0[j];
                 w[j][KW + 1] = c1[j];
             }
-            load_col32_any(s.carry2, vec, base, end, c0);
+            load_col32_any(s.carry2, vec, base, end, c0, tid);
 #pragma unroll
             for (int j = 0; j < PT_ITEMS; ++j) w[j][KW + 2] = c0[j];
-        } else if constexpr (CW >= 1) {
-            if (s.carry_mode == CARRY_ROWIDX) {  // CW == 1 by construction
+        } else if constexpr (CW == 1) {
+            // (a row-index carry is one word by construction.  Asked for at every CW, the branch left the
+            // second carry word of a two-word tuple undefined on one path, and the compiler kept the last
+            // item's pair in scratch memory for it: 16 bytes per lane, stored behind a wait for the payload)
+            if (s.carry_mode == CARRY_ROWIDX) {
 #pragma unroll
-                for (int j = 0; j < PT_ITEMS; ++j) w[j][KW] = item_row(vec, base, j);
-            } else if constexpr (CW == 1) {
+                for (int j = 0; j < PT_ITEMS; ++j) w[j][KW] = item_row(vec, base, j, tid);
+            } else {
                 uint32_t c0[PT_ITEMS];
-                load_col32(s.carry, vec, base, end, c0);
+                load_col32(s.carry, vec, base, end, c0, tid);
 #pragma unroll
                 for (int j = 0; j < PT_ITEMS; ++j) w[j][KW] = c0[j];
-            } else {
-                uint32_t c0[PT_ITEMS], c1[PT_ITEMS];
-                load_col64(s.carry, vec, base, end, c0, c1);
+            }
+        } else if constexpr (CW >= 2) {
+            uint32_t c0[PT_ITEMS], c1[PT_ITEMS];
+            load_col64(s.carry, vec, base, end, c0, c1, tid);
 #pragma unroll
-                for (int j = 0; j < PT_ITEMS; ++j) {
-                    w[j][KW] = c0[j];
-                    w[j][KW + 1] = c1[j];
-                }
+            for (int j = 0; j < PT_ITEMS; ++j) {
+                w[j][KW] = c0[j];
+                w[j][KW + 1] = c1[j];
             }
         }
 #pragma unroll
@@ -874,7 +881,7 @@ struct SrcLoader {
             lo[j] = w[j][0];
             hi[j] = KW == 2 ? w[j][KW - 1] : 0u;
         }
-        ok = drop_invalid(vec, base, end, ok);
+        ok = drop_invalid(vec, base, end, ok, tile_tid());
         ok = hash_keys(ok, lo, hi);
 #pragma unroll
         for (int j = 0; j < PT_ITEMS; ++j) {
@@ -1087,16 +1094,69 @@ __global__ __launch_bounds__(PT_MAXF) void k_scan_fine(const uint32_t* fine, uin
     }
 }
 
+// Ranking and positions of a tile where k_pass_scatter takes them branch-free (BATCHED there), so a thread's
+// PT_ITEMS LDS operations are issued together and waited for once (an exec-masked block per item made
+// them PT_ITEMS serial round trips), and both need the key words only: with a loader that issues the
+// key loads first, the carry loads are still in flight behind them.
+// rank_tile: every tuple takes its rank inside its digit from an LDS atomic add.  An item that holds
+// no tuple (ok bit clear: past the end of a partial tile, NULL key) adds to a dummy counter behind the
+// real ones instead of taking a branch; PT_DUMMY of them, by lane, so that a run of such items does
+// not serialise a wave on one LDS address.  Ranks are kept two per register.
+template <int NW>
+__device__ __forceinline__ void rank_tile(const PassParams& pp, uint32_t mask, uint32_t ok,
+                                          const uint32_t (&w)[PT_ITEMS][NW], uint32_t* s_cnt,
+                                          uint32_t (&rk)[PT_ITEMS / 2]) {
+    const uint32_t dummy = PT_MAXF + (threadIdx.x & (PT_DUMMY - 1));
+    uint32_t       r[PT_ITEMS];
+#pragma unroll
+    for (int j = 0; j < PT_ITEMS; ++j) {
+        const uint32_t m = 0u - ((ok >> j) & 1u);  // a bit select, not ?: (which compiles to a branch around the digit)
+        r[j] = atomicAdd(&s_cnt[(pass_digit(pp, w[j][0], mask) & m) | (dummy & ~m)], 1u);
+    }
+#pragma unroll
+    for (int j = 0; j < PT_ITEMS; j += 2)
+        rk[j / 2] = (r[j] & PT_RANK_MASK) | ((r[j + 1] & PT_RANK_MASK) << 16);
+}
+// place_tile: ranks -> LDS positions (start of the digit in the sorted tile + rank), in place and two per
+// register; PT_NO_POS, which no position reaches, for an item without a tuple.  The digit is recomputed
+// from the key word.
+constexpr uint32_t PT_NO_POS = 0xffffu;
+template <int NW>
+__device__ __forceinline__ void place_tile(const PassParams& pp, uint32_t mask, uint32_t ok,
+                                           const uint32_t (&w)[PT_ITEMS][NW], const uint32_t* s_base,
+                                           uint32_t (&rk)[PT_ITEMS / 2]) {
+    uint32_t b[PT_ITEMS];
+#pragma unroll
+    for (int j = 0; j < PT_ITEMS; ++j) b[j] = s_base[pass_digit(pp, w[j][0], mask)];
+#pragma unroll
+    for (int j = 0; j < PT_ITEMS; j += 2) {
+        const uint32_t p0 = ((ok >> j) & 1u) ? b[j] + (rk[j / 2] & 0xffffu) : PT_NO_POS;
+        const uint32_t p1 = ((ok >> (j + 1)) & 1u) ? b[j + 1] + (rk[j / 2] >> 16) : PT_NO_POS;
+        rk[j / 2] = p0 | (p1 << 16);
+    }
+}
+__device__ __forceinline__ uint32_t tile_pos(const uint32_t (&ps)[PT_ITEMS / 2], int j) {
+    return (j & 1) ? ps[j / 2] >> 16 : ps[j / 2] & 0xffffu;
+}
+
+template <class L>
+struct is_src_loader : std::false_type {};
+template <int KW, int CW, int WIDE>
+struct is_src_loader<SrcLoader<KW, CW, WIDE>> : std::true_type {};
+
 // ================================================================ K4 scatter
 // Scatter half of the radix partition (reference counterpart: the serial
 // scatter src/execute.cpp:175-184).  Per tile of PT_TILE (16384) tuples:
-//   1. every tuple takes its rank inside its digit from an LDS atomic add;
+//   1. every tuple takes its rank inside its digit from an LDS atomic add (rank_tile);
 //   2. the digit counters are scanned (wave shuffles) into LDS positions;
 //   3. per word array the tile is written to LDS in digit order, then copied out
 //      so that consecutive lanes write consecutive addresses of one digit's run
 //      (software write-combining: HBM sees contiguous runs, not 4-byte scatters).
 // Every tile reserves its output ranges with one atomic per digit (cursor = start of the
 // digit's partition, from the scanned histogram).
+// Steps 1 and 2 and the reservation need the key words only.  In the first pass of a key + two-word-carry
+// plan (SrcLoader issues the key loads first) they run while the tile's carry loads, two thirds of its
+// bytes, are in flight; the carries are waited for where they are staged.
 // PAIR >= 0: words PAIR and PAIR+1 (a two-word carry) are written as 8-byte pairs into ONE array,
 // out.w[PAIR] — one output stream and one staging round less than two word arrays.
 // AOS (NW == 3, PAIR == 1: key + two-word carry, the LAST pass of a plan): the output is ONE array
@@ -1114,7 +1174,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
     static_assert(!AOS || (NW == 3 && PAIR == 1), "12-byte tuples: one key word + a two-word carry");
     __shared__ uint2    s_stage2[PT_TILE];  // 128 KiB: a word array uses the first half
     uint32_t* const     s_stage = reinterpret_cast<uint32_t*>(s_stage2);
-    __shared__ uint32_t s_cnt[PT_MAXF];
+    __shared__ uint32_t s_cnt[PT_MAXF + PT_DUMMY];  // (see rank_tile)
     __shared__ uint32_t s_base[PT_MAXF];
     __shared__ uint32_t s_delta[PT_MAXF];
     __shared__ uint32_t s_wsum[PT_THREADS / 64];
@@ -1131,16 +1191,27 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
         for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) s_cnt[d] = 0;
         lds_barrier();
 
-        uint32_t dr[PT_ITEMS];  // digit << 16 | rank, 0xffffffff = no tuple
-        // every load of the tile is issued before the first rank is taken
+        // every load of the tile is issued before the first rank is taken; the ranks wait for the keys only
         const uint32_t ok = ld.template load_tile<NW>(base, end, w);
+        // first pass of key + two-word carry: ranks and positions two per register, branch-free (rank_tile).
+        // Everything else keeps a rank per register and a branch per item.  The later passes of that shape
+        // and the packed kernel gained nothing measurable from the branch-free form
+        // (profiles/scatter_rank_ab.log), and with up to four words per tuple in registers there is no room
+        // for PT_ITEMS ranks in flight (compiled that way, the four-word kernels spilled more than they do)
+        constexpr bool BATCHED = NW == 3 && PAIR == 1 && is_src_loader<Loader>::value;
+        uint32_t       ps[PT_ITEMS / 2];  // BATCHED: ranks, then LDS positions, two per register
+        uint32_t       dr[PT_ITEMS];      // otherwise: digit << 16 | rank, then LDS position; 0xffffffff = no tuple
+        if constexpr (BATCHED) {
+            rank_tile<NW>(pp, mask, ok, w, s_cnt, ps);
+        } else {
 #pragma unroll
-        for (int j = 0; j < PT_ITEMS; ++j) {
-            dr[j] = 0xffffffffu;
-            if ((ok >> j) & 1u) {
-                uint32_t d = pass_digit(pp, w[j][0], mask);
-                uint32_t r = atomicAdd(&s_cnt[d], 1u);
-                dr[j] = (d << 16) | r;
+            for (int j = 0; j < PT_ITEMS; ++j) {
+                dr[j] = 0xffffffffu;
+                if ((ok >> j) & 1u) {
+                    uint32_t d = pass_digit(pp, w[j][0], mask);
+                    uint32_t r = atomicAdd(&s_cnt[d], 1u);
+                    dr[j] = (d << 16) | r;
+                }
             }
         }
         lds_barrier();
@@ -1159,33 +1230,44 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
         lds_barrier();
 
         // LDS position of every tuple, computed once for all word arrays
+        if constexpr (BATCHED) {
+            place_tile<NW>(pp, mask, ok, w, s_base, ps);
+        } else {
 #pragma unroll
-        for (int j = 0; j < PT_ITEMS; ++j)
-            if (dr[j] != 0xffffffffu) dr[j] = s_base[dr[j] >> 16] + (dr[j] & 0xffffu);
+            for (int j = 0; j < PT_ITEMS; ++j)
+                if (dr[j] != 0xffffffffu) dr[j] = s_base[dr[j] >> 16] + (dr[j] & 0xffffu);
+        }
 
         // key + two-word carry (NW == 3): keys and carry pairs of half the sorted tile are staged
         // TOGETHER and copied out together — as 12-byte tuples (AOS) or into the key array and the
         // pair array — so no per-element destination has to be kept in registers between the two
         // arrays (the 16 extra VGPRs spilled to scratch)
+        // (the copy-out's thread index is opaque to the compiler: its element indices and LDS addresses,
+        // 3 * PT_ITEMS values that do not change from tile to tile, were otherwise hoisted out of the tile
+        // loop and held in registers — or spilled — through the phases that have every load in flight)
+        const uint32_t tid = BATCHED ? tile_tid() : threadIdx.x;  // (the other shapes compile to more scratch with it)
         if constexpr (NW == 3 && PAIR == 1) {
             constexpr uint32_t HALF = PT_TILE / 2;
             uint2* const       s_p = s_stage2;                                      // [HALF] carries
             uint32_t* const    s_k = reinterpret_cast<uint32_t*>(s_stage2 + HALF);  // [HALF] keys
-            if (threadIdx.x < F) s_delta[threadIdx.x] = run - ex;  // global index = delta + sorted position
+            if (!BATCHED && threadIdx.x < F) s_delta[threadIdx.x] = run - ex;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
 #pragma unroll
                 for (int j = 0; j < PT_ITEMS; ++j) {
-                    const uint32_t lp = dr[j] - h * HALF;  // (no tuple: 0xffffffff stays out of range)
+                    const uint32_t lp = (BATCHED ? tile_pos(ps, j) : dr[j]) - h * HALF;  // (no tuple: PT_NO_POS stays out of range)
                     if (lp < HALF) {
                         s_k[lp] = w[j][0];
                         s_p[lp] = make_uint2(w[j][1], w[j][2]);
                     }
                 }
+                // global index = delta + sorted position.  BATCHED: behind the first half's staging, since the
+                // reservation was issued after the carry loads and waiting for it waits for all of them
+                if (BATCHED && h == 0 && threadIdx.x < F) s_delta[threadIdx.x] = run - ex;
                 lds_barrier();
 #pragma unroll
                 for (int k = 0; k < PT_ITEMS / 2; ++k) {
-                    const uint32_t i = k * PT_THREADS + threadIdx.x, gi = h * HALF + i;
+                    const uint32_t i = k * PT_THREADS + tid, gi = h * HALF + i;
                     if (gi < total) {
                         const uint32_t v = s_k[i];
                         const uint2    c = s_p[i];
@@ -1217,7 +1299,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
         uint32_t dest[PT_ITEMS];
 #pragma unroll
         for (int k = 0; k < PT_ITEMS; ++k) {
-            const uint32_t i = k * PT_THREADS + threadIdx.x;
+            const uint32_t i = k * PT_THREADS + tid;
             dest[k] = 0;
             if (i < total) {
                 const uint32_t v = s_stage[i];
@@ -1239,7 +1321,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
                     uint2* dst2 = reinterpret_cast<uint2*>(out.w[a]);
 #pragma unroll
                     for (int k = 0; k < PT_ITEMS; ++k) {
-                        const uint32_t i = k * PT_THREADS + threadIdx.x;
+                        const uint32_t i = k * PT_THREADS + tid;
                         if (i < total) dst2[dest[k]] = s_stage2[i];
                     }
                     lds_barrier();
@@ -1253,7 +1335,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
             uint32_t* dst = out.w[a];
 #pragma unroll
             for (int k = 0; k < PT_ITEMS; ++k) {
-                const uint32_t i = k * PT_THREADS + threadIdx.x;
+                const uint32_t i = k * PT_THREADS + tid;
                 if (i < total) dst[dest[k]] = s_stage[i];
             }
             lds_barrier();
