@@ -242,6 +242,55 @@ typedef enum rj_status {
  *   an error.
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
+ *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Grouping (GROUP BY any keys, or none, with COUNT / SUM / MIN / MAX; SELECT DISTINCT; no reference
+ * counterpart).
+ * RJ_NODE_GROUP has ONE child, `left`; `build_left`, `base_table_id` and `left_attr` are ignored.
+ *   It is the general form of RJ_NODE_AGG: any number of keys of INT32, INT64 or FP64, any number of
+ *   aggregated columns, FP64 columns under MIN / MAX / COUNT, and the aggregate without a key.  It
+ *   sorts where RJ_NODE_AGG hashes, so for ONE INT32 / INT64 key and columns within that kind's carry
+ *   limit RJ_NODE_AGG is the faster node (DESIGN.md §4 has the figures).
+ *   Keys: rj_node cannot grow, so RJ_GROUP_N_KEYS(node) = `right` (0 .. RJ_SORT_MAX_KEYS) and
+ *   RJ_GROUP_KEYS(node) = `right_attr` as a `const rj_sort_key*` that stays valid during the call.
+ *   rj_sort_key::column indexes the CHILD's outputs and may repeat; rj_sort_key::flags is a set of
+ *   RJ_SORT_DESC and RJ_SORT_NULLS_FIRST and says where the key's groups go in the result's order.
+ *   Outputs: as for RJ_NODE_AGG, out_idx[k] = RJ_AGG_OUT(func, column), out_type[k] = the declared
+ *   RESULT type; any number of outputs over any number of distinct columns:
+ *     RJ_AGG_KEY        the group's value of a key column; column must be one of the key columns;
+ *                       that column's type; a key may appear 0, 1 or several times
+ *     RJ_AGG_COUNT_STAR rows of the group; column must be 0; INT64
+ *     RJ_AGG_COUNT      non-NULL values of an INT32 / INT64 / FP64 column; INT64
+ *     RJ_AGG_SUM        sum of the non-NULL values of an INT32 / INT64 column, wrapping modulo 2^64;
+ *                       INT64; NULL if the group has no non-NULL value
+ *     RJ_AGG_MIN / RJ_AGG_MAX  over the non-NULL values of an INT32 / INT64 / FP64 column; the
+ *                       column's type; NULL if the group has no non-NULL value
+ *   Grouping equality: two rows are in one group exactly when they tie on every key under
+ *   rj_debug_sort_key's encoding.  So a NULL equals a NULL, per column — (NULL, 1), (1, NULL) and
+ *   (NULL, NULL) are three groups —, -0.0 equals +0.0 and every NaN equals every other NaN.
+ *   Values: a key column holds the group's CANONICAL value, the decoding of the encoded key
+ *   (rj_debug_sort_key_value): the value itself for INT32 / INT64, +0.0 for either zero,
+ *   0x7ff8000000000000 for any NaN, NULL for the NULL group.  FP64 MIN / MAX order by the same
+ *   encoding — a NaN is above +inf — and return the canonical value too.  The result is therefore
+ *   one deterministic multiset whatever order the child's rows have.
+ *   Rows: one per group.  n_keys == 0 is the scalar aggregate, ONE group of all rows: over an empty
+ *   child it gives ONE row, the counts 0 and SUM / MIN / MAX NULL, as SQL does.  With keys an empty
+ *   child gives 0 rows with the declared column types and zero pages.  A node without any aggregate
+ *   is SELECT DISTINCT.
+ *   Order: the groups come out ordered by the keys under their flags, the first key most
+ *   significant, as RJ_NODE_SORT orders rows.  As for that kind the order is promised ONLY when the
+ *   node is the plan's root; below another node the result is an ordinary relation, and a parent of
+ *   any kind may use every column of it, as a key too.
+ *   RJ_ERR_ARG: a key column or output column out of range; flag bits other than the two defined
+ *   ones; n_keys != 0 with a NULL pointer; an unknown function code; RJ_AGG_KEY on a column that is
+ *   not a key; RJ_AGG_COUNT_STAR with a column; a declared type other than the table above says.
+ *   RJ_ERR_UNSUPPORTED: a VARCHAR key; a VARCHAR aggregated column (it travels as a row id, so
+ *   MIN(title) is out of scope); SUM over an FP64 column (it depends on the order of the rows, which
+ *   no result of this library does); more than RJ_SORT_MAX_KEYS keys; more than 2^32 - 16 child rows.
+ *   The child may carry VARCHAR columns that the node does not name.  The node is checked before
+ *   its child's rows are looked at: an empty child does not hide an error.
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
  *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").                 */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
@@ -252,10 +301,11 @@ typedef enum rj_node_kind {
     RJ_NODE_FULL = 5,  /* inner join + unmatched rows of BOTH sides, padded  */
     RJ_NODE_AGG = 6,   /* GROUP BY left_attr of the one child `left`         */
     RJ_NODE_SELECT = 7, /* rows of the one child `left` that pass a predicate */
-    RJ_NODE_SORT = 8    /* ORDER BY / LIMIT / OFFSET over the one child `left` */
+    RJ_NODE_SORT = 8,   /* ORDER BY / LIMIT / OFFSET over the one child `left` */
+    RJ_NODE_GROUP = 9   /* GROUP BY any keys, or none, over the one child `left` */
 } rj_node_kind;
 
-/* Aggregate functions of RJ_NODE_AGG and the encoding of its out_idx values. */
+/* Aggregate functions of RJ_NODE_AGG / RJ_NODE_GROUP and the encoding of their out_idx values. */
 typedef enum rj_agg_func {
     RJ_AGG_KEY        = 0,
     RJ_AGG_COUNT_STAR = 1,
@@ -296,6 +346,10 @@ typedef struct rj_sort_key {
 #define RJ_SORT_KEYS(node) ((const rj_sort_key*)(uintptr_t)(node)->right_attr)
 #define RJ_SORT_LIMIT(node) ((node)->left_attr)
 #define RJ_SORT_OFFSET(node) ((node)->base_table_id)
+
+/* The keys of an RJ_NODE_GROUP node (`node`: a const rj_node*): rj_sort_key as above. */
+#define RJ_GROUP_N_KEYS(node) ((node)->right)
+#define RJ_GROUP_KEYS(node) ((const rj_sort_key*)(uintptr_t)(node)->right_attr)
 
 /* One Column (include/plan.h:60-100): `pages[i]` points at an 8192-byte Page. */
 typedef struct rj_column {
@@ -468,6 +522,12 @@ int rj_debug_parse_fp64(const char* field, uint64_t n, uint64_t* bits);
  * those bits.  null_digit: the NULL flag oriented by RJ_SORT_NULLS_FIRST; a NULL's key is 0.
  * Needs neither a context nor a GPU.  RJ_ERR_ARG: another type, other flag bits, a NULL pointer.  */
 int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, uint64_t* key, uint32_t* null_digit);
+/* Its inverse for a non-NULL key, run on the host (the kernels of RJ_NODE_GROUP share the code): *bits =
+ * the CANONICAL value bits of the values whose key under `flags` is `key` — an INT32's in the low
+ * word; +0.0 for the key of the zeros, 0x7ff8000000000000 for the key of the NaNs.  Needs neither a
+ * context nor a GPU (an INT32 key is its low 32 bits).  RJ_ERR_ARG: another type, other flag bits, a
+ * NULL pointer.                                                                                     */
+int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t* bits);
 uint64_t rj_table_num_rows(const rj_table* t);
 uint64_t rj_table_col_pages(const rj_table* t, uint64_t col);
 int      rj_table_copy_pages(rj_context* ctx, const rj_table* t, uint64_t col, void* const* dst, uint64_t n_dst);
@@ -520,16 +580,16 @@ void     rj_result_free(rj_result* r);
  * all ranks' shards is the input.  out[d] receives local device d's slice of the result (rows
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
- * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join or an
- * aggregation; others return RJ_ERR_UNSUPPORTED.                                                                       */
+ * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join, an
+ * aggregation, a selection, a sort or a grouping; others return RJ_ERR_UNSUPPORTED.                                                                       */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join, an aggregation, a selection or a sort is not shardable; the reason names the kind
- * (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG / RJ_NODE_SELECT /
- * RJ_NODE_SORT).                                                                                 */
+ * join, an aggregation, a selection, a sort or a grouping is not shardable; the reason names the
+ * kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG / RJ_NODE_SELECT /
+ * RJ_NODE_SORT / RJ_NODE_GROUP).                                                                                 */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

@@ -190,6 +190,13 @@ int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, u
     return RJ_OK;
 }
 
+int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t* bits) {
+    if (!bits || (flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST))) return RJ_ERR_ARG;
+    if (type != RJ_INT32 && type != RJ_INT64 && type != RJ_FP64) return RJ_ERR_ARG;
+    *bits = rj::sort_key_value(key, type == RJ_INT32 ? 4 : 8, type == RJ_FP64, (flags & RJ_SORT_DESC) != 0);
+    return RJ_OK;
+}
+
 int rj_debug_launch_log(rj_context* ctx, int on) {
     if (!ctx) return RJ_ERR_ARG;
     for (int l = 0; l < ctx->n_lanes(); ++l) {  // a group context: every device's launches

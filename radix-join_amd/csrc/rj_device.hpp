@@ -456,4 +456,27 @@ enum SortMode : int32_t {
     SORT_FLAG = 2    // the NULL flag of the row the id names (no keys travel: the column's last pass)
 };
 
+// ---- Grouping (RJ_NODE_GROUP): the rows ordered by the sort above, then cut into runs of equal keys.
+// The geometry is the sort's: a tile is GROUP_TILE consecutive positions of the sorted order, wave w
+// of a workgroup holds positions [w * GROUP_TILE / 4, (w + 1) * GROUP_TILE / 4) of it, 64 consecutive
+// ones per item, so that "previous row" is (wave, item, lane) order.  One 64-bit head mask per item
+// (bit l: position 64 * item + l starts a group); a position's group is the number of heads up to it.
+constexpr int GROUP_THREADS = 256;
+constexpr int GROUP_TILE = 4096;                            // positions per tile
+constexpr int GROUP_WAVES = GROUP_THREADS / 64;
+constexpr int GROUP_ITEMS = GROUP_TILE / GROUP_THREADS;     // items of 64 positions per wave
+static_assert(GROUP_TILE % GROUP_THREADS == 0 && GROUP_ITEMS <= 64, "whole items; a wave's masks sit in one lane each");
+
+// The accumulator arrays of one k_group_reduce launch, one entry per group; nullptr = not wanted.
+// mn / mx hold the ENCODED value (sort_key_bits, ascending), so that they compare as unsigned numbers.
+struct GroupAcc {
+    unsigned long long* rows;  // COUNT(*)
+    unsigned long long* nn;    // non-NULL values of the column
+    unsigned long long* sum;   // their sum, wrapping
+    unsigned long long* mn;
+    unsigned long long* mx;
+};
+// how k_group_column turns an accumulator into a result column
+enum GroupDecode : int32_t { GROUP_RAW = 0, GROUP_KEY32 = 1, GROUP_KEY64 = 2, GROUP_KEYF64 = 3 };
+
 }  // namespace rj

@@ -365,6 +365,10 @@ class Exec {
             Rel child = node(n.left, nullptr, depth + 1);
             return sort(child, n, root_res);
         }
+        if (n.kind == RJ_NODE_GROUP) {
+            Rel child = node(n.left, nullptr, depth + 1);
+            return group(child, n, root_res);
+        }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
         Rel             r = node(n.right, nullptr, depth + 1);
@@ -1950,6 +1954,196 @@ class Exec {
         return emit_rows(child, n, perm, perm ? perm->as<uint32_t>() + begin : nullptr, count, root_res);
     }
 
+    // -------------------------------------------------------------------- grouping
+    // RJ_NODE_GROUP (semantics in rj.h): GROUP BY any number of INT32 / INT64 / FP64 keys, or none.  The
+    // rows are ordered by the keys as a sort orders them (sort_column, the last key first), which puts
+    // every group into one run of the permutation; k_group_heads marks where the runs begin, a scan
+    // numbers them, and k_group_reduce reduces one aggregated column per launch, run by run
+    // (rj_group.hip).  Host syncs: one per key column (its digit histograms) and one for the group
+    // count, which sizes the outputs.  Nothing is sized for a bound, nothing is attempted twice.
+    struct GroupCol {
+        bool want_nn = false, want_sum = false, want_mn = false, want_mx = false;
+        BufP nn, sum, mn, mx;
+    };
+    Rel group(Rel& child, const rj_node& n, Result* root_res) {
+        const size_t       cw = child.cols.size();
+        const uint64_t     n_keys = RJ_GROUP_N_KEYS(&n);
+        const rj_sort_key* keys = RJ_GROUP_KEYS(&n);
+        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "group: more than %d keys", SORT_MAX_KEYS);
+        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "group: %llu keys but a NULL key pointer", (unsigned long long)n_keys);
+        std::vector<int> key_cols;  // the distinct key columns, the first key's first
+        for (uint64_t k = 0; k < n_keys; ++k) {
+            if (keys[k].column < 0 || (uint64_t)keys[k].column >= cw) throw_fmt(RJ_ERR_ARG, "group: key column out of range");
+            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "group: unknown key flags %d", keys[k].flags);
+            if (child.cols[(size_t)keys[k].column].type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "group: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
+                                              "are not read here", keys[k].column);
+            if (std::find(key_cols.begin(), key_cols.end(), keys[k].column) == key_cols.end()) key_cols.push_back(keys[k].column);
+        }
+        struct Out {
+            uint32_t func;
+            int      col;
+        };
+        std::vector<Out>        outs;
+        std::map<int, GroupCol> agg;  // per distinct aggregated column
+        bool                    want_rows = false;
+        JoinSpec                js;  // (the declared types, for empty_rel)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint32_t func = RJ_AGG_FUNC(n.out_idx[k]);
+            const uint64_t col = RJ_AGG_COL(n.out_idx[k]);
+            if (func > RJ_AGG_MAX) throw_fmt(RJ_ERR_ARG, "group: unknown function code %u", func);
+            int32_t expect = RJ_INT64;
+            if (func == RJ_AGG_COUNT_STAR) {
+                if (col != 0) throw_fmt(RJ_ERR_ARG, "group: COUNT(*) takes no column");
+                want_rows = true;
+            } else {
+                if (col >= cw) throw_fmt(RJ_ERR_ARG, "group: output attr out of range");
+                const DCol& c = child.cols[col];
+                if (func == RJ_AGG_KEY) {
+                    if (std::find(key_cols.begin(), key_cols.end(), (int)col) == key_cols.end())
+                        throw_fmt(RJ_ERR_ARG, "group: RJ_AGG_KEY names child column %llu, which is not a key", (unsigned long long)col);
+                    expect = c.type;
+                } else {
+                    if (c.type == RJ_VARCHAR)
+                        throw_fmt(RJ_ERR_UNSUPPORTED, "group: aggregate over a VARCHAR column (child column %llu): a VARCHAR value "
+                                                      "travels as a row id, its pages are not read here", (unsigned long long)col);
+                    if (func == RJ_AGG_SUM && c.type == RJ_FP64)
+                        throw_fmt(RJ_ERR_UNSUPPORTED, "group: SUM over an FP64 column (child column %llu): a floating-point sum depends "
+                                                      "on the order of the rows", (unsigned long long)col);
+                    if (func == RJ_AGG_MIN || func == RJ_AGG_MAX) expect = c.type;
+                    GroupCol& g = agg[(int)col];
+                    g.want_nn = true;  // (COUNT itself, and what says whether SUM / MIN / MAX are NULL)
+                    g.want_sum = g.want_sum || func == RJ_AGG_SUM;
+                    g.want_mn = g.want_mn || func == RJ_AGG_MIN;
+                    g.want_mx = g.want_mx || func == RJ_AGG_MAX;
+                }
+            }
+            if (n.out_type[k] != expect) throw_fmt(RJ_ERR_ARG, "group: declared type differs from the function's result type");
+            outs.push_back(Out{func, (int)col});
+            js.out_type.push_back(n.out_type[k]);
+        }
+        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        if (child.n == 0 && n_keys) return empty_rel(js, root_res);
+        const uint32_t rows = (uint32_t)child.n;
+
+        // ---- the order, the heads, the group count
+        BufP     perm, masks, tile_base;
+        uint32_t G = 1;
+        if (n_keys) {
+            for (uint64_t k = n_keys; k-- > 0;) {
+                bool shadowed = false;  // (as in sort(): behind the same column nothing is left to order)
+                for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
+                if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, rows, perm);
+            }
+            const uint32_t n_tiles = rows / GROUP_TILE + (rows % GROUP_TILE != 0);
+            masks = ctx->buf(((uint64_t)rows + 63) / 64 * 8);
+            tile_base = ctx->buf(((uint64_t)n_tiles + 1) * 4);
+            BufP tile_heads = ctx->buf((uint64_t)n_tiles * 4), total = ctx->buf(4);
+            for (size_t k = 0; k < key_cols.size(); ++k) {
+                const DCol& c = child.cols[(size_t)key_cols[k]];
+                launch_group_heads(L, c.ref(), perm ? perm->as<uint32_t>() : nullptr, rows, c.type == RJ_FP64, k == 0,
+                                   k + 1 == key_cols.size(), masks->as<unsigned long long>(), tile_heads->as<uint32_t>());
+            }
+            launch_group_scan(L, tile_heads->as<uint32_t>(), rows, tile_base->as<uint32_t>(), total->as<uint32_t>());
+            try {
+                RJ_HIP(hipMemcpyAsync(&G, total->p, 4, hipMemcpyDeviceToHost, ctx->stream));
+                ctx->sync();
+            } catch (...) {
+                (void)hipStreamSynchronize(ctx->stream);  // `G` is the end of a copy that may still be queued
+                throw;
+            }
+            if (G == 0 || G > rows) throw_fmt(RJ_ERR_DEVICE, "group: %u groups out of %u rows", G, rows);
+        }
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] group rows=%u keys=%llu groups=%u permuted=%d columns=%zu\n", rows, (unsigned long long)n_keys, G,
+                    perm ? 1 : 0, agg.size());
+        const uint32_t*           dperm = perm ? perm->as<uint32_t>() : nullptr;
+        const unsigned long long* dmasks = masks ? masks->as<unsigned long long>() : nullptr;
+        const uint32_t*           dbase = tile_base ? tile_base->as<uint32_t>() : nullptr;
+
+        // ---- the keys that are output: one array per distinct column
+        std::map<int, DCol> key_out;
+        for (const Out& o : outs) {
+            if (o.func != RJ_AGG_KEY || key_out.count(o.col)) continue;
+            const DCol& c = child.cols[(size_t)o.col];
+            DCol        d;
+            d.type = c.type;
+            d.kind = COL_DENSE;
+            d.width = c.width;
+            d.hold = ctx->buf((uint64_t)G * d.width);
+            d.ptr = d.hold->as<uint8_t>();
+            if (c.valid) {
+                d.hold_valid = ctx->buf(G);
+                d.valid = d.hold_valid->as<uint8_t>();
+            }
+            launch_group_keys(L, c.ref(), dperm, rows, c.type == RJ_FP64, dmasks, dbase, G, d.hold->as<uint8_t>(),
+                              d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
+            key_out[o.col] = d;
+        }
+
+        // ---- the reductions: one launch per distinct aggregated column, the first of which counts the rows too
+        const uint32_t max_grid = ctx->tune.group_grid > 0 ? (uint32_t)ctx->tune.group_grid : (uint32_t)ctx->compute_units() * 8u;
+        BufP           rows_acc = want_rows ? ctx->buf((uint64_t)G * 8) : BufP();
+        bool           rows_done = !want_rows;
+        auto           ull = [](const BufP& b) { return b ? b->as<unsigned long long>() : nullptr; };
+        for (auto& kv : agg) {
+            const DCol& c = child.cols[(size_t)kv.first];
+            GroupCol&   g = kv.second;
+            if (g.want_nn) g.nn = ctx->buf((uint64_t)G * 8);
+            if (g.want_sum) g.sum = ctx->buf((uint64_t)G * 8);
+            if (g.want_mn) g.mn = ctx->buf((uint64_t)G * 8);
+            if (g.want_mx) g.mx = ctx->buf((uint64_t)G * 8);
+            const GroupAcc acc{rows_done ? nullptr : ull(rows_acc), ull(g.nn), ull(g.sum), ull(g.mn), ull(g.mx)};
+            const ColRef   ref = c.ref();
+            launch_group_reduce(L, &ref, dperm, rows, c.type == RJ_FP64, dmasks, dbase, G, acc, max_grid);
+            rows_done = true;
+        }
+        if (!rows_done) {
+            const GroupAcc acc{ull(rows_acc), nullptr, nullptr, nullptr, nullptr};
+            launch_group_reduce(L, nullptr, dperm, rows, false, dmasks, dbase, G, acc, max_grid);
+        }
+
+        // ---- the output columns
+        Rel out;
+        out.n = G;
+        for (size_t k = 0; k < outs.size(); ++k) {
+            const Out& o = outs[k];
+            if (o.func == RJ_AGG_KEY) {
+                out.cols.push_back(key_out.at(o.col));
+                continue;
+            }
+            DCol d;
+            d.type = js.out_type[k];
+            d.kind = COL_DENSE;
+            d.width = d.type == RJ_INT32 ? 4 : 8;
+            if (o.func == RJ_AGG_COUNT_STAR) {
+                d.hold = rows_acc;
+            } else if (o.func == RJ_AGG_COUNT) {
+                d.hold = agg.at(o.col).nn;
+            } else {
+                const GroupCol& g = agg.at(o.col);
+                const DCol&     c = child.cols[(size_t)o.col];
+                const BufP&     acc = o.func == RJ_AGG_SUM ? g.sum : (o.func == RJ_AGG_MIN ? g.mn : g.mx);
+                // NULL where the group has no non-NULL value: a nullable column, or the one row over no rows
+                const bool nullable = c.valid != nullptr || rows == 0;
+                const int  decode = o.func == RJ_AGG_SUM ? GROUP_RAW : (c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64));
+                if (decode == GROUP_RAW && !nullable) {
+                    d.hold = acc;
+                } else {
+                    d.hold = ctx->buf((uint64_t)G * d.width);
+                    if (nullable) d.hold_valid = ctx->buf(G);
+                    launch_group_column(L, acc->as<unsigned long long>(), nullable ? g.nn->as<unsigned long long>() : nullptr, G, decode,
+                                        d.width, d.hold->as<uint8_t>(), d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
+                }
+            }
+            d.ptr = d.hold->as<uint8_t>();
+            d.valid = d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr;
+            out.cols.push_back(d);
+        }
+        if (root_res) rel_to_result(out, *root_res);
+        return out;
+    }
+
     // a fixed-width column (paged, or dense with or without validity) as a root result column: Page
     // images encoded on the device
     ResultColumn col_to_result(const DCol& d, uint64_t rows) {
@@ -2459,6 +2653,8 @@ class ShardedExec {
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: selection (RJ_NODE_SELECT) nodes run on one device");
         if (n.kind == RJ_NODE_SORT)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: sort (RJ_NODE_SORT) nodes run on one device");
+        if (n.kind == RJ_NODE_GROUP)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: grouping (RJ_NODE_GROUP) nodes run on one device");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -2858,6 +3054,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "a sort node (RJ_NODE_SORT) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_GROUP) {
+        if (why) *why = "a grouping node (RJ_NODE_GROUP) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -2936,6 +3136,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
                   "rj_execute_sharded: the plan holds a selection (RJ_NODE_SELECT) node; selections run on one device");
     if (n.kind == RJ_NODE_SORT)
         throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds a sort (RJ_NODE_SORT) node; sorts run on one device");
+    if (n.kind == RJ_NODE_GROUP)
+        throw_fmt(RJ_ERR_UNSUPPORTED,
+                  "rj_execute_sharded: the plan holds a grouping (RJ_NODE_GROUP) node; groupings run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

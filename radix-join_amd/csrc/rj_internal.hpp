@@ -228,6 +228,8 @@ struct Tuning {
                           // every column is gathered afterwards (k_gather)
     int fold_owner = 1;   // RJ_TUNE_FOLD_OWNER: a sharded join's stage A partitions by (owner rank, first local digit)
                           // in one pass; 0: by owner rank only (stage B then runs one more pass)
+    int group_grid = 0;   // RJ_TUNE_GROUP_GRID: cap on the workgroups of k_group_reduce, so that a small input walks several
+                          // tiles per workgroup (0 = 8 per compute unit)
     int exchange_timeout_ms = 120000;  // RJ_EXCHANGE_TIMEOUT_MS: bound on every wait of the exchange step of a
                                        // sharded join (communicator bring-up, count gathers, the all-to-all)
     int bringup_timeout_ms = 0;        // RJ_BRINGUP_TIMEOUT_MS: its own bound for the bring-up (0: the same) — in a

@@ -198,6 +198,31 @@ void launch_sort_scatter(const Launch& L, int mode, const uint8_t* keys_in, cons
 // out[i] = base + i, i < n
 void launch_sort_iota(const Launch& L, uint32_t* out, uint32_t base, uint32_t n);
 
+// ---- grouping (RJ_NODE_GROUP): runs of equal keys in the order the sort left, tiles of GROUP_TILE
+// positions (rj_device.hpp).  perm: row i of that order = row perm[i] (nullptr = i); masks: one 64-bit
+// head mask per 64 positions (ceil(n_rows / 64)); n_tiles = ceil(n_rows / GROUP_TILE) everywhere.
+// One key column: heads where it changes.  first: the masks are written, else OR-ed into; last:
+// tile_heads[n_tiles] = heads per tile.
+void launch_group_heads(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, bool f64, bool first, bool last,
+                        unsigned long long* masks, uint32_t* tile_heads);
+// tile_base[n_tiles + 1] = exclusive scan of tile_heads, *total = the group count
+void launch_group_scan(const Launch& L, const uint32_t* tile_heads, uint32_t n_rows, uint32_t* tile_base, uint32_t* total);
+// out[g] (col.width bytes) = the canonical key value of group g, out_valid[g] (optional) = 0 for the NULL group
+void launch_group_keys(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, bool f64,
+                       const unsigned long long* masks, const uint32_t* tile_base, uint32_t n_groups, uint8_t* out, uint8_t* out_valid);
+// One aggregated column (col == nullptr: none, COUNT(*) only) -> the arrays of `acc`, one entry per
+// group, every entry written whatever the memory held (k_group_init, then k_group_reduce on at most
+// max_grid workgroups).  masks == tile_base == perm == nullptr: the scalar aggregate, one group of all
+// rows (n_groups = 1; the kernel's variant without heads) — also over n_rows = 0, where the identities
+// are the result.
+void launch_group_reduce(const Launch& L, const ColRef* col, const uint32_t* perm, uint32_t n_rows, bool f64,
+                         const unsigned long long* masks, const uint32_t* tile_base, uint32_t n_groups, const GroupAcc& acc,
+                         uint32_t max_grid);
+// an accumulator array as a result column of `width` bytes: decode = GroupDecode; validity bytes
+// nn[i] != 0 (dst_valid optional; nn == nullptr: all valid), the value of a NULL is 0
+void launch_group_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int decode, int width,
+                         uint8_t* dst, uint8_t* dst_valid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

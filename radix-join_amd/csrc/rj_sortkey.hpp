@@ -1,5 +1,6 @@
-// rj_sortkey.hpp — the order-preserving key encoding of RJ_NODE_SORT, one function for the sort
-// kernels (k_sort_encode) and the host (rj_debug_sort_key, which the CPU tests pin it through).
+// rj_sortkey.hpp — the order-preserving key encoding of RJ_NODE_SORT and RJ_NODE_GROUP and its
+// inverse, one function each for the kernels (k_sort_encode, k_group_*) and the host
+// (rj_debug_sort_key / rj_debug_sort_key_value, which the CPU tests pin them through).
 #pragma once
 #include <stdint.h>
 
@@ -27,6 +28,20 @@ __host__ __device__ inline uint64_t sort_key_bits(uint64_t bits, int width, bool
         k = bits ^ 0x8000000000000000ull;
     }
     return desc ? ~k : k;
+}
+
+// The inverse of sort_key_bits for a non-NULL key: the canonical value bits of every value that has
+// this key (an INT32's in the low word).  For INT32 / INT64 that is the value itself; for a double
+// +0.0 for either zero and 0x7ff8000000000000 for any NaN, every other value its own bits.  A grouping
+// (RJ_NODE_GROUP) outputs its keys, and decodes the unsigned minima / maxima it keeps, through it.
+__host__ __device__ inline uint64_t sort_key_value(uint64_t key, int width, bool f64, bool desc) {
+    if (width == 4) {
+        const uint32_t k = desc ? ~(uint32_t)key : (uint32_t)key;
+        return k ^ 0x80000000u;
+    }
+    const uint64_t k = desc ? ~key : key;
+    if (f64) return k ^ ((k >> 63) ? 0x8000000000000000ull : ~0ull);
+    return k ^ 0x8000000000000000ull;
 }
 
 // The digit above the value bits of a nullable column: NULLs last unless nulls_first.

@@ -127,6 +127,7 @@ EXPORTS = [
     "rj_table_from_csv",
     "rj_debug_parse_fp64",
     "rj_debug_sort_key",
+    "rj_debug_sort_key_value",
     "rj_table_num_rows",
     "rj_table_col_pages",
     "rj_table_copy_pages",
@@ -626,6 +627,19 @@ def sort_key(dtype: int, flags: int, bits: int, is_null: bool = False):
     if rc != 0:
         raise RjError(rc, "rj_debug_sort_key: bad type or flags")
     return int(nd.value), int(key.value)
+
+
+def sort_key_value(dtype: int, flags: int, key: int) -> int:
+    """rj_debug_sort_key_value: the canonical value bits (unsigned, an INT32's in the low word) of the
+    values whose key under `flags` is `key` — the inverse of sort_key for a non-NULL value."""
+    L = load()
+    L.rj_debug_sort_key_value.restype = C.c_int
+    L.rj_debug_sort_key_value.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64)]
+    bits = C.c_uint64(0)
+    rc = L.rj_debug_sort_key_value(dtype, flags, key, C.byref(bits))
+    if rc != 0:
+        raise RjError(rc, "rj_debug_sort_key_value: bad type or flags")
+    return int(bits.value)
 
 
 def make_comm_id() -> bytes:

@@ -51,6 +51,7 @@ class JoinNode:
 # rj_node_kind (include/rj.h)
 NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG, NODE_SELECT = 0, 1, 2, 3, 4, 5, 6, 7
 NODE_SORT = 8
+NODE_GROUP = 9
 # rj_sort_key::flags, RJ_SORT_NO_LIMIT
 SORT_DESC, SORT_NULLS_FIRST = 1, 2
 SORT_NO_LIMIT = 2**64 - 1
@@ -143,6 +144,17 @@ class SortNode:
 
 
 @dataclass
+class GroupNode:
+    """Grouping (kind NODE_GROUP): GROUP BY keys, or with keys == [] the scalar aggregate over all
+    rows.  keys = [(column, flags)] as a SortNode's; the PlanNode's output_attrs hold
+    (RJ_AGG_OUT(func, column), result type) pairs as an AggNode's, over any number of columns; AGG_KEY
+    may name any key column.  The groups come out in the order of the keys, promised only at the
+    plan's root (include/rj.h)."""
+    child: int
+    keys: list
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -199,6 +211,13 @@ class Plan:
         """ORDER BY / LIMIT / OFFSET: rows [offset, offset + limit) of the child ordered by `keys`
         (see SortNode)."""
         self.nodes.append(PlanNode(SortNode(child, [tuple(k) for k in keys], limit, offset), list(output_attrs)))
+        return len(self.nodes) - 1
+
+    def new_group_node(self, child, keys, outputs):
+        """GROUP BY keys ([(column, flags)], [] = one group of all rows).  outputs = [(func, column,
+        result type)] as for new_agg_node."""
+        oa = [(agg_out(f, c), t) for f, c, t in outputs]
+        self.nodes.append(PlanNode(GroupNode(child, [tuple(k) for k in keys]), oa))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -441,6 +460,16 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.right_attr = C.addressof(karr) if nk else 0
             nd.left_attr = SORT_NO_LIMIT if n.data.limit is None else int(n.data.limit)
             nd.base_table_id = int(n.data.offset)
+        elif isinstance(n.data, GroupNode):
+            nk = len(n.data.keys)
+            karr = (rj_sort_key * max(1, nk))()
+            for j, (col, flags) in enumerate(n.data.keys):
+                karr[j].column, karr[j].flags = int(col), int(flags)
+            keep.append(karr)
+            nd.kind = NODE_GROUP
+            nd.left = n.data.child
+            nd.right = nk  # RJ_GROUP_N_KEYS / RJ_GROUP_KEYS: the struct cannot grow
+            nd.right_attr = C.addressof(karr) if nk else 0
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
