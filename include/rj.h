@@ -291,6 +291,63 @@ typedef enum rj_status {
  *   its child's rows are looked at: an empty child does not hide an error.
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
+ *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Window functions (ROW_NUMBER / RANK / DENSE_RANK and COUNT / SUM / MIN / MAX ... OVER (PARTITION BY
+ * ... ORDER BY ...); no reference counterpart).
+ * RJ_NODE_WINDOW has ONE child, `left`; `build_left` and `base_table_id` are ignored.
+ *   Keys: rj_node cannot grow, so RJ_WINDOW_N_KEYS(node) = `right` is the total number of keys
+ *   (0 .. RJ_SORT_MAX_KEYS), RJ_WINDOW_KEYS(node) = `right_attr` a `const rj_sort_key*` that stays
+ *   valid during the call, and RJ_WINDOW_N_PART(node) = `left_attr` says how many of them, the first
+ *   ones, are PARTITION BY keys; the rest are ORDER BY keys.  rj_sort_key::column indexes the CHILD's
+ *   outputs and may repeat, in one list or in both.
+ *   Outputs: out_idx[k] = RJ_WIN_OUT(func, column) (the bit layout of RJ_AGG_OUT), out_type[k] = the
+ *   declared RESULT type; any number of outputs over any number of distinct columns:
+ *     RJ_WIN_COL         a child column passes through: out_idx[k] is then a plain column index, as a
+ *                        selection's; the child column's type, bits and nullability; a VARCHAR column
+ *                        passes through as row ids
+ *     RJ_WIN_ROW_NUMBER  1 + the rows of the partition in front of this one in the sorted order
+ *     RJ_WIN_RANK        1 + the rows of the partition in front of this row's first peer
+ *     RJ_WIN_DENSE_RANK  the number of peer groups of the partition up to and including this row's
+ *                        (these three: column must be 0; INT64; never NULL)
+ *     RJ_WIN_COUNT_STAR  rows of the frame; column must be 0; INT64
+ *     RJ_WIN_COUNT       non-NULL values of an INT32 / INT64 / FP64 column in the frame; INT64
+ *     RJ_WIN_SUM         sum of the non-NULL values of an INT32 / INT64 column in the frame, wrapping
+ *                        modulo 2^64; INT64; NULL if the frame has no non-NULL value
+ *     RJ_WIN_MIN / RJ_WIN_MAX  over the non-NULL values of an INT32 / INT64 / FP64 column in the frame;
+ *                        the column's type; NULL if the frame has none
+ *   Equality and order: two rows are in one partition exactly when they tie on every partition key
+ *   under rj_debug_sort_key's encoding — the grouping equalities of RJ_NODE_GROUP: NULL = NULL per
+ *   column, -0.0 = +0.0, NaN = NaN.  Inside a partition the rows are ordered by the order keys under
+ *   their flags, as RJ_NODE_SORT orders them.  Two rows of a partition are PEERS when they tie on
+ *   every order key; with no order key all rows of a partition are peers.  The flags of a partition
+ *   key only say where its partitions go in the result's order.
+ *   Frame: SQL's default and no other.  With order keys it is RANGE BETWEEN UNBOUNDED PRECEDING AND
+ *   CURRENT ROW: every row of the partition up to and INCLUDING the current row's last peer.  Without
+ *   order keys it is the whole partition.  Every aggregate value therefore depends only on the
+ *   multiset of child rows, never on their order on the device.  A result is NULL where the frame
+ *   has no non-NULL value, which the count decides, never a sentinel.  FP64 MIN / MAX order by the
+ *   sort encoding — a NaN is above +inf — and return the canonical value (rj_debug_sort_key_value),
+ *   as RJ_NODE_GROUP does.
+ *   Rows: exactly the child's rows, each once, ordered by (partition keys, order keys), the first key
+ *   most significant.  As for RJ_NODE_SORT and RJ_NODE_GROUP the order is promised ONLY when the node
+ *   is the plan's root.  Ties are stable with respect to the child's order on the device: for a
+ *   SCAN child ROW_NUMBER among peers and the result order are fully determined, for any other child
+ *   which peer gets which row number is unspecified.  An empty child gives 0 rows with the declared
+ *   types and zero pages.  With no key at all there is one partition of all rows, in the child's
+ *   order, and nothing is sorted.
+ *   RJ_ERR_ARG: n_part > n_keys; a key or output column out of range; flag bits other than the two
+ *   defined ones; n_keys != 0 with a NULL pointer; a function code above RJ_WIN_MAX; a ranking
+ *   function or RJ_WIN_COUNT_STAR with a column other than 0; a declared type other than the table
+ *   above says (for RJ_WIN_COL the child column's type).
+ *   RJ_ERR_UNSUPPORTED: a VARCHAR key; a VARCHAR column under a function (it travels as a row id);
+ *   SUM over an FP64 column (it depends on the order of the rows); more than RJ_SORT_MAX_KEYS keys in
+ *   total; more than 2^32 - 16 child rows.  The node is checked before its child's rows are looked
+ *   at: an empty child does not hide an error.
+ *   Out of scope: ROWS and every explicit frame; LAG / LEAD / FIRST_VALUE / NTILE; VARCHAR anywhere but
+ *   passing through; sharding.
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
  *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").                 */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
@@ -302,7 +359,8 @@ typedef enum rj_node_kind {
     RJ_NODE_AGG = 6,   /* GROUP BY left_attr of the one child `left`         */
     RJ_NODE_SELECT = 7, /* rows of the one child `left` that pass a predicate */
     RJ_NODE_SORT = 8,   /* ORDER BY / LIMIT / OFFSET over the one child `left` */
-    RJ_NODE_GROUP = 9   /* GROUP BY any keys, or none, over the one child `left` */
+    RJ_NODE_GROUP = 9,  /* GROUP BY any keys, or none, over the one child `left` */
+    RJ_NODE_WINDOW = 10 /* window functions OVER (PARTITION BY / ORDER BY) over the one child `left` */
 } rj_node_kind;
 
 /* Aggregate functions of RJ_NODE_AGG / RJ_NODE_GROUP and the encoding of their out_idx values. */
@@ -350,6 +408,28 @@ typedef struct rj_sort_key {
 /* The keys of an RJ_NODE_GROUP node (`node`: a const rj_node*): rj_sort_key as above. */
 #define RJ_GROUP_N_KEYS(node) ((node)->right)
 #define RJ_GROUP_KEYS(node) ((const rj_sort_key*)(uintptr_t)(node)->right_attr)
+
+/* The keys of an RJ_NODE_WINDOW node (`node`: a const rj_node*): rj_sort_key as above; the first
+ * RJ_WINDOW_N_PART of the RJ_WINDOW_N_KEYS keys are PARTITION BY keys, the rest ORDER BY keys. */
+#define RJ_WINDOW_N_KEYS(node) ((node)->right)
+#define RJ_WINDOW_KEYS(node) ((const rj_sort_key*)(uintptr_t)(node)->right_attr)
+#define RJ_WINDOW_N_PART(node) ((node)->left_attr)
+
+/* Functions of RJ_NODE_WINDOW and the encoding of its out_idx values (the bit layout of RJ_AGG_OUT). */
+typedef enum rj_win_func {
+    RJ_WIN_COL        = 0, /* a child column passes through */
+    RJ_WIN_ROW_NUMBER = 1,
+    RJ_WIN_RANK       = 2,
+    RJ_WIN_DENSE_RANK = 3,
+    RJ_WIN_COUNT_STAR = 4,
+    RJ_WIN_COUNT      = 5,
+    RJ_WIN_SUM        = 6,
+    RJ_WIN_MIN        = 7,
+    RJ_WIN_MAX        = 8
+} rj_win_func;
+#define RJ_WIN_OUT(func, col) (((uint64_t)(func) << 56) | (uint64_t)(col))
+#define RJ_WIN_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
+#define RJ_WIN_COL(x) ((uint64_t)(x) & 0x00ffffffffffffffull)
 
 /* One Column (include/plan.h:60-100): `pages[i]` points at an 8192-byte Page. */
 typedef struct rj_column {
@@ -581,15 +661,15 @@ void     rj_result_free(rj_result* r);
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
  * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join, an
- * aggregation, a selection, a sort or a grouping; others return RJ_ERR_UNSUPPORTED.                                                                       */
+ * aggregation, a selection, a sort, a grouping or a window node; others return RJ_ERR_UNSUPPORTED.                                                                       */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join, an aggregation, a selection, a sort or a grouping is not shardable; the reason names the
- * kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG / RJ_NODE_SELECT /
- * RJ_NODE_SORT / RJ_NODE_GROUP).                                                                                 */
+ * join, an aggregation, a selection, a sort, a grouping or a window node is not shardable; the reason
+ * names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG /
+ * RJ_NODE_SELECT / RJ_NODE_SORT / RJ_NODE_GROUP / RJ_NODE_WINDOW).                                                                                 */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

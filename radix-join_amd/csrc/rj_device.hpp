@@ -479,4 +479,47 @@ struct GroupAcc {
 // how k_group_column turns an accumulator into a result column
 enum GroupDecode : int32_t { GROUP_RAW = 0, GROUP_KEY32 = 1, GROUP_KEY64 = 2, GROUP_KEYF64 = 3 };
 
+// ---- Window functions (RJ_NODE_WINDOW): the rows ordered by (partition keys, order keys) as above, and
+// TWO head masks in the grouping's layout: P marks where the partitions begin, Q (a superset) where
+// the peer groups begin.  The kernels work QUARTER by quarter — the positions of one wave of a tile,
+// WIN_ITEMS mask words — and no wave waits for another: what a quarter needs from outside is one entry
+// per quarter, computed by a launch of its own (rj_window.hip).
+constexpr int WIN_QUARTER = GROUP_TILE / GROUP_WAVES;  // positions per wave
+constexpr int WIN_ITEMS = GROUP_ITEMS;                 // items of 64 positions per quarter
+constexpr int WIN_CARRY_THREADS = 1024;                // threads of the one workgroup that scans the quarters' entries
+static_assert(WIN_QUARTER == 64 * WIN_ITEMS && WIN_ITEMS <= 64, "a quarter's masks sit in one lane each");
+
+// One entry per quarter.  k_win_marks writes the quarter's own summary, k_win_carry turns it in place
+// into what the quarter needs from outside (positions as 1 + position, 0 = none):
+struct WinMarks {
+    uint32_t* last_p;  // the quarter's last P head          -> the last P head in front of the quarter
+    uint32_t* last_q;  // ... last Q head                     -> the last Q head in front of the quarter
+    uint32_t* dense;   // Q heads at or behind its last P head (all, if it has none) -> ... in front of the quarter
+    uint32_t* next_q;  // position of its first Q head, n_rows = none -> of the first Q head behind the quarter
+};
+// What k_win_ranks writes, one entry per position of the order; nullptr = not wanted.
+struct WinRanks {
+    unsigned long long* row_number;
+    unsigned long long* rank;
+    unsigned long long* dense_rank;
+    unsigned long long* count_star;  // rows of the frame
+    uint32_t*           peer_end;    // position of the row's last peer: where its frame ends
+};
+// One entry per quarter: k_win_tails writes the accumulators of the quarter's positions from its last
+// P head on (head = 1 if it has one), k_win_tail_carry turns them in place into the quarter's carry-in.
+struct WinTails {
+    uint32_t*           head;
+    uint32_t*           nn;
+    unsigned long long* sum;
+    unsigned long long* mn;
+    unsigned long long* mx;
+};
+// The segmented inclusive scan of one value column, one entry per position; nullptr = not wanted.
+struct WinScan {
+    uint32_t*           nn;
+    unsigned long long* sum;
+    unsigned long long* mn;
+    unsigned long long* mx;
+};
+
 }  // namespace rj

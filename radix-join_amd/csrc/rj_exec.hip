@@ -369,6 +369,10 @@ class Exec {
             Rel child = node(n.left, nullptr, depth + 1);
             return group(child, n, root_res);
         }
+        if (n.kind == RJ_NODE_WINDOW) {
+            Rel child = node(n.left, nullptr, depth + 1);
+            return window(child, n, root_res);
+        }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
         Rel             r = node(n.right, nullptr, depth + 1);
@@ -2144,6 +2148,204 @@ class Exec {
         return out;
     }
 
+    // ---------------------------------------------------------------------- window
+    // RJ_NODE_WINDOW (semantics in rj.h): ROW_NUMBER / RANK / DENSE_RANK and COUNT / SUM / MIN / MAX OVER
+    // (PARTITION BY ... ORDER BY ...).  The rows are ordered by (partition keys, order keys) as a sort
+    // orders them (sort_column, the last key first); k_group_heads marks where the partitions begin (P)
+    // and, OR-ed over the order keys into a copy of P, where the peer groups begin (Q); the k_win_*
+    // kernels (rj_window.hip) turn the two masks into the ranks and every row's peer end, and scan one
+    // value column per set of launches.  The passed-through columns are gathered through the permutation
+    // as a sort's (emit_rows).  Host syncs: those of sort_column only — the result has the child's rows.
+    struct WinCol {
+        bool want_sum = false, want_mn = false, want_mx = false;
+        BufP nn, sum, mn, mx;
+    };
+    Rel window(Rel& child, const rj_node& n, Result* root_res) {
+        const size_t       cw = child.cols.size();
+        const uint64_t     n_keys = RJ_WINDOW_N_KEYS(&n), n_part = RJ_WINDOW_N_PART(&n);
+        const rj_sort_key* keys = RJ_WINDOW_KEYS(&n);
+        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "window: more than %d keys", SORT_MAX_KEYS);
+        if (n_part > n_keys)
+            throw_fmt(RJ_ERR_ARG, "window: %llu partition keys out of %llu keys", (unsigned long long)n_part, (unsigned long long)n_keys);
+        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "window: %llu keys but a NULL key pointer", (unsigned long long)n_keys);
+        std::vector<int> part_cols, order_cols;  // the distinct key columns; an order key that is a partition key too orders nothing
+        for (uint64_t k = 0; k < n_keys; ++k) {
+            if (keys[k].column < 0 || (uint64_t)keys[k].column >= cw) throw_fmt(RJ_ERR_ARG, "window: key column out of range");
+            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "window: unknown key flags %d", keys[k].flags);
+            if (child.cols[(size_t)keys[k].column].type == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "window: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
+                                              "are not read here", keys[k].column);
+            const bool in_part = std::find(part_cols.begin(), part_cols.end(), keys[k].column) != part_cols.end();
+            if (k < n_part) {
+                if (!in_part) part_cols.push_back(keys[k].column);
+            } else if (!in_part && std::find(order_cols.begin(), order_cols.end(), keys[k].column) == order_cols.end()) {
+                order_cols.push_back(keys[k].column);
+            }
+        }
+        struct Out {
+            uint32_t func;
+            int      col;
+        };
+        std::vector<Out>      outs;
+        std::map<int, WinCol> agg;  // per distinct value column
+        std::vector<uint64_t> pass;  // the distinct passed-through columns
+        bool                  want[RJ_WIN_COUNT_STAR + 1] = {false, false, false, false, false};
+        JoinSpec              js;  // (the declared types, for empty_rel)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint32_t func = RJ_WIN_FUNC(n.out_idx[k]);
+            const uint64_t col = RJ_WIN_COL(n.out_idx[k]);
+            if (func > RJ_WIN_MAX) throw_fmt(RJ_ERR_ARG, "window: unknown function code %u", func);
+            int32_t expect = RJ_INT64;
+            if (func >= RJ_WIN_ROW_NUMBER && func <= RJ_WIN_COUNT_STAR) {
+                if (col != 0)
+                    throw_fmt(RJ_ERR_ARG, "window: %s takes no column", func == RJ_WIN_COUNT_STAR ? "COUNT(*)" : "a ranking function");
+                want[func] = true;
+            } else {
+                if (col >= cw) throw_fmt(RJ_ERR_ARG, "window: output attr out of range");
+                const DCol& c = child.cols[col];
+                if (func == RJ_WIN_COL) {
+                    expect = c.type;
+                    if (std::find(pass.begin(), pass.end(), col) == pass.end()) pass.push_back(col);
+                } else {
+                    if (c.type == RJ_VARCHAR)
+                        throw_fmt(RJ_ERR_UNSUPPORTED, "window: function over a VARCHAR column (child column %llu): a VARCHAR value "
+                                                      "travels as a row id, its pages are not read here", (unsigned long long)col);
+                    if (func == RJ_WIN_SUM && c.type == RJ_FP64)
+                        throw_fmt(RJ_ERR_UNSUPPORTED, "window: SUM over an FP64 column (child column %llu): a floating-point sum depends "
+                                                      "on the order of the rows", (unsigned long long)col);
+                    if (func == RJ_WIN_MIN || func == RJ_WIN_MAX) expect = c.type;
+                    WinCol& w = agg[(int)col];
+                    w.want_sum = w.want_sum || func == RJ_WIN_SUM;
+                    w.want_mn = w.want_mn || func == RJ_WIN_MIN;
+                    w.want_mx = w.want_mx || func == RJ_WIN_MAX;
+                }
+            }
+            if (n.out_type[k] != expect) throw_fmt(RJ_ERR_ARG, "window: declared type differs from the function's result type");
+            outs.push_back(Out{func, (int)col});
+            js.out_type.push_back(n.out_type[k]);
+        }
+        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        if (child.n == 0) return empty_rel(js, root_res);
+        const uint32_t rows = (uint32_t)child.n;
+
+        // ---- the order
+        BufP perm;
+        for (uint64_t k = n_keys; k-- > 0;) {
+            bool shadowed = false;  // (as in sort(): behind the same column nothing is left to order)
+            for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
+            if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, rows, perm);
+        }
+        const uint32_t* dperm = perm ? perm->as<uint32_t>() : nullptr;
+        const bool      any_func = std::any_of(outs.begin(), outs.end(), [](const Out& o) { return o.func != RJ_WIN_COL; });
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] window rows=%u keys=%llu partition keys=%llu permuted=%d value columns=%zu\n", rows,
+                    (unsigned long long)n_keys, (unsigned long long)n_part, perm ? 1 : 0, agg.size());
+
+        // ---- the heads: P of the partitions, Q of the peer groups; the ranks and the peer ends
+        const uint32_t max_chunk = ctx->tune.win_grid > 0 ? (uint32_t)ctx->tune.win_grid : 0u;
+        const uint32_t n_quarters = rows / WIN_QUARTER + (rows % WIN_QUARTER != 0);
+        BufP           P, Q, rank_col[RJ_WIN_COUNT_STAR + 1], peer_end;
+        auto           ull = [](const BufP& b) { return b ? b->as<unsigned long long>() : nullptr; };
+        auto           u32 = [](const BufP& b) { return b ? b->as<uint32_t>() : nullptr; };
+        if (any_func) {
+            const uint64_t mask_bytes = ((uint64_t)rows + 63) / 64 * 8;
+            P = ctx->buf(mask_bytes);
+            if (part_cols.empty()) launch_win_one_head(L, ull(P), rows);
+            for (size_t k = 0; k < part_cols.size(); ++k) {
+                const DCol& c = child.cols[(size_t)part_cols[k]];
+                launch_group_heads(L, c.ref(), dperm, rows, c.type == RJ_FP64, k == 0, false, ull(P), nullptr);
+            }
+            Q = P;  // without order keys every row of a partition is a peer of every other
+            if (!order_cols.empty()) {
+                Q = ctx->buf(mask_bytes);
+                RJ_HIP(hipMemcpyAsync(Q->p, P->p, mask_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                for (int col : order_cols) {
+                    const DCol& c = child.cols[(size_t)col];
+                    launch_group_heads(L, c.ref(), dperm, rows, c.type == RJ_FP64, false, false, ull(Q), nullptr);
+                }
+            }
+            for (uint32_t f = RJ_WIN_ROW_NUMBER; f <= RJ_WIN_COUNT_STAR; ++f)
+                if (want[f]) rank_col[f] = ctx->buf((uint64_t)rows * 8);
+            if (!agg.empty()) peer_end = ctx->buf((uint64_t)rows * 4);
+            BufP           marks[4];
+            for (BufP& b : marks) b = ctx->buf((uint64_t)n_quarters * 4);
+            const WinMarks m{u32(marks[0]), u32(marks[1]), u32(marks[2]), u32(marks[3])};
+            const WinRanks r{ull(rank_col[RJ_WIN_ROW_NUMBER]), ull(rank_col[RJ_WIN_RANK]), ull(rank_col[RJ_WIN_DENSE_RANK]),
+                             ull(rank_col[RJ_WIN_COUNT_STAR]), u32(peer_end)};
+            launch_win_ranks(L, ull(P), ull(Q), rows, m, r, max_chunk);
+        }
+
+        // ---- the scans: one set of launches per distinct value column
+        for (auto& kv : agg) {
+            const DCol& c = child.cols[(size_t)kv.first];
+            WinCol&     w = kv.second;
+            w.nn = ctx->buf((uint64_t)rows * 4);  // (COUNT itself, and what says whether SUM / MIN / MAX are NULL)
+            if (w.want_sum) w.sum = ctx->buf((uint64_t)rows * 8);
+            if (w.want_mn) w.mn = ctx->buf((uint64_t)rows * 8);
+            if (w.want_mx) w.mx = ctx->buf((uint64_t)rows * 8);
+            BufP t_head = ctx->buf((uint64_t)n_quarters * 4), t_nn = ctx->buf((uint64_t)n_quarters * 4), t_sum = ctx->buf((uint64_t)n_quarters * 8),
+                 t_mn = ctx->buf((uint64_t)n_quarters * 8), t_mx = ctx->buf((uint64_t)n_quarters * 8);
+            const WinTails tails{u32(t_head), u32(t_nn), ull(t_sum), ull(t_mn), ull(t_mx)};
+            const WinScan  scan{u32(w.nn), ull(w.sum), ull(w.mn), ull(w.mx)};
+            launch_win_scan(L, c.ref(), dperm, rows, c.type == RJ_FP64, ull(P), tails, scan, max_chunk);
+        }
+
+        // ---- the passed-through columns, gathered once each
+        rj_node through = n;
+        through.n_out = pass.size();
+        through.out_idx = pass.data();
+        Result pass_res;
+        Rel    pass_rel = emit_rows(child, through, perm, dperm, rows, root_res ? &pass_res : nullptr);
+
+        // ---- the output columns
+        Rel out;
+        out.n = rows;
+        if (root_res) root_res->num_rows = rows;
+        std::map<uint64_t, DCol> made;  // a function column named several times is made once
+        for (size_t k = 0; k < outs.size(); ++k) {
+            const Out& o = outs[k];
+            if (o.func == RJ_WIN_COL) {
+                const size_t at = (size_t)(std::find(pass.begin(), pass.end(), (uint64_t)o.col) - pass.begin());
+                if (root_res)
+                    root_res->cols.push_back(pass_res.cols[at]);
+                else
+                    out.cols.push_back(pass_rel.cols[at]);
+                continue;
+            }
+            const uint64_t id = n.out_idx[k];
+            if (!made.count(id)) {
+                DCol d;
+                d.type = js.out_type[k];
+                d.kind = COL_DENSE;
+                d.width = d.type == RJ_INT32 ? 4 : 8;
+                if (o.func <= RJ_WIN_COUNT_STAR) {
+                    d.hold = rank_col[o.func];
+                } else {
+                    const WinCol& w = agg.at(o.col);
+                    const DCol&   c = child.cols[(size_t)o.col];
+                    const BufP&   src = o.func == RJ_WIN_SUM ? w.sum : (o.func == RJ_WIN_MIN ? w.mn : (o.func == RJ_WIN_MAX ? w.mx : BufP()));
+                    // NULL where the frame has no non-NULL value: only a nullable column's frames can
+                    const bool nullable = c.valid != nullptr && o.func != RJ_WIN_COUNT;
+                    const int  decode = o.func == RJ_WIN_SUM || o.func == RJ_WIN_COUNT
+                                            ? GROUP_RAW
+                                            : (c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64));
+                    d.hold = ctx->buf((uint64_t)rows * d.width);
+                    if (nullable) d.hold_valid = ctx->buf(rows);
+                    launch_win_column(L, ull(src), u32(w.nn), u32(peer_end), rows, decode, d.width, d.hold->as<uint8_t>(),
+                                      d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
+                }
+                d.ptr = d.hold->as<uint8_t>();
+                d.valid = d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr;
+                made[id] = d;
+            }
+            if (root_res)
+                root_res->cols.push_back(col_to_result(made.at(id), rows));
+            else
+                out.cols.push_back(made.at(id));
+        }
+        return out;
+    }
+
     // a fixed-width column (paged, or dense with or without validity) as a root result column: Page
     // images encoded on the device
     ResultColumn col_to_result(const DCol& d, uint64_t rows) {
@@ -2655,6 +2857,8 @@ class ShardedExec {
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: sort (RJ_NODE_SORT) nodes run on one device");
         if (n.kind == RJ_NODE_GROUP)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: grouping (RJ_NODE_GROUP) nodes run on one device");
+        if (n.kind == RJ_NODE_WINDOW)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: window (RJ_NODE_WINDOW) nodes run on one device");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -3058,6 +3262,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "a grouping node (RJ_NODE_GROUP) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_WINDOW) {
+        if (why) *why = "a window node (RJ_NODE_WINDOW) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -3139,6 +3347,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_GROUP)
         throw_fmt(RJ_ERR_UNSUPPORTED,
                   "rj_execute_sharded: the plan holds a grouping (RJ_NODE_GROUP) node; groupings run on one device");
+    if (n.kind == RJ_NODE_WINDOW)
+        throw_fmt(RJ_ERR_UNSUPPORTED,
+                  "rj_execute_sharded: the plan holds a window (RJ_NODE_WINDOW) node; window functions run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

@@ -230,6 +230,8 @@ struct Tuning {
                           // in one pass; 0: by owner rank only (stage B then runs one more pass)
     int group_grid = 0;   // RJ_TUNE_GROUP_GRID: cap on the workgroups of k_group_reduce, so that a small input walks several
                           // tiles per workgroup (0 = 8 per compute unit)
+    int win_grid = 0;     // RJ_TUNE_WIN_GRID: cap on the quarter entries k_win_carry / k_win_tail_carry take per step, so that a
+                          // small input takes several steps and carries from one to the next (0 = 1024, one per thread)
     int exchange_timeout_ms = 120000;  // RJ_EXCHANGE_TIMEOUT_MS: bound on every wait of the exchange step of a
                                        // sharded join (communicator bring-up, count gathers, the all-to-all)
     int bringup_timeout_ms = 0;        // RJ_BRINGUP_TIMEOUT_MS: its own bound for the bring-up (0: the same) — in a

@@ -223,6 +223,24 @@ void launch_group_reduce(const Launch& L, const ColRef* col, const uint32_t* per
 void launch_group_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int decode, int width,
                          uint8_t* dst, uint8_t* dst_valid);
 
+// ---- window functions (RJ_NODE_WINDOW): P / Q = the head masks of the partitions / the peer groups in
+// the grouping's layout, over the order the sort left; one entry per quarter of a tile in WinMarks / WinTails
+// (ceil(n_rows / WIN_QUARTER)); max_chunk: cap on the entries a carry kernel's workgroup takes per step
+// (0 = one per thread).
+// masks[0] = 1, every other word 0: one partition of all rows
+void launch_win_one_head(const Launch& L, unsigned long long* masks, uint32_t n_rows);
+// k_win_marks, k_win_carry, k_win_ranks: the arrays of `out` that are wanted
+void launch_win_ranks(const Launch& L, const unsigned long long* P, const unsigned long long* Q, uint32_t n_rows, const WinMarks& m,
+                      const WinRanks& out, uint32_t max_chunk);
+// k_win_tails, k_win_tail_carry, k_win_scan: the segmented inclusive scan of one value column over the
+// P segments -> the arrays of `out` that are wanted
+void launch_win_scan(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, bool f64, const unsigned long long* P,
+                     const WinTails& tails, const WinScan& out, uint32_t max_chunk);
+// row i of a result column of `width` bytes = src[peer_end[i]] (src == nullptr: the count nn[...]),
+// decode = GroupDecode; validity bytes nn[peer_end[i]] != 0 where dst_valid is given, the value of a NULL is 0
+void launch_win_column(const Launch& L, const unsigned long long* src, const uint32_t* nn, const uint32_t* peer_end, uint64_t n, int decode,
+                       int width, uint8_t* dst, uint8_t* dst_valid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

@@ -52,6 +52,7 @@ class JoinNode:
 NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG, NODE_SELECT = 0, 1, 2, 3, 4, 5, 6, 7
 NODE_SORT = 8
 NODE_GROUP = 9
+NODE_WINDOW = 10
 # rj_sort_key::flags, RJ_SORT_NO_LIMIT
 SORT_DESC, SORT_NULLS_FIRST = 1, 2
 SORT_NO_LIMIT = 2**64 - 1
@@ -68,6 +69,23 @@ def agg_func(x):
 
 
 def agg_col(x):
+    return int(x) & ((1 << 56) - 1)
+
+
+# rj_win_func and the RJ_WIN_OUT / RJ_WIN_FUNC / RJ_WIN_COL encoding of a window node's out_idx (the
+# bit layout of RJ_AGG_OUT)
+WIN_COL, WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX = range(9)
+
+
+def win_out(func, col):
+    return (int(func) << 56) | int(col)
+
+
+def win_func(x):
+    return int(x) >> 56
+
+
+def win_col(x):
     return int(x) & ((1 << 56) - 1)
 
 
@@ -155,6 +173,18 @@ class GroupNode:
 
 
 @dataclass
+class WindowNode:
+    """Window functions (kind NODE_WINDOW) OVER (PARTITION BY part_keys ORDER BY order_keys), both
+    lists [(column, flags)] as a SortNode's and either may be empty.  The PlanNode's output_attrs hold
+    (RJ_WIN_OUT(func, column), result type) pairs; WIN_COL passes a child column through.  The frame is
+    SQL's default: up to the current row's last peer with order keys, the whole partition without.  The
+    rows come out ordered by (part_keys, order_keys), promised only at the plan's root (include/rj.h)."""
+    child: int
+    part_keys: list
+    order_keys: list
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -218,6 +248,14 @@ class Plan:
         result type)] as for new_agg_node."""
         oa = [(agg_out(f, c), t) for f, c, t in outputs]
         self.nodes.append(PlanNode(GroupNode(child, [tuple(k) for k in keys]), oa))
+        return len(self.nodes) - 1
+
+    def new_window_node(self, child, part_keys, order_keys, outputs):
+        """Window functions over PARTITION BY part_keys ORDER BY order_keys ([(column, flags)] each).
+        outputs = [(func, column, result type)] with func one of WIN_COL ... WIN_MAX; the column of a
+        ranking function and of WIN_COUNT_STAR is 0."""
+        oa = [(win_out(f, c), t) for f, c, t in outputs]
+        self.nodes.append(PlanNode(WindowNode(child, [tuple(k) for k in part_keys], [tuple(k) for k in order_keys]), oa))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -470,6 +508,18 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.left = n.data.child
             nd.right = nk  # RJ_GROUP_N_KEYS / RJ_GROUP_KEYS: the struct cannot grow
             nd.right_attr = C.addressof(karr) if nk else 0
+        elif isinstance(n.data, WindowNode):
+            wkeys = list(n.data.part_keys) + list(n.data.order_keys)
+            nk = len(wkeys)
+            karr = (rj_sort_key * max(1, nk))()
+            for j, (col, flags) in enumerate(wkeys):
+                karr[j].column, karr[j].flags = int(col), int(flags)
+            keep.append(karr)
+            nd.kind = NODE_WINDOW
+            nd.left = n.data.child
+            nd.right = nk  # RJ_WINDOW_N_KEYS / RJ_WINDOW_KEYS / RJ_WINDOW_N_PART: the struct cannot grow
+            nd.right_attr = C.addressof(karr) if nk else 0
+            nd.left_attr = len(n.data.part_keys)
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
