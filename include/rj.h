@@ -348,6 +348,65 @@ typedef enum rj_status {
  *   passing through; sharding.
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
+ *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Computed columns (scalar expressions in a select list or under an aggregate; no reference counterpart).
+ * RJ_NODE_MAP has ONE child, `left`; `build_left`, `base_table_id` and `left_attr` are ignored.
+ *   Program: rj_node cannot grow, so RJ_MAP_N_OPS(node) = `right` and RJ_MAP_OPS(node) = `right_attr` as a
+ *   `const rj_expr_op*` that stays valid during the call.  The program is ONE postfix list that holds any
+ *   number of expressions: RJ_X_OUT pops the top of the stack and ends expression number e = 0, 1, 2 ...
+ *   in order of appearance; after an RJ_X_OUT the stack must be empty.  rj_expr_op::column indexes the
+ *   CHILD's outputs.
+ *   Outputs (the bit layout of RJ_AGG_OUT): out_idx[k] = RJ_MAP_OUT(RJ_MAP_COL, c) passes child column c
+ *   through — a plain column index; the child column's type, bits and nullability; a VARCHAR column passes
+ *   through as row ids; nothing is copied.  out_idx[k] = RJ_MAP_OUT(RJ_MAP_EXPR, e) is expression e.  An
+ *   expression may be named by several outputs; one that no output names is RJ_ERR_ARG.
+ *   Values on the stack are I64 or F64 (typed by the host), each with a NULL flag:
+ *     RJ_X_COL (column)      INT32 sign-extends to I64; INT64 -> I64; FP64 -> F64; NULL where the column is
+ *     RJ_X_INT (ivalue), RJ_X_F64 (ivalue = the bits), RJ_X_NULL (column = RJ_INT64 or RJ_FP64: a typed
+ *                            NULL)  literals
+ *     RJ_X_ADD SUB MUL DIV MOD, RJ_X_NEG, RJ_X_ABS  both operands of ONE type (mixed is RJ_ERR_ARG: cast
+ *                            first); NULL if an operand is NULL
+ *     RJ_X_EQ NEQ LT GT LEQ GEQ  both of one type -> I64 0 / 1; NULL if an operand is NULL; F64 compares
+ *                            IEEE-wise, as RJ_NODE_SELECT does
+ *     RJ_X_AND, RJ_X_OR, RJ_X_NOT  integer operands, true = non-zero; Kleene's three-valued logic:
+ *                            NULL AND 0 = 0, NULL AND 1 = NULL, NULL OR 1 = 1, NULL OR 0 = NULL, NOT NULL = NULL
+ *     RJ_X_IS_NULL, RJ_X_IS_NOT_NULL  any type -> 0 / 1, never NULL
+ *     RJ_X_COALESCE (a, b)   same type; a unless it is NULL, then b
+ *     RJ_X_CASE (c, a, b)    c integer, a and b of the same type; a where c is non-NULL and non-zero, else
+ *                            b; all three are always evaluated
+ *     RJ_X_TO_I64, RJ_X_TO_F64  casts; to the value's own type the identity
+ *     RJ_X_OUT               ends an expression
+ *   Integer arithmetic wraps modulo 2^64, as RJ_AGG_SUM does: NEG and ABS of INT64_MIN give INT64_MIN; DIV
+ *   truncates toward zero, MOD takes the sign of the dividend; a zero divisor gives NULL, never an error
+ *   and never a trap; INT64_MIN / -1 is INT64_MIN and INT64_MIN % -1 is 0.
+ *   F64 arithmetic is IEEE-754 binary64, round to nearest even, every op rounded once (no contraction into
+ *   FMA, no fast-math, denormals kept); division is correctly rounded and x / 0.0 is +-inf or NaN, not
+ *   NULL; NEG flips the sign bit, ABS clears it; MOD on F64 is RJ_ERR_ARG.
+ *   Casts: TO_F64 of an I64 rounds to nearest even; TO_I64 of an F64 truncates toward zero and gives NULL
+ *   for a NaN and for a value outside [-2^63, 2^63).
+ *   An F64 value that is a NaN when RJ_X_OUT pops it comes out as 0x7ff8000000000000 (NaN payloads differ
+ *   between hosts and the device).  Nothing else is canonicalised: -0.0 stays -0.0, and a passed-through
+ *   column keeps its bits.
+ *   Declared result types: an I64 expression INT64, or INT32 (the low 32 bits, wrapping); an F64
+ *   expression FP64; anything else is RJ_ERR_ARG.  A computed column is nullable unless the program shows
+ *   that it cannot be NULL.
+ *   Rows: exactly the child's rows, each once; output row i is computed from row i of the child in the
+ *   order the child's rows have on the device.  An empty child gives 0 rows with the declared types and
+ *   zero pages.  RJ_MAP_N_OPS == 0 with only pass-through outputs is a projection and launches nothing.
+ *   Order: with a SCAN child the result is in the table's row order.  A MAP passes the root's order promise
+ *   down: when a MAP is the root, or every ancestor of it up to the root is a MAP, a SORT / GROUP / WINDOW
+ *   child delivers its rows in the order it promises at the root and the MAP keeps it (so ORDER BY k LIMIT n
+ *   below a MAP computes n rows).  Below any other kind the result is an ordinary relation.
+ *   RJ_ERR_ARG: an unknown opcode; a column out of range; operands of different types; a non-integer
+ *   operand of AND / OR / NOT or CASE's condition; MOD on F64; RJ_X_NULL with another type code; stack
+ *   underflow; a non-empty stack after RJ_X_OUT or at the end of the program; a program that does not end
+ *   in RJ_X_OUT; n_ops != 0 with a NULL pointer; an output that names an expression that does not exist;
+ *   an expression that no output names; a declared-type mismatch.  RJ_ERR_UNSUPPORTED: RJ_X_COL on a
+ *   VARCHAR column; more than RJ_MAP_MAX_OPS ops; a stack deeper than RJ_MAP_MAX_DEPTH; more than
+ *   2^32 - 16 child rows.  The node is checked before its child's rows are looked at.
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
  *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").                 */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
@@ -360,7 +419,8 @@ typedef enum rj_node_kind {
     RJ_NODE_SELECT = 7, /* rows of the one child `left` that pass a predicate */
     RJ_NODE_SORT = 8,   /* ORDER BY / LIMIT / OFFSET over the one child `left` */
     RJ_NODE_GROUP = 9,  /* GROUP BY any keys, or none, over the one child `left` */
-    RJ_NODE_WINDOW = 10 /* window functions OVER (PARTITION BY / ORDER BY) over the one child `left` */
+    RJ_NODE_WINDOW = 10, /* window functions OVER (PARTITION BY / ORDER BY) over the one child `left` */
+    RJ_NODE_MAP = 11     /* computed columns (scalar expressions) over the one child `left` */
 } rj_node_kind;
 
 /* Aggregate functions of RJ_NODE_AGG / RJ_NODE_GROUP and the encoding of their out_idx values. */
@@ -430,6 +490,32 @@ typedef enum rj_win_func {
 #define RJ_WIN_OUT(func, col) (((uint64_t)(func) << 56) | (uint64_t)(col))
 #define RJ_WIN_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
 #define RJ_WIN_COL(x) ((uint64_t)(x) & 0x00ffffffffffffffull)
+
+/* The program of an RJ_NODE_MAP node (`node`: a const rj_node*) and the encoding of its out_idx values
+ * (the bit layout of RJ_AGG_OUT). */
+typedef enum rj_expr_opcode {
+    RJ_X_COL = 0, RJ_X_INT = 1, RJ_X_F64 = 2, RJ_X_NULL = 3,
+    RJ_X_ADD = 4, RJ_X_SUB = 5, RJ_X_MUL = 6, RJ_X_DIV = 7, RJ_X_MOD = 8, RJ_X_NEG = 9, RJ_X_ABS = 10,
+    RJ_X_EQ = 11, RJ_X_NEQ = 12, RJ_X_LT = 13, RJ_X_GT = 14, RJ_X_LEQ = 15, RJ_X_GEQ = 16,
+    RJ_X_AND = 17, RJ_X_OR = 18, RJ_X_NOT = 19, RJ_X_IS_NULL = 20, RJ_X_IS_NOT_NULL = 21,
+    RJ_X_COALESCE = 22, RJ_X_CASE = 23, RJ_X_TO_I64 = 24, RJ_X_TO_F64 = 25, RJ_X_OUT = 26
+} rj_expr_opcode;
+typedef struct rj_expr_op {
+    int32_t op;     /* rj_expr_opcode */
+    int32_t column; /* RJ_X_COL: index into the child's outputs; RJ_X_NULL: RJ_INT64 or RJ_FP64 */
+    int64_t ivalue; /* RJ_X_INT: the literal; RJ_X_F64: the bits of the literal */
+} rj_expr_op;
+#define RJ_MAP_MAX_OPS 128
+#define RJ_MAP_MAX_DEPTH 8
+#define RJ_MAP_N_OPS(node) ((node)->right)
+#define RJ_MAP_OPS(node) ((const rj_expr_op*)(uintptr_t)(node)->right_attr)
+typedef enum rj_map_func {
+    RJ_MAP_COL  = 0, /* a child column passes through */
+    RJ_MAP_EXPR = 1  /* expression number RJ_MAP_ARG(x) of the program */
+} rj_map_func;
+#define RJ_MAP_OUT(func, x) (((uint64_t)(func) << 56) | (uint64_t)(x))
+#define RJ_MAP_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
+#define RJ_MAP_ARG(x) ((uint64_t)(x) & 0x00ffffffffffffffull)
 
 /* One Column (include/plan.h:60-100): `pages[i]` points at an 8192-byte Page. */
 typedef struct rj_column {
@@ -608,6 +694,16 @@ int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, u
  * context nor a GPU (an INT32 key is its low 32 bits).  RJ_ERR_ARG: another type, other flag bits, a
  * NULL pointer.                                                                                     */
 int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t* bits);
+/* The program of an RJ_NODE_MAP node on ONE row, run on the host: it is validated by the code the
+ * executor uses and evaluated through the op functions the kernel calls.  The row has n_cols columns:
+ * col_type[c] (rj_dtype), col_bits[c] (the value's bits, an INT32's in the low word), col_null[c] != 0 =
+ * NULL.  Expression e (at most out_cap of them are written, *n_out = how many the program holds) leaves
+ * out_bits[e], out_null[e] and out_kind[e] = RJ_INT64 for an I64 result, RJ_FP64 for an F64 one (the
+ * bits of a NULL result are 0).  Needs neither a context nor a GPU.  Returns the executor's status codes
+ * for the program (the outputs of a node are not part of it), the message in rj_last_error(NULL).      */
+int rj_debug_map_eval(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type,
+                      const uint64_t* col_bits, const uint8_t* col_null, uint64_t out_cap, uint64_t* out_bits,
+                      uint8_t* out_null, int32_t* out_kind, uint64_t* n_out);
 uint64_t rj_table_num_rows(const rj_table* t);
 uint64_t rj_table_col_pages(const rj_table* t, uint64_t col);
 int      rj_table_copy_pages(rj_context* ctx, const rj_table* t, uint64_t col, void* const* dst, uint64_t n_dst);
@@ -661,15 +757,15 @@ void     rj_result_free(rj_result* r);
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
  * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join, an
- * aggregation, a selection, a sort, a grouping or a window node; others return RJ_ERR_UNSUPPORTED.                                                                       */
+ * aggregation, a selection, a sort, a grouping, a window or a map node; others return RJ_ERR_UNSUPPORTED.                                                                       */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join, an aggregation, a selection, a sort, a grouping or a window node is not shardable; the reason
- * names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG /
- * RJ_NODE_SELECT / RJ_NODE_SORT / RJ_NODE_GROUP / RJ_NODE_WINDOW).                                                                                 */
+ * join, an aggregation, a selection, a sort, a grouping, a window or a map node is not shardable; the
+ * reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG /
+ * RJ_NODE_SELECT / RJ_NODE_SORT / RJ_NODE_GROUP / RJ_NODE_WINDOW / RJ_NODE_MAP).                                                                                 */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

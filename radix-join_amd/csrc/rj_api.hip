@@ -197,6 +197,24 @@ int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t*
     return RJ_OK;
 }
 
+int rj_debug_map_eval(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type, const uint64_t* col_bits,
+                      const uint8_t* col_null, uint64_t out_cap, uint64_t* out_bits, uint8_t* out_null, int32_t* out_kind, uint64_t* n_out) {
+    if (!n_out || (n_cols && (!col_type || !col_bits || !col_null)) || (out_cap && (!out_bits || !out_null || !out_kind))) return RJ_ERR_ARG;
+    *n_out = 0;
+    try {
+        rj::map_eval_row(ops, n_ops, n_cols, col_type, col_bits, col_null, out_cap, out_bits, out_null, out_kind, n_out);
+        return RJ_OK;
+    } catch (const rj::Error& e) {
+        std::lock_guard<std::mutex> g(g_err_mu);
+        g_create_error = e.what();  // rj_last_error(NULL)
+        return e.code;
+    } catch (const std::exception& e) {
+        std::lock_guard<std::mutex> g(g_err_mu);
+        g_create_error = e.what();
+        return RJ_ERR_DEVICE;
+    }
+}
+
 int rj_debug_launch_log(rj_context* ctx, int on) {
     if (!ctx) return RJ_ERR_ARG;
     for (int l = 0; l < ctx->n_lanes(); ++l) {  // a group context: every device's launches

@@ -16,6 +16,7 @@
 #include <functional>
 #include <set>
 
+#include "rj_expr.hpp"
 #include "rj_internal.hpp"
 #include "rj_xplan.hpp"
 
@@ -348,7 +349,10 @@ class Exec {
 
     // ------------------------------------------------------------- plan walk
     // execute_impl (reference src/execute.cpp:302-314); children left first (:48-49)
-    Rel node(uint64_t idx, Result* root_res, int depth) {
+    // `ordered`: every ancestor of this node up to the root is a MAP, which passes the root's order promise
+    // down: a sort then orders its rows as at the root (groupings and window nodes always leave theirs in
+    // key order)
+    Rel node(uint64_t idx, Result* root_res, int depth, bool ordered = false) {
         if (idx >= plan->n_nodes) throw_fmt(RJ_ERR_ARG, "bad node index");
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
@@ -363,7 +367,7 @@ class Exec {
         }
         if (n.kind == RJ_NODE_SORT) {
             Rel child = node(n.left, nullptr, depth + 1);
-            return sort(child, n, root_res);
+            return sort(child, n, root_res, ordered);
         }
         if (n.kind == RJ_NODE_GROUP) {
             Rel child = node(n.left, nullptr, depth + 1);
@@ -372,6 +376,10 @@ class Exec {
         if (n.kind == RJ_NODE_WINDOW) {
             Rel child = node(n.left, nullptr, depth + 1);
             return window(child, n, root_res);
+        }
+        if (n.kind == RJ_NODE_MAP) {
+            Rel child = node(n.left, nullptr, depth + 1, root_res != nullptr || ordered);
+            return map(child, n, root_res);
         }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
@@ -1912,7 +1920,7 @@ class Exec {
         perm = ids_in;
     }
 
-    Rel sort(Rel& child, const rj_node& n, Result* root_res) {
+    Rel sort(Rel& child, const rj_node& n, Result* root_res, bool ordered = false) {
         const size_t cw = child.cols.size();
         JoinSpec     js;  // (the declared types, for empty_rel)
         for (uint64_t k = 0; k < n.n_out; ++k) {
@@ -1939,8 +1947,9 @@ class Exec {
         if (count == 0) return empty_rel(js, root_res);
         const bool whole = count == child.n;
         // below another node the order is nobody's business: without a slice the child passes through
+        // (not below the MAPs of a root, which keep the order: `ordered`)
         BufP perm;
-        if (root_res || !whole) {
+        if (root_res || ordered || !whole) {
             for (uint64_t k = n_keys; k-- > 0;) {
                 bool shadowed = false;  // behind the same column nothing is left to order: rows that tie on it tie again
                 for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
@@ -2342,6 +2351,137 @@ class Exec {
                 root_res->cols.push_back(col_to_result(made.at(id), rows));
             else
                 out.cols.push_back(made.at(id));
+        }
+        return out;
+    }
+
+    // ---------------------------------------------------------------------- map
+    // RJ_NODE_MAP (semantics in rj.h): computed columns over the one child.  The program is checked and typed
+    // by map_check (shared with rj_debug_map_eval), translated into MapProg with one ColRef per RJ_X_COL and
+    // the result arrays in its RJ_X_OUT ops, and k_map (rj_map.hip) evaluates ALL expressions in one launch.
+    // Passed-through columns are the child's own DCols.  No host sync: the result has the child's rows.
+    std::vector<std::unique_ptr<MapProg>> map_progs_;  // the host ends of queued copies: they live as long as the Exec
+    ~Exec() {
+        if (!map_progs_.empty()) (void)hipStreamSynchronize(ctx->stream);
+    }
+    Rel map(Rel& child, const rj_node& n, Result* root_res) {
+        const size_t      cw = child.cols.size();
+        const uint64_t    n_ops = RJ_MAP_N_OPS(&n);
+        const rj_expr_op* ops = RJ_MAP_OPS(&n);
+        std::vector<int32_t> types(cw);
+        std::vector<uint8_t> nullable(cw);
+        for (size_t c = 0; c < cw; ++c) {
+            types[c] = child.cols[c].type;
+            nullable[c] = child.cols[c].valid != nullptr;
+        }
+        std::vector<MapOp>   dev;
+        std::vector<MapExpr> exprs;
+        map_check(ops, n_ops, cw, types.data(), nullable.data(), dev, exprs);
+        struct ExprOut {
+            bool want8 = false, want4 = false;
+            DCol d8, d4;
+        };
+        std::vector<ExprOut>  eo(exprs.size());
+        std::vector<uint64_t> pass;  // the distinct passed-through columns
+        JoinSpec              js;    // (the declared types, for empty_rel)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint32_t func = RJ_MAP_FUNC(n.out_idx[k]);
+            const uint64_t arg = RJ_MAP_ARG(n.out_idx[k]);
+            if (func == RJ_MAP_COL) {
+                if (arg >= cw) throw_fmt(RJ_ERR_ARG, "map: output attr out of range");
+                if (child.cols[arg].type != n.out_type[k])
+                    throw_fmt(RJ_ERR_ARG, "map: declared type differs from the child column's type");
+                if (std::find(pass.begin(), pass.end(), arg) == pass.end()) pass.push_back(arg);
+            } else if (func == RJ_MAP_EXPR) {
+                if (arg >= exprs.size())
+                    throw_fmt(RJ_ERR_ARG, "map: output %llu names expression %llu, the program holds %zu", (unsigned long long)k,
+                              (unsigned long long)arg, exprs.size());
+                const int32_t t = n.out_type[k];
+                if (exprs[arg].f64 ? t != RJ_FP64 : (t != RJ_INT64 && t != RJ_INT32))
+                    throw_fmt(RJ_ERR_ARG, "map: declared type differs from the expression's type (an I64 expression is INT64 or INT32, "
+                                          "an F64 one FP64)");
+                (t == RJ_INT32 ? eo[arg].want4 : eo[arg].want8) = true;
+            } else {
+                throw_fmt(RJ_ERR_ARG, "map: unknown output code %u", func);
+            }
+            js.out_type.push_back(n.out_type[k]);
+        }
+        for (size_t e = 0; e < eo.size(); ++e)
+            if (!eo[e].want8 && !eo[e].want4) throw_fmt(RJ_ERR_ARG, "map: no output names expression %zu", e);
+        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        if (child.n == 0) return empty_rel(js, root_res);
+        const uint64_t rows = child.n;
+
+        // ---- the device program: the columns it reads, the arrays it writes
+        if (!exprs.empty()) {
+            map_progs_.emplace_back(new MapProg());
+            MapProg& prog = *map_progs_.back();
+            size_t   e = 0;
+            for (uint64_t k = 0; k < n_ops; ++k) {
+                MapOp& o = dev[k];
+                if (o.op == X_COL) o.a = child.cols[(size_t)ops[k].column].ref();
+                if (o.op == X_OUT) {
+                    ExprOut& x = eo[e];
+                    BufP     valid = exprs[e].nullable ? ctx->buf(rows) : BufP();
+                    auto     make = [&](DCol& d, int32_t type, int width) {
+                        d.type = type;
+                        d.kind = COL_DENSE;
+                        d.width = width;
+                        d.hold = ctx->buf(rows * (uint64_t)width);
+                        d.ptr = d.hold->as<uint8_t>();
+                        d.hold_valid = valid;
+                        d.valid = valid ? valid->as<uint8_t>() : nullptr;
+                    };
+                    if (x.want8) make(x.d8, exprs[e].f64 ? RJ_FP64 : RJ_INT64, 8);
+                    if (x.want4) make(x.d4, RJ_INT32, 4);
+                    o.out8 = x.want8 ? x.d8.hold->as<uint8_t>() : nullptr;
+                    o.out4 = x.want4 ? x.d4.hold->as<uint8_t>() : nullptr;
+                    o.valid = valid ? valid->as<uint8_t>() : nullptr;
+                    ++e;
+                }
+                prog.ops[k] = o;
+            }
+            BufP           dprog = ctx->buf(sizeof(MapProg));
+            const uint64_t tiles = (rows + MAP_TILE - 1) / MAP_TILE;
+            uint64_t       grid = std::min<uint64_t>(tiles, (uint64_t)ctx->compute_units() * 8);
+            if (ctx->tune.map_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)ctx->tune.map_grid);
+            RJ_HIP(hipMemcpyAsync(dprog->p, &prog, n_ops * sizeof(MapOp), hipMemcpyHostToDevice, ctx->stream));
+            launch_map(L, dprog->as<MapProg>(), (uint32_t)n_ops, (uint32_t)rows, (uint32_t)grid);
+        }
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] map rows=%llu ops=%llu expressions=%zu\n", (unsigned long long)rows, (unsigned long long)n_ops,
+                    exprs.size());
+
+        // ---- the passed-through columns: the child's own (at the root through the writers of a projection)
+        rj_node through = n;
+        through.n_out = pass.size();
+        through.out_idx = pass.data();
+        Result pass_res;
+        Rel    pass_rel = emit_rows(child, through, BufP(), nullptr, rows, root_res ? &pass_res : nullptr);
+
+        // ---- the output columns
+        Rel out;
+        out.n = rows;
+        if (root_res) root_res->num_rows = rows;
+        std::map<uint64_t, ResultColumn> made_rc;  // (an expression named twice under one type is encoded once)
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint64_t arg = RJ_MAP_ARG(n.out_idx[k]);
+            if (RJ_MAP_FUNC(n.out_idx[k]) == RJ_MAP_COL) {
+                const size_t at = (size_t)(std::find(pass.begin(), pass.end(), arg) - pass.begin());
+                if (root_res)
+                    root_res->cols.push_back(pass_res.cols[at]);
+                else
+                    out.cols.push_back(pass_rel.cols[at]);
+                continue;
+            }
+            const DCol& d = n.out_type[k] == RJ_INT32 ? eo[arg].d4 : eo[arg].d8;
+            if (!root_res) {
+                out.cols.push_back(d);
+                continue;
+            }
+            const uint64_t id = arg * 2 + (n.out_type[k] == RJ_INT32);
+            if (!made_rc.count(id)) made_rc[id] = col_to_result(d, rows);
+            root_res->cols.push_back(made_rc.at(id));
         }
         return out;
     }
@@ -2859,6 +2999,8 @@ class ShardedExec {
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: grouping (RJ_NODE_GROUP) nodes run on one device");
         if (n.kind == RJ_NODE_WINDOW)
             throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: window (RJ_NODE_WINDOW) nodes run on one device");
+        if (n.kind == RJ_NODE_MAP)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: map (RJ_NODE_MAP) nodes run on one device");
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -3266,6 +3408,10 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
         if (why) *why = "a window node (RJ_NODE_WINDOW) runs on one device";
         return false;
     }
+    if (n.kind == RJ_NODE_MAP) {
+        if (why) *why = "a map node (RJ_NODE_MAP) runs on one device";
+        return false;
+    }
     if (n.kind != RJ_NODE_JOIN) return false;
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
@@ -3310,6 +3456,174 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
 }
 }  // namespace
 
+// ------------------------------------------------------------------ RJ_NODE_MAP: the program
+static_assert((int)X_COL == RJ_X_COL && (int)X_NULL == RJ_X_NULL && (int)X_MOD == RJ_X_MOD && (int)X_ABS == RJ_X_ABS && (int)X_GEQ == RJ_X_GEQ &&
+                  (int)X_NOT == RJ_X_NOT && (int)X_IS_NOT_NULL == RJ_X_IS_NOT_NULL && (int)X_CASE == RJ_X_CASE && (int)X_TO_F64 == RJ_X_TO_F64 &&
+                  (int)X_OUT == RJ_X_OUT && MAP_MAX_OPS == RJ_MAP_MAX_OPS && MAP_MAX_DEPTH == RJ_MAP_MAX_DEPTH,
+              "rj_expr.hpp mirrors rj_expr_opcode");
+
+void map_check(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type, const uint8_t* col_nullable,
+               std::vector<MapOp>& dev_ops, std::vector<MapExpr>& exprs) {
+    dev_ops.clear();
+    exprs.clear();
+    if (n_ops > (uint64_t)MAP_MAX_OPS) throw_fmt(RJ_ERR_UNSUPPORTED, "map: program longer than %d operations", MAP_MAX_OPS);
+    if (n_ops && !ops) throw_fmt(RJ_ERR_ARG, "map: %llu operations but a NULL program pointer", (unsigned long long)n_ops);
+    struct Slot {
+        bool f64, nullable;
+    };
+    Slot st[MAP_MAX_DEPTH + 1];
+    int  sp = 0;
+    auto need = [&](int k, uint64_t at) {
+        if (sp < k) throw_fmt(RJ_ERR_ARG, "map: stack underflow at op %llu", (unsigned long long)at);
+    };
+    auto same = [&](const Slot& x, const Slot& y, uint64_t at) {
+        if (x.f64 != y.f64) throw_fmt(RJ_ERR_ARG, "map: operands of different types at op %llu (cast first)", (unsigned long long)at);
+    };
+    auto integer = [&](const Slot& x, uint64_t at, const char* what) {
+        if (x.f64) throw_fmt(RJ_ERR_ARG, "map: %s takes integer operands (op %llu)", what, (unsigned long long)at);
+    };
+    for (uint64_t k = 0; k < n_ops; ++k) {
+        const rj_expr_op& o = ops[k];
+        MapOp             d{};
+        d.op = o.op;
+        Slot r{false, false};
+        bool push = true;
+        if (o.op == RJ_X_COL) {
+            if (o.column < 0 || (uint64_t)o.column >= n_cols) throw_fmt(RJ_ERR_ARG, "map: column out of range at op %llu", (unsigned long long)k);
+            const int32_t t = col_type[o.column];
+            if (t == RJ_VARCHAR)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "map: expression over a VARCHAR column (child column %d): a VARCHAR value travels as a row "
+                                              "id, its pages are not read here", o.column);
+            if (t != RJ_INT32 && t != RJ_INT64 && t != RJ_FP64) throw_fmt(RJ_ERR_ARG, "map: bad column type %d", t);
+            r = Slot{t == RJ_FP64, col_nullable ? col_nullable[o.column] != 0 : true};
+        } else if (o.op == RJ_X_INT || o.op == RJ_X_F64) {
+            d.lit = o.ivalue;
+            r = Slot{o.op == RJ_X_F64, false};
+        } else if (o.op == RJ_X_NULL) {
+            if (o.column != RJ_INT64 && o.column != RJ_FP64)
+                throw_fmt(RJ_ERR_ARG, "map: RJ_X_NULL with type code %d (RJ_INT64 or RJ_FP64)", o.column);
+            r = Slot{o.column == RJ_FP64, true};
+        } else if (o.op >= RJ_X_ADD && o.op <= RJ_X_MOD) {
+            need(2, k);
+            const Slot &a = st[sp - 2], &b = st[sp - 1];
+            same(a, b, k);
+            if (o.op == RJ_X_MOD && a.f64) throw_fmt(RJ_ERR_ARG, "map: MOD on F64 (op %llu)", (unsigned long long)k);
+            d.arity = 2;
+            d.f64 = a.f64;
+            r = Slot{a.f64, a.nullable || b.nullable || (!a.f64 && (o.op == RJ_X_DIV || o.op == RJ_X_MOD))};
+        } else if (o.op == RJ_X_NEG || o.op == RJ_X_ABS) {
+            need(1, k);
+            d.arity = 1;
+            d.f64 = st[sp - 1].f64;
+            r = st[sp - 1];
+        } else if (o.op >= RJ_X_EQ && o.op <= RJ_X_GEQ) {
+            need(2, k);
+            const Slot &a = st[sp - 2], &b = st[sp - 1];
+            same(a, b, k);
+            d.arity = 2;
+            d.f64 = a.f64;
+            r = Slot{false, a.nullable || b.nullable};
+        } else if (o.op == RJ_X_AND || o.op == RJ_X_OR) {
+            need(2, k);
+            integer(st[sp - 2], k, "AND / OR");
+            integer(st[sp - 1], k, "AND / OR");
+            d.arity = 2;
+            r = Slot{false, st[sp - 2].nullable || st[sp - 1].nullable};
+        } else if (o.op == RJ_X_NOT) {
+            need(1, k);
+            integer(st[sp - 1], k, "NOT");
+            d.arity = 1;
+            r = st[sp - 1];
+        } else if (o.op == RJ_X_IS_NULL || o.op == RJ_X_IS_NOT_NULL) {
+            need(1, k);
+            d.arity = 1;
+            d.f64 = st[sp - 1].f64;
+            r = Slot{false, false};
+        } else if (o.op == RJ_X_COALESCE) {
+            need(2, k);
+            const Slot &a = st[sp - 2], &b = st[sp - 1];
+            same(a, b, k);
+            d.arity = 2;
+            d.f64 = a.f64;
+            r = Slot{a.f64, a.nullable && b.nullable};
+        } else if (o.op == RJ_X_CASE) {
+            need(3, k);
+            const Slot &c = st[sp - 3], &a = st[sp - 2], &b = st[sp - 1];
+            integer(c, k, "the condition of CASE");
+            same(a, b, k);
+            d.arity = 3;
+            d.f64 = a.f64;
+            r = Slot{a.f64, a.nullable || b.nullable};
+        } else if (o.op == RJ_X_TO_I64 || o.op == RJ_X_TO_F64) {
+            need(1, k);
+            const Slot& a = st[sp - 1];
+            d.arity = 1;
+            d.f64 = a.f64;
+            r = Slot{o.op == RJ_X_TO_F64, a.nullable || (o.op == RJ_X_TO_I64 && a.f64)};
+        } else if (o.op == RJ_X_OUT) {
+            need(1, k);
+            if (sp != 1) throw_fmt(RJ_ERR_ARG, "map: %d values left on the stack behind RJ_X_OUT (op %llu)", sp - 1, (unsigned long long)k);
+            d.arity = 1;
+            d.f64 = st[0].f64;
+            exprs.push_back(MapExpr{st[0].f64 ? 1 : 0, st[0].nullable});
+            push = false;
+        } else {
+            throw_fmt(RJ_ERR_ARG, "map: bad expression opcode %d (op %llu)", o.op, (unsigned long long)k);
+        }
+        sp -= d.arity;
+        if (push) {
+            if (sp >= MAP_MAX_DEPTH) throw_fmt(RJ_ERR_UNSUPPORTED, "map: stack deeper than %d (op %llu)", MAP_MAX_DEPTH, (unsigned long long)k);
+            if (d.arity == 0) d.f64 = r.f64;
+            st[sp++] = r;
+        }
+        dev_ops.push_back(d);
+    }
+    if (sp != 0) throw_fmt(RJ_ERR_ARG, "map: the program does not end in RJ_X_OUT (%d values left on the stack)", sp);
+}
+
+void map_eval_row(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type, const uint64_t* col_bits,
+                  const uint8_t* col_null, uint64_t out_cap, uint64_t* out_bits, uint8_t* out_null, int32_t* out_kind, uint64_t* n_out) {
+    std::vector<MapOp>   dev;
+    std::vector<MapExpr> exprs;
+    map_check(ops, n_ops, n_cols, col_type, nullptr, dev, exprs);
+    uint64_t v[MAP_MAX_DEPTH + 3] = {};
+    bool     nl[MAP_MAX_DEPTH + 3] = {};
+    uint32_t sp = 0;
+    uint64_t e = 0;
+    for (uint64_t k = 0; k < n_ops; ++k) {
+        const MapOp& o = dev[k];
+        uint64_t     r = 0;
+        bool         rn = false;
+        if (o.op == X_COL) {
+            const int32_t c = ops[k].column;
+            r = col_type[c] == RJ_INT32 ? (uint64_t)(int64_t)(int32_t)(uint32_t)col_bits[c] : col_bits[c];
+            rn = col_null[c] != 0;
+        } else if (o.op <= X_NULL) {
+            r = (uint64_t)o.lit;
+            rn = o.op == X_NULL;
+        } else {
+            const uint32_t base = sp - (uint32_t)o.arity;
+            if (o.op == X_OUT) {
+                if (e < out_cap) {
+                    out_null[e] = nl[base] ? 1 : 0;
+                    out_bits[e] = nl[base] ? 0 : x_out(o.f64 != 0, v[base]);
+                    out_kind[e] = o.f64 ? RJ_FP64 : RJ_INT64;
+                }
+                ++e;
+                sp = base;
+                continue;
+            }
+            r = x_apply(o.op, o.f64 != 0, v[base], nl[base], o.arity >= 2 ? v[base + 1] : 0, o.arity >= 2 && nl[base + 1],
+                        o.arity >= 3 ? v[base + 2] : 0, o.arity >= 3 && nl[base + 2], rn);
+            sp = base;
+        }
+        v[sp] = r;
+        nl[sp] = rn;
+        ++sp;
+    }
+    *n_out = e;
+}
+
 Result* execute_plan(Context* ctx, const rj_plan* plan, Table* const* tables, uint64_t n_tables,
                      int flags, TableFetch* fetch) {
     Exec e(ctx, plan, tables, n_tables, flags);
@@ -3350,6 +3664,9 @@ static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
     if (n.kind == RJ_NODE_WINDOW)
         throw_fmt(RJ_ERR_UNSUPPORTED,
                   "rj_execute_sharded: the plan holds a window (RJ_NODE_WINDOW) node; window functions run on one device");
+    if (n.kind == RJ_NODE_MAP)
+        throw_fmt(RJ_ERR_UNSUPPORTED,
+                  "rj_execute_sharded: the plan holds a map (RJ_NODE_MAP) node; computed columns run on one device");
     if (n.kind == RJ_NODE_JOIN) {
         refuse_filter_nodes(plan, n.left, depth + 1);
         refuse_filter_nodes(plan, n.right, depth + 1);

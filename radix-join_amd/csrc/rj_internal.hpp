@@ -230,6 +230,7 @@ struct Tuning {
                           // in one pass; 0: by owner rank only (stage B then runs one more pass)
     int group_grid = 0;   // RJ_TUNE_GROUP_GRID: cap on the workgroups of k_group_reduce, so that a small input walks several
                           // tiles per workgroup (0 = 8 per compute unit)
+    int map_grid = 0;     // RJ_TUNE_MAP_GRID: cap on the workgroups of k_map, so that a small input makes one workgroup walk several tiles (tests)
     int win_grid = 0;     // RJ_TUNE_WIN_GRID: cap on the quarter entries k_win_carry / k_win_tail_carry take per step, so that a
                           // small input takes several steps and carries from one to the next (0 = 1024, one per thread)
     int exchange_timeout_ms = 120000;  // RJ_EXCHANGE_TIMEOUT_MS: bound on every wait of the exchange step of a
@@ -322,6 +323,23 @@ void    shard_partition(Context* ctx, const Table* t, uint64_t key_col, uint64_t
                         uint32_t n_ranks, rj_tuples* out, uint64_t* counts);
 
 // rj_table.hip
+// The program of an RJ_NODE_MAP node, checked and typed (rj_exec.hip; shared by Exec::map and
+// rj_debug_map_eval): the errors of rj.h in the order of the ops.  col_type[c]: rj_dtype of child column c;
+// col_nullable[c] != 0: the column may hold NULLs (nullptr: every column may).  -> one MapOp per op
+// (rj_expr.hpp: op, operand type, arity, literal; no pointers yet) and, per expression, the type of its
+// value (0 = I64, 1 = F64) and whether it can be NULL: a value can if it comes from a nullable column,
+// RJ_X_NULL, an integer DIV / MOD, TO_I64 of an F64, or anything fed by one of those.
+struct MapOp;
+struct MapExpr {
+    int32_t f64;
+    bool    nullable;
+};
+void map_check(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type, const uint8_t* col_nullable,
+               std::vector<MapOp>& dev_ops, std::vector<MapExpr>& exprs);
+// rj_debug_map_eval: map_check, then the program on one row through x_apply
+void map_eval_row(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type, const uint64_t* col_bits,
+                  const uint8_t* col_null, uint64_t out_cap, uint64_t* out_bits, uint8_t* out_null, int32_t* out_kind, uint64_t* n_out);
+
 // col_used: upload only these columns (nullptr = all); borrow_varchar: keep pointers to the
 // caller's VARCHAR pages instead of copying them
 Table* table_upload(Context* ctx, const rj_input* host, const std::vector<bool>* col_used = nullptr,

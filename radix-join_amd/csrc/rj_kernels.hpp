@@ -178,6 +178,12 @@ void launch_agg_column(const Launch& L, const unsigned long long* src, const uns
 void launch_select(const Launch& L, const SelectProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t* out_ids,
                    unsigned long long* cursor, uint32_t grid);
 
+// ---- computed columns (RJ_NODE_MAP, rj_map.hip): the n_ops ops of the program (a device copy of MapProg,
+// rj_expr.hpp) over every row of [0, n_rows); every X_OUT op names the dense arrays it writes.  `grid`
+// workgroups stride over the tiles of MAP_TILE rows.
+struct MapProg;
+void launch_map(const Launch& L, const MapProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t grid);
+
 // ---- sort (RJ_NODE_SORT): a stable LSD radix sort of {key, row id}, SORT_RADIX bins per pass, tiles of
 // SORT_TILE rows (rj_device.hpp).  n_tiles = ceil(n_rows / SORT_TILE) everywhere.
 // One key column read through `perm` (row i of the current order = row perm[i]; nullptr = i) -> keys_out

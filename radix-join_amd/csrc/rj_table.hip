@@ -304,7 +304,7 @@ static void scan_order(const rj_plan* plan, uint64_t idx, int depth, std::vector
         scan_order(plan, n.left, depth + 1, seen, order);
         scan_order(plan, n.right, depth + 1, seen, order);
     } else if (n.kind == RJ_NODE_AGG || n.kind == RJ_NODE_SELECT || n.kind == RJ_NODE_SORT || n.kind == RJ_NODE_GROUP ||
-               n.kind == RJ_NODE_WINDOW) {
+               n.kind == RJ_NODE_WINDOW || n.kind == RJ_NODE_MAP) {
         scan_order(plan, n.left, depth + 1, seen, order);
     }
 }

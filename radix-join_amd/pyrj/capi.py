@@ -93,6 +93,44 @@ def filter_to_c(prog):
     return arr, len(prog), keep
 
 
+class rj_expr_op(C.Structure):
+    _fields_ = [("op", C.c_int32), ("column", C.c_int32), ("ivalue", C.c_int64)]
+
+
+# rj_expr_opcode (include/rj.h): the program of a map node is a postfix list that holds any number of
+# expressions, each ended by ("OUT",), e.g. a * b + 5 and COALESCE(c, 0.0):
+#   [("COL", 0), ("COL", 1), ("MUL",), ("INT", 5), ("ADD",), ("OUT",), ("COL", 2), ("F64", 0.0), ("COALESCE",), ("OUT",)]
+# ("F64", x): a Python float is that double, an int the BITS of the double; ("NULL", type): pl.INT64 / pl.FP64.
+X_OPS = {"COL": 0, "INT": 1, "F64": 2, "NULL": 3, "ADD": 4, "SUB": 5, "MUL": 6, "DIV": 7, "MOD": 8, "NEG": 9, "ABS": 10,
+         "EQ": 11, "NEQ": 12, "LT": 13, "GT": 14, "LEQ": 15, "GEQ": 16, "AND": 17, "OR": 18, "NOT": 19, "IS_NULL": 20,
+         "IS_NOT_NULL": 21, "COALESCE": 22, "CASE": 23, "TO_I64": 24, "TO_F64": 25, "OUT": 26}
+
+
+def f64_bits(x) -> int:
+    """the bits (signed, as rj_expr_op::ivalue holds them) of an ("F64", x) literal"""
+    if isinstance(x, float):
+        return int(np.array([x], dtype=np.float64).view(np.int64)[0])
+    x = int(x)
+    return x - 2**64 if x >= 2**63 else x
+
+
+def expr_to_c(prog):
+    """-> (rj_expr_op array, n)"""
+    prog = list(prog or [])
+    arr = (rj_expr_op * max(1, len(prog)))()
+    for k, term in enumerate(prog):
+        op = X_OPS[term[0]]
+        arr[k].op = op
+        if op in (0, 3):
+            arr[k].column = int(term[1])
+        elif op == 1:
+            v = int(term[1])
+            arr[k].ivalue = v - 2**64 if v >= 2**63 else v
+        elif op == 2:
+            arr[k].ivalue = f64_bits(term[1])
+    return arr, len(prog)
+
+
 class rj_kernel_stat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -128,6 +166,7 @@ EXPORTS = [
     "rj_debug_parse_fp64",
     "rj_debug_sort_key",
     "rj_debug_sort_key_value",
+    "rj_debug_map_eval",
     "rj_table_num_rows",
     "rj_table_col_pages",
     "rj_table_copy_pages",
@@ -640,6 +679,30 @@ def sort_key_value(dtype: int, flags: int, key: int) -> int:
     if rc != 0:
         raise RjError(rc, "rj_debug_sort_key_value: bad type or flags")
     return int(bits.value)
+
+
+def map_eval(prog, row):
+    """rj_debug_map_eval: the program of a map node (tuple form, see X_OPS) on ONE row, on the host.  row =
+    [(dtype, bits, is_null)], bits the value's bits as an unsigned number (an INT32's in the low word).
+    -> [(kind, bits, is_null)] per expression, kind pl.INT64 or pl.FP64, bits unsigned."""
+    L = load()
+    u64p = C.POINTER(C.c_uint64)
+    L.rj_debug_map_eval.restype = C.c_int
+    L.rj_debug_map_eval.argtypes = [C.POINTER(rj_expr_op), C.c_uint64, C.c_uint64, C.POINTER(C.c_int32), u64p, C.POINTER(C.c_uint8),
+                                    C.c_uint64, u64p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), u64p]
+    ops, n_ops = expr_to_c(prog)
+    nc = len(row)
+    types = (C.c_int32 * max(1, nc))(*[int(r[0]) for r in row])
+    bits = (C.c_uint64 * max(1, nc))(*[int(r[1]) & (2**64 - 1) for r in row])
+    nulls = (C.c_uint8 * max(1, nc))(*[1 if r[2] else 0 for r in row])
+    cap = max(1, n_ops)
+    ob, on, ok, n_out = (C.c_uint64 * cap)(), (C.c_uint8 * cap)(), (C.c_int32 * cap)(), C.c_uint64(0)
+    rc = L.rj_debug_map_eval(ops if n_ops else None, n_ops, nc, types, bits, nulls, cap, ob, on, ok, C.byref(n_out))
+    if rc != 0:
+        L.rj_last_error.restype = C.c_char_p
+        L.rj_last_error.argtypes = [C.c_void_p]
+        raise RjError(rc, (L.rj_last_error(None) or b"").decode())
+    return [(int(ok[e]), int(ob[e]), bool(on[e])) for e in range(int(n_out.value))]
 
 
 def make_comm_id() -> bytes:

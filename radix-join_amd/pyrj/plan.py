@@ -53,6 +53,7 @@ NODE_SCAN, NODE_JOIN, NODE_SEMI, NODE_ANTI, NODE_OUTER, NODE_FULL, NODE_AGG, NOD
 NODE_SORT = 8
 NODE_GROUP = 9
 NODE_WINDOW = 10
+NODE_MAP = 11
 # rj_sort_key::flags, RJ_SORT_NO_LIMIT
 SORT_DESC, SORT_NULLS_FIRST = 1, 2
 SORT_NO_LIMIT = 2**64 - 1
@@ -86,6 +87,24 @@ def win_func(x):
 
 
 def win_col(x):
+    return int(x) & ((1 << 56) - 1)
+
+
+# rj_map_func and the RJ_MAP_OUT / RJ_MAP_FUNC / RJ_MAP_ARG encoding of a map node's out_idx (the bit layout
+# of RJ_AGG_OUT)
+MAP_COL, MAP_EXPR = 0, 1
+MAP_OUT_NAMES = {"COL": MAP_COL, "EXPR": MAP_EXPR}
+
+
+def map_out(func, x):
+    return (int(func) << 56) | int(x)
+
+
+def map_func(x):
+    return int(x) >> 56
+
+
+def map_arg(x):
     return int(x) & ((1 << 56) - 1)
 
 
@@ -185,6 +204,18 @@ class WindowNode:
 
 
 @dataclass
+class MapNode:
+    """Computed columns (kind NODE_MAP): `program` is a postfix list in the tuple form capi.expr_to_c
+    takes (capi.X_OPS) that holds any number of expressions, each ended by ("OUT",); its columns are the
+    child's outputs.  The PlanNode's output_attrs hold (RJ_MAP_OUT(func, x), result type) pairs: MAP_COL
+    passes child column x through, MAP_EXPR is expression x.  The result has the child's rows in the child's
+    order; below the root (or below MAPs only) a sort, grouping or window child keeps its order
+    (include/rj.h)."""
+    child: int
+    program: list
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -256,6 +287,13 @@ class Plan:
         ranking function and of WIN_COUNT_STAR is 0."""
         oa = [(win_out(f, c), t) for f, c, t in outputs]
         self.nodes.append(PlanNode(WindowNode(child, [tuple(k) for k in part_keys], [tuple(k) for k in order_keys]), oa))
+        return len(self.nodes) - 1
+
+    def new_map_node(self, child, program, outputs):
+        """Computed columns over `child` (see MapNode).  outputs = [("COL", c, type) | ("EXPR", e, type)]
+        (or MAP_COL / MAP_EXPR for the names)."""
+        oa = [(map_out(MAP_OUT_NAMES.get(f, f), x), t) for f, x, t in outputs]
+        self.nodes.append(PlanNode(MapNode(child, [tuple(t) for t in (program or [])]), oa))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -520,6 +558,15 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.right = nk  # RJ_WINDOW_N_KEYS / RJ_WINDOW_KEYS / RJ_WINDOW_N_PART: the struct cannot grow
             nd.right_attr = C.addressof(karr) if nk else 0
             nd.left_attr = len(n.data.part_keys)
+        elif isinstance(n.data, MapNode):
+            from . import capi  # (capi imports this module)
+
+            ops, n_ops = capi.expr_to_c(n.data.program)
+            keep.append(ops)
+            nd.kind = NODE_MAP
+            nd.left = n.data.child
+            nd.right = n_ops  # RJ_MAP_N_OPS / RJ_MAP_OPS: the struct cannot grow
+            nd.right_attr = C.addressof(ops) if n_ops else 0
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
