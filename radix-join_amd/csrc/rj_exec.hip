@@ -22,7 +22,36 @@
 
 namespace rj {
 
+// What the plan walks know about a node kind: Exec::node, ShardedExec, first_unshardable and the
+// uploader's scan_order (rj_table.hip).  A new kind gets its line here, its driver in Exec and, if it has
+// one child, its case in Exec::node's switch (without one the walk reports "bad node kind").
+const NodeKind* node_kind(int kind) {
+    static const NodeKind kinds[] = {
+        {RJ_NODE_SCAN, "a scan", "RJ_NODE_SCAN", 0, true},
+        {RJ_NODE_JOIN, "a join", "RJ_NODE_JOIN", 2, true},
+        {RJ_NODE_SEMI, "a semi join", "RJ_NODE_SEMI", 2, false},
+        {RJ_NODE_ANTI, "an anti join", "RJ_NODE_ANTI", 2, false},
+        {RJ_NODE_OUTER, "an outer join", "RJ_NODE_OUTER", 2, false},
+        {RJ_NODE_FULL, "a full outer join", "RJ_NODE_FULL", 2, false},
+        {RJ_NODE_AGG, "an aggregation", "RJ_NODE_AGG", 1, false},
+        {RJ_NODE_SELECT, "a selection", "RJ_NODE_SELECT", 1, false},
+        {RJ_NODE_SORT, "a sort", "RJ_NODE_SORT", 1, false},
+        {RJ_NODE_GROUP, "a grouping", "RJ_NODE_GROUP", 1, false},
+        {RJ_NODE_WINDOW, "a window", "RJ_NODE_WINDOW", 1, false},
+        {RJ_NODE_MAP, "a map", "RJ_NODE_MAP", 1, false},
+    };
+    for (const NodeKind& k : kinds)
+        if (k.kind == kind) return &k;
+    return nullptr;
+}
+
 namespace {
+
+// a buffer's memory, or nullptr where there is no buffer
+template <class T>
+T* ptr(const BufP& b) {
+    return b ? b->as<T>() : nullptr;
+}
 
 struct DCol {
     int32_t        type = RJ_INT32;  // declared DataType
@@ -157,10 +186,7 @@ class Exec {
         auto mk = [](const rj_tuples* t) {
             Rel r;
             r.n = t->n;
-            DCol k;
-            k.type = RJ_INT32;
-            k.kind = COL_DENSE;
-            k.width = 4;
+            DCol k = dense_col(RJ_INT32, BufP());  // (the caller's arrays: nothing to hold)
             k.ptr = static_cast<const uint8_t*>(t->key);
             DCol c = k;
             c.ptr = static_cast<const uint8_t*>(t->carry);
@@ -208,9 +234,7 @@ class Exec {
         ext.w[1] = static_cast<uint32_t*>(out->carry);
         Parted P = partition(&src, nullptr, 1, 1, rb, /*shift0=*/rb ? 32 - rb : 31, /*single pass*/ true, &ext);
         std::vector<uint32_t> off(n_ranks + 1);
-        RJ_HIP(hipMemcpyAsync(off.data(), P.off->p, (n_ranks + 1) * 4, hipMemcpyDeviceToHost,
-                              ctx->stream));
-        ctx->sync();
+        read_back(off.data(), P.off->p, (n_ranks + 1) * 4);
         for (uint32_t r = 0; r < n_ranks; ++r) counts[r] = off[r + 1] - off[r];
         out->n = off[n_ranks];
         out->hashed = 1;
@@ -228,23 +252,94 @@ class Exec {
     std::map<std::pair<const Table*, int>, DCol> decoded_;
     std::map<std::pair<int, int>, std::vector<uint64_t>> vc_dir_;  // VARCHAR page directories
 
+    // ------------------------------------------------------------- columns
+    // bytes per value on the device (VARCHAR: a row id)
+    static int width_of(int32_t type) { return type == RJ_INT32 || type == RJ_VARCHAR ? 4 : 8; }
+    // a dense column over existing arrays (either may be none: no rows, no NULLs)
+    static DCol dense_col(int32_t type, const BufP& values, const BufP& valid = BufP()) {
+        DCol d;
+        d.type = type;
+        d.kind = COL_DENSE;
+        d.width = width_of(type);
+        d.hold = values;
+        d.ptr = ptr<uint8_t>(values);
+        d.hold_valid = valid;
+        d.valid = ptr<uint8_t>(valid);
+        return d;
+    }
+    // ... of `src`'s type, with its VARCHAR provenance
+    static DCol dense_like(const DCol& src, const BufP& values, const BufP& valid = BufP()) {
+        DCol d = dense_col(src.type, values, valid);
+        d.vc_table = src.vc_table;
+        d.vc_col = src.vc_col;
+        return d;
+    }
+    // ... over new arrays of `rows` values
+    DCol new_col(int32_t type, uint64_t rows, bool nullable) {
+        BufP values = ctx->buf(rows * width_of(type));
+        return dense_col(type, values, nullable ? ctx->buf(rows) : BufP());
+    }
+
+    static void check_rows(const Rel& r) {
+        if (r.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+    }
+
+    // `bytes` from the device into `dst`, waited for.  `dst` is the end of a copy that may still be
+    // queued when something throws: the stream drains before the exception travels on, so that the
+    // caller's variable outlives the copy.
+    void read_back(void* dst, const void* src, size_t bytes) {
+        try {
+            RJ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+            ctx->sync();
+        } catch (...) {
+            (void)hipStreamSynchronize(ctx->stream);
+            throw;
+        }
+    }
+
+    // Where the columns of a one-child node's output go: below the root into the Rel its parent reads,
+    // at the root into the Result as Page images.
+    struct Sink {
+        Exec*   E;
+        Result* res;  // the root's result, or nullptr below the root
+        Rel     out;
+        std::map<uint64_t, DCol>         made;     // per id ...
+        std::map<uint64_t, ResultColumn> encoded;  // ... and its pages at the root
+        Sink(Exec* e, Result* root_res, uint64_t rows) : E(e), res(root_res) {
+            out.n = rows;
+            if (res) res->num_rows = rows;
+        }
+        // a column of its own
+        void add(const DCol& d) {
+            if (res)
+                res->cols.push_back(E->col_to_result(d, out.n));
+            else
+                out.cols.push_back(d);
+        }
+        // a column that may be named several times: `make` runs, and the root encodes, once per id
+        template <class Make>
+        void add(uint64_t id, Make&& make) {
+            if (!made.count(id)) made[id] = make();
+            if (!res) {
+                out.cols.push_back(made.at(id));
+                return;
+            }
+            if (!encoded.count(id)) encoded[id] = E->col_to_result(made.at(id), out.n);
+            res->cols.push_back(encoded.at(id));
+        }
+    };
+
     // ------------------------------------------------------------- scan side
     DCol table_col(const Table* t, int c) {
         const TableColumn& tc = t->cols[c];
         if (tc.skipped) throw_fmt(RJ_ERR_ARG, "column was not uploaded (not referenced by a scan)");
-        DCol               d;
-        d.type = tc.type;
+        DCol d = dense_col(tc.type, BufP());
         d.tcol = &tc;
         if (tc.type == RJ_VARCHAR) {
             d.kind = COL_IOTA;
-            d.width = 4;
             return d;
         }
-        d.width = tc.type == RJ_INT32 ? 4 : 8;
-        if (t->num_rows == 0) {  // nothing to address (an empty shard): no validity to carry either
-            d.kind = COL_DENSE;
-            return d;
-        }
+        if (t->num_rows == 0) return d;  // nothing to address (an empty shard): no validity to carry either
         if (tc.regular) {
             d.kind = COL_PAGED;
             d.ptr = tc.dev_pages;
@@ -255,9 +350,8 @@ class Exec {
         if (it != decoded_.end()) return it->second;
         // K1: irregular pages (NULLs, short pages) -> dense values + validity
         uint64_t n = t->num_rows;
-        d.kind = COL_DENSE;
-        d.hold = ctx->buf(n * d.width);
-        d.hold_valid = ctx->buf(n);
+        d = new_col(tc.type, n, true);
+        d.tcol = &tc;
         RJ_HIP(hipMemsetAsync(d.hold->p, 0, n * d.width, ctx->stream));
         RJ_HIP(hipMemsetAsync(d.hold_valid->p, 0, n, ctx->stream));
         if (tc.n_pages) {
@@ -268,8 +362,6 @@ class Exec {
                                 row_base->as<uint32_t>(), n, d.hold->as<uint8_t>(),
                                 d.hold_valid->as<uint8_t>());
         }
-        d.ptr = d.hold->as<uint8_t>();
-        d.valid = d.hold_valid->as<uint8_t>();
         decoded_[key] = d;
         return d;
     }
@@ -357,29 +449,17 @@ class Exec {
         if (depth > 4096) throw_fmt(RJ_ERR_ARG, "plan too deep (cycle?)");
         const rj_node& n = plan->nodes[idx];
         if (n.kind == RJ_NODE_SCAN) return scan(n);
-        if (n.kind == RJ_NODE_AGG) {
-            Rel child = node(n.left, nullptr, depth + 1);
-            return agg(child, n, root_res);
-        }
-        if (n.kind == RJ_NODE_SELECT) {
-            Rel child = node(n.left, nullptr, depth + 1);
-            return select(child, n, root_res);
-        }
-        if (n.kind == RJ_NODE_SORT) {
-            Rel child = node(n.left, nullptr, depth + 1);
-            return sort(child, n, root_res, ordered);
-        }
-        if (n.kind == RJ_NODE_GROUP) {
-            Rel child = node(n.left, nullptr, depth + 1);
-            return group(child, n, root_res);
-        }
-        if (n.kind == RJ_NODE_WINDOW) {
-            Rel child = node(n.left, nullptr, depth + 1);
-            return window(child, n, root_res);
-        }
-        if (n.kind == RJ_NODE_MAP) {
-            Rel child = node(n.left, nullptr, depth + 1, root_res != nullptr || ordered);
-            return map(child, n, root_res);
+        const NodeKind* nk = node_kind(n.kind);
+        if (nk && nk->children == 1) {
+            Rel child = node(n.left, nullptr, depth + 1, n.kind == RJ_NODE_MAP && (root_res != nullptr || ordered));
+            switch (n.kind) {
+            case RJ_NODE_AGG: return agg(child, n, root_res);
+            case RJ_NODE_SELECT: return select(child, n, root_res);
+            case RJ_NODE_SORT: return sort(child, n, root_res, ordered);
+            case RJ_NODE_GROUP: return group(child, n, root_res);
+            case RJ_NODE_WINDOW: return window(child, n, root_res);
+            case RJ_NODE_MAP: return map(child, n, root_res);
+            }
         }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
@@ -787,26 +867,22 @@ class Exec {
         return (rows + rf - 1) / rf;
     }
 
-    Rel empty_rel(const JoinSpec& js, Result* root_res) {
+    // no rows of the declared types: typed columns, at the root with zero pages
+    Rel empty_rel(const int32_t* types, uint64_t n_types, Result* root_res) {
         Rel r;
         r.n = 0;
-        for (size_t k = 0; k < js.out_type.size(); ++k) {
-            DCol d;
-            d.type = js.out_type[k];
-            d.kind = COL_DENSE;
-            d.width = d.type == RJ_INT32 || d.type == RJ_VARCHAR ? 4 : 8;
-            r.cols.push_back(d);
-        }
-        if (root_res) {
-            root_res->num_rows = 0;
-            for (size_t k = 0; k < js.out_type.size(); ++k) {
-                ResultColumn rc;
-                rc.type = js.out_type[k];
-                root_res->cols.push_back(std::move(rc));
-            }
+        if (root_res) root_res->num_rows = 0;
+        for (uint64_t k = 0; k < n_types; ++k) {
+            r.cols.push_back(dense_col(types[k], BufP()));
+            if (!root_res) continue;
+            ResultColumn rc;
+            rc.type = types[k];
+            root_res->cols.push_back(std::move(rc));
         }
         return r;
     }
+    Rel empty_rel(const rj_node& n, Result* root_res) { return empty_rel(n.out_type, n.n_out, root_res); }
+    Rel empty_rel(const JoinSpec& js, Result* root_res) { return empty_rel(js.out_type.data(), js.out_type.size(), root_res); }
 
     // What a JoinNode decides before any tuple moves: key type, which columns each side
     // must deliver and how they travel (execute_hash_join, reference src/execute.cpp:266-282,
@@ -988,7 +1064,7 @@ class Exec {
             size_t k = 0;
             for (int c : s.wide_cols) refs[k++] = s.rel->cols[c].ref();
             if (s.valid_word >= 0)
-                refs[k++] = ColRef{s.vword ? s.vword->as<uint8_t>() : nullptr, nullptr, COL_DENSE, 4};
+                refs[k++] = ColRef{ptr<uint8_t>(s.vword), nullptr, COL_DENSE, 4};
             src.wide = s.wide;
             src.carry = refs[0];
             src.carry2 = refs[1];
@@ -1071,7 +1147,7 @@ class Exec {
         op.aosP = cp.P.aos3 ? 1 : 0;
     }
 
-    static OutStream out_stream(const BufP& b, int mode) { return OutStream{b ? b->as<uint8_t>() : nullptr, mode, 0}; }
+    static OutStream out_stream(const BufP& b, int mode) { return OutStream{ptr<uint8_t>(b), mode, 0}; }
     static OutStream out_stream(const Side& s) { return out_stream(s.stream, s.stream_mode); }
     // rows the streams of a first attempt hold when the result may exceed `rows`
     static uint64_t first_cap(uint64_t rows) { return std::min<uint64_t>(rows + 1024, 0xfffffff0ull); }
@@ -1106,8 +1182,7 @@ class Exec {
             e.finished.clear();
             finish_paged_streams(st, e, counters, cap);
             unsigned long long h = 0;
-            RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
+            read_back(&h, counters->p, 8);
             e.nrows = h;
             if (e.nrows <= cap) return e;
             if (K.attempts == 1)
@@ -1191,8 +1266,7 @@ class Exec {
             launch_join(L, KW, bs.CW, ps.CW, jp, cp->max_tasks + (PB.NP + ppw - 1) / ppw);
             if (diag) {
                 unsigned long long hd[16];
-                RJ_HIP(hipMemcpyAsync(hd, diag->p, sizeof hd, hipMemcpyDeviceToHost, ctx->stream));
-                ctx->sync();
+                read_back(hd, diag->p, sizeof hd);
                 static const char* names[] = {"loads issued", "table clear", "build", "count/probe",
                                               "prefix+barrier", "reserve", "emit"};
                 double tot = 0;
@@ -1437,7 +1511,6 @@ class Exec {
         s.rel = &child;
         s.key_col = n.left_attr;
         std::vector<AggOut> outs;
-        JoinSpec            js;  // (the declared types, for empty_rel)
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint32_t func = RJ_AGG_FUNC(n.out_idx[k]);
             const uint64_t col = RJ_AGG_COL(n.out_idx[k]);
@@ -1462,7 +1535,6 @@ class Exec {
             }
             if (type != expect) throw_fmt(RJ_ERR_ARG, "aggregation: declared type differs from the function's result type");
             outs.push_back(AggOut{func, (int)col, -1});
-            js.out_type.push_back(type);
         }
         // how the aggregated columns travel with the key
         const int KW = kc.type == RJ_INT32 ? 1 : 2;
@@ -1489,8 +1561,8 @@ class Exec {
                       "another word)",
                       words + (any_null ? 1 : 0), MAX_WORDS - KW, KW == 1 ? "INT32" : "INT64");
         }
-        if (child.n == 0) return empty_rel(js, root_res);
-        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        if (child.n == 0) return empty_rel(n, root_res);
+        check_rows(child);
         for (AggOut& o : outs)
             for (size_t i = 0; i < s.wide_cols.size(); ++i)
                 if (o.func >= RJ_AGG_COUNT && s.wide_cols[i] == o.col) o.slot = (int)i;
@@ -1521,8 +1593,7 @@ class Exec {
             }
         }
         prepare_wide(s);
-        JoinState st;  // (integer keys, not pre-hashed)
-        const TupleSrc src = make_src(st, s, js);
+        const TupleSrc src = make_src(JoinState(), s, JoinSpec());  // (integer keys, not pre-hashed)
         const uint32_t bits = agg_bits(child.n);
         const uint64_t cap = child.n + 1;  // every row its own group, and the NULL-key group
         if (ctx->tune.diag >= 2)
@@ -1534,13 +1605,13 @@ class Exec {
             BufP key, keyvalid, rows, nn[AGG_MAX_COLS], sum[AGG_MAX_COLS], mn[AGG_MAX_COLS], mx[AGG_MAX_COLS];
         } O, M;
         auto fill = [](AggArrays& a, const Arrays& b) {
-            a.key = b.key ? b.key->as<uint8_t>() : nullptr;
-            a.rows = b.rows ? b.rows->as<unsigned long long>() : nullptr;
+            a.key = ptr<uint8_t>(b.key);
+            a.rows = ptr<unsigned long long>(b.rows);
             for (int i = 0; i < AGG_MAX_COLS; ++i) {
-                a.nn[i] = b.nn[i] ? b.nn[i]->as<unsigned long long>() : nullptr;
-                a.sum[i] = b.sum[i] ? b.sum[i]->as<unsigned long long>() : nullptr;
-                a.mn[i] = b.mn[i] ? b.mn[i]->as<long long>() : nullptr;
-                a.mx[i] = b.mx[i] ? b.mx[i]->as<long long>() : nullptr;
+                a.nn[i] = ptr<unsigned long long>(b.nn[i]);
+                a.sum[i] = ptr<unsigned long long>(b.sum[i]);
+                a.mn[i] = ptr<long long>(b.mn[i]);
+                a.mx[i] = ptr<long long>(b.mx[i]);
             }
         };
         if (need_key) O.key = ctx->buf(cap * KW * 4);
@@ -1553,7 +1624,7 @@ class Exec {
             if (ap.col[i].need & AGG_NEED_MAX) O.mx[i] = ctx->buf(cap * 8);
         }
         fill(ap.out, O);
-        ap.out_keyvalid = O.keyvalid ? O.keyvalid->as<uint8_t>() : nullptr;
+        ap.out_keyvalid = ptr<uint8_t>(O.keyvalid);
         ap.out_cap = cap;
         ap.src = src;
 
@@ -1570,8 +1641,7 @@ class Exec {
             // the merge table is sized from the tuples that sit in heavy partitions (an upper bound of
             // their groups), capped at first: a partition is usually heavy because its keys repeat
             uint32_t n_heavy = 0;
-            RJ_HIP(hipMemcpyAsync(&n_heavy, counters->as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
+            read_back(&n_heavy, counters->as<uint32_t>() + 2, 4);
             n_heavy = std::min(n_heavy, max_tasks);
             uint64_t heavy_tuples = std::min<uint64_t>(P.n_tuples, (uint64_t)n_heavy * JN_HEAVY);
             if (attempt == 0) heavy_tuples = std::min<uint64_t>(heavy_tuples, 1u << 20);
@@ -1605,8 +1675,7 @@ class Exec {
                                                                                       (uint64_t)ctx->compute_units() * 4));
             launch_agg_emit(L, KW, ap, mgrid);
             uint32_t h[4] = {0, 0, 0, 0};
-            RJ_HIP(hipMemcpyAsync(h, counters->p, 16, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
+            read_back(h, counters->p, 16);
             nrows = (uint64_t)h[0] | ((uint64_t)h[1] << 32);
             if (!h[3]) break;
             // more groups in heavy partitions than the capped table holds: once more (the rounds of
@@ -1638,41 +1707,25 @@ class Exec {
         }
 
         // ---- the output columns: accumulator arrays as they are, narrowed or with validity
-        Rel out;
-        out.n = nrows;
+        Sink sink(this, root_res, nrows);
         for (size_t k = 0; k < outs.size(); ++k) {
             const AggOut& o = outs[k];
-            DCol          d;
-            d.type = js.out_type[k];
-            d.kind = COL_DENSE;
-            d.width = d.type == RJ_INT32 ? 4 : 8;
-            BufP values, valid;
-            if (o.func == RJ_AGG_KEY) {
-                values = O.key;
-                valid = O.keyvalid;
-            } else if (o.func == RJ_AGG_COUNT_STAR) {
-                values = O.rows;
-            } else if (o.func == RJ_AGG_COUNT) {
-                values = O.nn[o.slot];
-            } else {
+            const int32_t type = n.out_type[k];
+            sink.add([&] {
+                if (o.func == RJ_AGG_KEY) return dense_col(type, O.key, O.keyvalid);
+                if (o.func == RJ_AGG_COUNT_STAR) return dense_col(type, O.rows);
+                if (o.func == RJ_AGG_COUNT) return dense_col(type, O.nn[o.slot]);
                 const BufP& acc = o.func == RJ_AGG_SUM ? O.sum[o.slot] : (o.func == RJ_AGG_MIN ? O.mn[o.slot] : O.mx[o.slot]);
-                const bool  nullable = s.nullable(o.col);
-                values = acc;
-                if (d.width == 4) values = ctx->buf(std::max<uint64_t>(nrows, 1) * 4);
-                if (nullable) valid = ctx->buf(std::max<uint64_t>(nrows, 1));
-                if (d.width == 4 || nullable)
+                const bool  nullable = s.nullable(o.col), narrow = width_of(type) == 4;
+                BufP        values = narrow ? ctx->buf(std::max<uint64_t>(nrows, 1) * 4) : acc;
+                BufP        valid = nullable ? ctx->buf(std::max<uint64_t>(nrows, 1)) : BufP();
+                if (narrow || nullable)
                     launch_agg_column(L, acc->as<unsigned long long>(), nullable ? O.nn[o.slot]->as<unsigned long long>() : nullptr,
-                                      nrows, d.width, d.width == 4 ? values->as<uint8_t>() : nullptr,
-                                      valid ? valid->as<uint8_t>() : nullptr);
-            }
-            d.hold = values;
-            d.ptr = values->as<uint8_t>();
-            d.hold_valid = valid;
-            d.valid = valid ? valid->as<uint8_t>() : nullptr;
-            out.cols.push_back(d);
+                                      nrows, narrow ? 4 : 8, narrow ? values->as<uint8_t>() : nullptr, ptr<uint8_t>(valid));
+                return dense_col(type, values, valid);
+            }());
         }
-        if (root_res) rel_to_result(out, *root_res);
-        return out;
+        return sink.out;
     }
 
     // ---------------------------------------------------------------- selection
@@ -1737,22 +1790,15 @@ class Exec {
     }
 
     Rel select(Rel& child, const rj_node& n, Result* root_res) {
-        const size_t cw = child.cols.size();
-        JoinSpec     js;  // (the declared types, for empty_rel)
-        for (uint64_t k = 0; k < n.n_out; ++k) {
-            if (n.out_idx[k] >= cw) throw_fmt(RJ_ERR_ARG, "select: output attr out of range");
-            if (child.cols[n.out_idx[k]].type != n.out_type[k])
-                throw_fmt(RJ_ERR_ARG, "select: declared type differs from the child column's type");
-            js.out_type.push_back(n.out_type[k]);
-        }
+        check_projection("select", child, n);
         const uint64_t      n_ops = RJ_SELECT_N_OPS(&n);
         const rj_filter_op* ops = RJ_SELECT_OPS(&n);
         if (n_ops > (uint64_t)SEL_MAX_OPS) throw_fmt(RJ_ERR_UNSUPPORTED, "select: filter longer than %d operations", SEL_MAX_OPS);
         if (n_ops && !ops) throw_fmt(RJ_ERR_ARG, "select: %llu filter operations but a NULL program pointer", (unsigned long long)n_ops);
         std::unique_ptr<SelectProg> prog(new SelectProg());
         select_program(child, ops, n_ops, *prog);
-        if (child.n == 0) return empty_rel(js, root_res);
-        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        if (child.n == 0) return empty_rel(n, root_res);
+        check_rows(child);
 
         // ---- the rows that pass: ids[0 .. nrows); no program = every row, and no list at all
         uint64_t nrows = child.n;
@@ -1768,17 +1814,16 @@ class Exec {
                 launch_select(L, dprog->as<SelectProg>(), (uint32_t)n_ops, (uint32_t)child.n, ids->as<uint32_t>(),
                               counters->as<unsigned long long>(),
                               (uint32_t)std::min<uint64_t>(tiles, (uint64_t)ctx->compute_units() * 8));
-                RJ_HIP(hipMemcpyAsync(&h, counters->p, 8, hipMemcpyDeviceToHost, ctx->stream));
-                ctx->sync();
+                read_back(&h, counters->p, 8);
             } catch (...) {
-                // `prog` and `h` are the ends of copies that may still be queued: they outlive them
+                // `prog` too is the end of a copy that may still be queued: it outlives it
                 (void)hipStreamSynchronize(ctx->stream);
                 throw;
             }
             nrows = h;
             if (nrows > child.n) throw_fmt(RJ_ERR_DEVICE, "select kept %llu rows out of %llu", (unsigned long long)nrows,
                                            (unsigned long long)child.n);
-            if (nrows == 0) return empty_rel(js, root_res);
+            if (nrows == 0) return empty_rel(n, root_res);
             if (nrows < child.n / 2) {  // (as the aggregation's arrays: nobody holds on to the bound's memory)
                 BufP small = ctx->buf(nrows * 4);
                 RJ_HIP(hipMemcpyAsync(small->p, ids->p, nrows * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1789,75 +1834,50 @@ class Exec {
             fprintf(stderr, "[rj diag] select rows=%llu ops=%llu kept=%llu\n", (unsigned long long)child.n, (unsigned long long)n_ops,
                     (unsigned long long)nrows);
 
-        return emit_rows(child, n, ids, ids ? ids->as<uint32_t>() : nullptr, nrows, root_res);
+        return emit_rows(child, n.out_idx, n.n_out, ids, ptr<uint32_t>(ids), nrows, root_res);
     }
 
-    // The tail of a selection and of a sort: output row i is row idx[i] of `child` (nrows of them; idx
-    // points into `ids`, in this order; nullptr = the child's own rows, all of them).  Every distinct
-    // output column is gathered once — at the root straight into Page images.
-    Rel emit_rows(const Rel& child, const rj_node& n, const BufP& ids, const uint32_t* idx, uint64_t nrows, Result* root_res) {
-        // ---- the output columns; a child column named several times is materialised once
-        const bool               is_root = root_res != nullptr;
-        std::map<uint64_t, DCol> made;
-        std::map<uint64_t, ResultColumn> made_rc;
-        Rel out;
-        out.n = nrows;
-        if (is_root) root_res->num_rows = nrows;
+    // a projection's outputs (select, sort): child columns under their own types
+    static void check_projection(const char* what, const Rel& child, const rj_node& n) {
         for (uint64_t k = 0; k < n.n_out; ++k) {
-            const uint64_t c = n.out_idx[k];
-            const DCol&    src = child.cols[c];
-            if (!made.count(c)) {
-                DCol d = src;  // (type, width, VARCHAR provenance; without a program the column itself)
-                if (idx && src.kind == COL_IOTA) {
-                    d.kind = COL_DENSE;  // row ids of the base table ARE the list
-                    d.hold = ids;
-                    d.ptr = reinterpret_cast<const uint8_t*>(idx);
-                    d.tcol = nullptr;
-                } else if (idx) {
-                    // a root column without NULLs goes straight into its Page images
-                    const bool to_pages = is_root && src.type != RJ_VARCHAR && src.valid == nullptr;
-                    const int  mode = to_pages ? (src.width == 4 ? ST_PAGED32 : ST_PAGED64) : (src.width == 4 ? ST_DENSE32 : ST_DENSE64);
-                    d.kind = to_pages ? COL_PAGED : COL_DENSE;
-                    d.tcol = nullptr;
-                    d.hold = ctx->buf(stream_bytes(mode, nrows));
-                    d.ptr = d.hold->as<uint8_t>();
-                    d.hold_valid = src.valid ? ctx->buf(nrows) : BufP();
-                    d.valid = d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr;
-                    launch_gather(L, src.ref(), idx, nrows, OutStream{d.hold->as<uint8_t>(), mode, 0},
-                                  d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
-                    if (to_pages) launch_finish_pages(L, d.hold->as<uint8_t>(), nrows, src.width);
-                }
-                made[c] = d;
-            }
-            const DCol& d = made.at(c);
-            if (!is_root) {
-                out.cols.push_back(d);
-                continue;
-            }
-            if (!made_rc.count(c)) {
-                ResultColumn rc;
-                if (d.type == RJ_VARCHAR) {
-                    rc.type = d.type;
-                    BufP            rowids;
-                    const uint32_t* rows = reinterpret_cast<const uint32_t*>(d.ptr);  // (`idx` itself may start inside `ids`)
-                    if (d.kind == COL_IOTA) {  // (a projection only: every row of the base table, in order)
-                        rowids = ctx->buf(nrows * 4);
-                        launch_gather(L, d.ref(), nullptr, nrows, OutStream{rowids->as<uint8_t>(), ST_DENSE32, 0}, nullptr);
-                        rows = rowids->as<uint32_t>();
-                    }
-                    varchar_root(rows, nrows, d, rc);
-                } else if (idx && d.kind == COL_PAGED) {  // gathered into Page images above
-                    rc.type = d.type;
-                    rc.dev_pages = d.hold;
-                    rc.n_pages = pages_for(nrows, d.width);
-                } else {
-                    rc = col_to_result(d, nrows);
-                }
-                made_rc[c] = std::move(rc);
-            }
-            root_res->cols.push_back(made_rc.at(c));
+            if (n.out_idx[k] >= child.cols.size()) throw_fmt(RJ_ERR_ARG, "%s: output attr out of range", what);
+            if (child.cols[n.out_idx[k]].type != n.out_type[k])
+                throw_fmt(RJ_ERR_ARG, "%s: declared type differs from the child column's type", what);
         }
-        return out;
+    }
+
+    // The tail of a selection and of a sort, and the passed-through columns of a window and a map node:
+    // columns cols[0 .. n_cols) of `child` go to `sink`, output row i being row idx[i] (sink.out.n of
+    // them; idx points into `ids`, in this order; nullptr = the child's own rows, all of them).  Every
+    // distinct column is gathered once — at the root straight into Page images.
+    void emit_rows(const Rel& child, const uint64_t* cols, uint64_t n_cols, const BufP& ids, const uint32_t* idx, Sink& sink) {
+        const uint64_t nrows = sink.out.n;
+        for (uint64_t k = 0; k < n_cols; ++k) {
+            const DCol& src = child.cols[cols[k]];
+            sink.add(cols[k], [&] {
+                if (!idx) return src;  // (without a list the column itself)
+                if (src.kind == COL_IOTA) {  // row ids of the base table ARE the list
+                    DCol d = dense_like(src, ids);
+                    d.ptr = reinterpret_cast<const uint8_t*>(idx);  // (`idx` itself may start inside `ids`)
+                    return d;
+                }
+                // a root column without NULLs goes straight into its Page images
+                const bool to_pages = sink.res && src.type != RJ_VARCHAR && src.valid == nullptr;
+                const int  mode = to_pages ? (src.width == 4 ? ST_PAGED32 : ST_PAGED64) : (src.width == 4 ? ST_DENSE32 : ST_DENSE64);
+                BufP       values = ctx->buf(stream_bytes(mode, nrows));
+                DCol       d = dense_like(src, values, src.valid ? ctx->buf(nrows) : BufP());
+                if (to_pages) d.kind = COL_PAGED;
+                launch_gather(L, src.ref(), idx, nrows, OutStream{values->as<uint8_t>(), mode, 0}, ptr<uint8_t>(d.hold_valid));
+                if (to_pages) launch_finish_pages(L, values->as<uint8_t>(), nrows, src.width);
+                return d;
+            });
+        }
+    }
+    Rel emit_rows(const Rel& child, const uint64_t* cols, uint64_t n_cols, const BufP& ids, const uint32_t* idx, uint64_t nrows,
+                  Result* root_res) {
+        Sink sink(this, root_res, nrows);
+        emit_rows(child, cols, n_cols, ids, idx, sink);
+        return sink.out;
     }
 
     // ---------------------------------------------------------------------- sort
@@ -1876,17 +1896,11 @@ class Exec {
         BufP           keys = ctx->buf((uint64_t)n * W);
         BufP           hist = ctx->buf(SORT_HIST_WORDS * 4);
         std::vector<uint32_t> h(SORT_HIST_WORDS);
-        try {
-            RJ_HIP(hipMemsetAsync(hist->p, 0, SORT_HIST_WORDS * 4, ctx->stream));
-            const uint32_t chunks = n / SORT_THREADS + (n % SORT_THREADS != 0);
-            launch_sort_encode(L, c.ref(), perm ? perm->as<uint32_t>() : nullptr, n, c.type == RJ_FP64, flags, keys->as<uint8_t>(),
-                               hist->as<uint32_t>(), std::min<uint32_t>(chunks, (uint32_t)ctx->compute_units() * 8));
-            RJ_HIP(hipMemcpyAsync(h.data(), hist->p, SORT_HIST_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);  // `h` is the end of a copy that may still be queued
-            throw;
-        }
+        RJ_HIP(hipMemsetAsync(hist->p, 0, SORT_HIST_WORDS * 4, ctx->stream));
+        const uint32_t chunks = n / SORT_THREADS + (n % SORT_THREADS != 0);
+        launch_sort_encode(L, c.ref(), ptr<uint32_t>(perm), n, c.type == RJ_FP64, flags, keys->as<uint8_t>(), hist->as<uint32_t>(),
+                           std::min<uint32_t>(chunks, (uint32_t)ctx->compute_units() * 8));
+        read_back(h.data(), hist->p, SORT_HIST_WORDS * 4);
         std::vector<int> passes;  // digit positions with more than one non-empty bin, the NULL digit last
         for (int p = 0; p <= SORT_NULL_DIGIT; ++p) {
             if (p >= W && p != SORT_NULL_DIGIT) continue;
@@ -1908,7 +1922,7 @@ class Exec {
             BufP           ids_out = spare ? spare : ctx->buf((uint64_t)n * 4);
             const int      mode = flag ? SORT_FLAG : (W == 4 ? SORT_KEY32 : SORT_KEY64);
             const uint32_t null_digit = (flags & RJ_SORT_NULLS_FIRST) ? 0u : 1u, shift = flag ? 0u : 8u * (uint32_t)p;
-            const uint32_t* in = ids_in ? ids_in->as<uint32_t>() : nullptr;
+            const uint32_t* in = ptr<uint32_t>(ids_in);
             launch_sort_count(L, mode, keys->as<uint8_t>(), in, c.valid, null_digit, n, shift, table->as<uint32_t>());
             launch_sort_scan(L, hist->as<uint32_t>() + (size_t)p * SORT_RADIX, n, table->as<uint32_t>());
             launch_sort_scatter(L, mode, keys->as<uint8_t>(), in, c.valid, null_digit, n, shift, table->as<uint32_t>(),
@@ -1920,51 +1934,58 @@ class Exec {
         perm = ids_in;
     }
 
-    Rel sort(Rel& child, const rj_node& n, Result* root_res, bool ordered = false) {
-        const size_t cw = child.cols.size();
-        JoinSpec     js;  // (the declared types, for empty_rel)
-        for (uint64_t k = 0; k < n.n_out; ++k) {
-            if (n.out_idx[k] >= cw) throw_fmt(RJ_ERR_ARG, "sort: output attr out of range");
-            if (child.cols[n.out_idx[k]].type != n.out_type[k])
-                throw_fmt(RJ_ERR_ARG, "sort: declared type differs from the child column's type");
-            js.out_type.push_back(n.out_type[k]);
-        }
-        const uint64_t     n_keys = RJ_SORT_N_KEYS(&n), limit = RJ_SORT_LIMIT(&n), offset = RJ_SORT_OFFSET(&n);
-        const rj_sort_key* keys = RJ_SORT_KEYS(&n);
-        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "sort: more than %d keys", SORT_MAX_KEYS);
-        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "sort: %llu keys but a NULL key pointer", (unsigned long long)n_keys);
+    // The key list of a sort, a grouping or a window node (`what`), checked in the order of the keys
+    // before the child's rows are looked at.
+    static std::vector<rj_sort_key> checked_keys(const char* what, const Rel& child, const rj_sort_key* keys, uint64_t n_keys) {
+        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "%s: more than %d keys", what, SORT_MAX_KEYS);
+        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "%s: %llu keys but a NULL key pointer", what, (unsigned long long)n_keys);
         for (uint64_t k = 0; k < n_keys; ++k) {
-            if (keys[k].column < 0 || (uint64_t)keys[k].column >= cw) throw_fmt(RJ_ERR_ARG, "sort: key column out of range");
-            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "sort: unknown key flags %d", keys[k].flags);
+            if (keys[k].column < 0 || (uint64_t)keys[k].column >= child.cols.size())
+                throw_fmt(RJ_ERR_ARG, "%s: key column out of range", what);
+            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "%s: unknown key flags %d", what, keys[k].flags);
             if (child.cols[(size_t)keys[k].column].type == RJ_VARCHAR)
-                throw_fmt(RJ_ERR_UNSUPPORTED, "sort: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
-                                              "are not read here", keys[k].column);
+                throw_fmt(RJ_ERR_UNSUPPORTED, "%s: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
+                                              "are not read here", what, keys[k].column);
         }
-        if (child.n == 0) return empty_rel(js, root_res);
-        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
+        return std::vector<rj_sort_key>(keys, keys + n_keys);
+    }
+    // The rows of `child` in the order of the keys: the permutation, or none where no pass moved a row.
+    // The last key first; a key behind an earlier one on the same column is skipped: nothing is left
+    // to order there, rows that tie on the column tie again.
+    BufP order_by(const Rel& child, const std::vector<rj_sort_key>& keys) {
+        BufP perm;
+        for (size_t k = keys.size(); k-- > 0;) {
+            bool shadowed = false;
+            for (size_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
+            if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, (uint32_t)child.n, perm);
+        }
+        return perm;
+    }
+
+    Rel sort(Rel& child, const rj_node& n, Result* root_res, bool ordered = false) {
+        check_projection("sort", child, n);
+        const uint64_t limit = RJ_SORT_LIMIT(&n), offset = RJ_SORT_OFFSET(&n);
+        const std::vector<rj_sort_key> keys = checked_keys("sort", child, RJ_SORT_KEYS(&n), RJ_SORT_N_KEYS(&n));
+        if (child.n == 0) return empty_rel(n, root_res);
+        check_rows(child);
         // the slice [begin, begin + count): offset + limit is never formed
         const uint64_t begin = std::min<uint64_t>(offset, child.n), count = std::min<uint64_t>(limit, child.n - begin);
-        if (count == 0) return empty_rel(js, root_res);
+        if (count == 0) return empty_rel(n, root_res);
         const bool whole = count == child.n;
         // below another node the order is nobody's business: without a slice the child passes through
         // (not below the MAPs of a root, which keep the order: `ordered`)
         BufP perm;
-        if (root_res || ordered || !whole) {
-            for (uint64_t k = n_keys; k-- > 0;) {
-                bool shadowed = false;  // behind the same column nothing is left to order: rows that tie on it tie again
-                for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
-                if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, (uint32_t)child.n, perm);
-            }
-        }
+        if (root_res || ordered || !whole) perm = order_by(child, keys);
         if (ctx->tune.diag >= 2)
             fprintf(stderr, "[rj diag] sort rows=%llu keys=%llu begin=%llu count=%llu permuted=%d\n", (unsigned long long)child.n,
-                    (unsigned long long)n_keys, (unsigned long long)begin, (unsigned long long)count, perm ? 1 : 0);
+                    (unsigned long long)keys.size(), (unsigned long long)begin, (unsigned long long)count, perm ? 1 : 0);
+        const uint32_t* idx = perm ? perm->as<uint32_t>() + begin : nullptr;
         if (!perm && !whole) {  // no pass moved a row: the slice is a run of positions
             perm = ctx->buf(count * 4);
+            idx = perm->as<uint32_t>();
             launch_sort_iota(L, perm->as<uint32_t>(), (uint32_t)begin, (uint32_t)count);
-            return emit_rows(child, n, perm, perm->as<uint32_t>(), count, root_res);
         }
-        return emit_rows(child, n, perm, perm ? perm->as<uint32_t>() + begin : nullptr, count, root_res);
+        return emit_rows(child, n.out_idx, n.n_out, perm, idx, count, root_res);
     }
 
     // -------------------------------------------------------------------- grouping
@@ -1979,20 +2000,12 @@ class Exec {
         BufP nn, sum, mn, mx;
     };
     Rel group(Rel& child, const rj_node& n, Result* root_res) {
-        const size_t       cw = child.cols.size();
-        const uint64_t     n_keys = RJ_GROUP_N_KEYS(&n);
-        const rj_sort_key* keys = RJ_GROUP_KEYS(&n);
-        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "group: more than %d keys", SORT_MAX_KEYS);
-        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "group: %llu keys but a NULL key pointer", (unsigned long long)n_keys);
-        std::vector<int> key_cols;  // the distinct key columns, the first key's first
-        for (uint64_t k = 0; k < n_keys; ++k) {
-            if (keys[k].column < 0 || (uint64_t)keys[k].column >= cw) throw_fmt(RJ_ERR_ARG, "group: key column out of range");
-            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "group: unknown key flags %d", keys[k].flags);
-            if (child.cols[(size_t)keys[k].column].type == RJ_VARCHAR)
-                throw_fmt(RJ_ERR_UNSUPPORTED, "group: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
-                                              "are not read here", keys[k].column);
-            if (std::find(key_cols.begin(), key_cols.end(), keys[k].column) == key_cols.end()) key_cols.push_back(keys[k].column);
-        }
+        const size_t                   cw = child.cols.size();
+        const std::vector<rj_sort_key> keys = checked_keys("group", child, RJ_GROUP_KEYS(&n), RJ_GROUP_N_KEYS(&n));
+        const uint64_t                 n_keys = keys.size();
+        std::vector<int>               key_cols;  // the distinct key columns, the first key's first
+        for (const rj_sort_key& key : keys)
+            if (std::find(key_cols.begin(), key_cols.end(), key.column) == key_cols.end()) key_cols.push_back(key.column);
         struct Out {
             uint32_t func;
             int      col;
@@ -2000,7 +2013,6 @@ class Exec {
         std::vector<Out>        outs;
         std::map<int, GroupCol> agg;  // per distinct aggregated column
         bool                    want_rows = false;
-        JoinSpec                js;  // (the declared types, for empty_rel)
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint32_t func = RJ_AGG_FUNC(n.out_idx[k]);
             const uint64_t col = RJ_AGG_COL(n.out_idx[k]);
@@ -2033,64 +2045,44 @@ class Exec {
             }
             if (n.out_type[k] != expect) throw_fmt(RJ_ERR_ARG, "group: declared type differs from the function's result type");
             outs.push_back(Out{func, (int)col});
-            js.out_type.push_back(n.out_type[k]);
         }
-        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
-        if (child.n == 0 && n_keys) return empty_rel(js, root_res);
+        check_rows(child);
+        if (child.n == 0 && n_keys) return empty_rel(n, root_res);
         const uint32_t rows = (uint32_t)child.n;
 
         // ---- the order, the heads, the group count
         BufP     perm, masks, tile_base;
         uint32_t G = 1;
         if (n_keys) {
-            for (uint64_t k = n_keys; k-- > 0;) {
-                bool shadowed = false;  // (as in sort(): behind the same column nothing is left to order)
-                for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
-                if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, rows, perm);
-            }
+            perm = order_by(child, keys);
             const uint32_t n_tiles = rows / GROUP_TILE + (rows % GROUP_TILE != 0);
             masks = ctx->buf(((uint64_t)rows + 63) / 64 * 8);
             tile_base = ctx->buf(((uint64_t)n_tiles + 1) * 4);
             BufP tile_heads = ctx->buf((uint64_t)n_tiles * 4), total = ctx->buf(4);
             for (size_t k = 0; k < key_cols.size(); ++k) {
                 const DCol& c = child.cols[(size_t)key_cols[k]];
-                launch_group_heads(L, c.ref(), perm ? perm->as<uint32_t>() : nullptr, rows, c.type == RJ_FP64, k == 0,
-                                   k + 1 == key_cols.size(), masks->as<unsigned long long>(), tile_heads->as<uint32_t>());
+                launch_group_heads(L, c.ref(), ptr<uint32_t>(perm), rows, c.type == RJ_FP64, k == 0, k + 1 == key_cols.size(),
+                                   masks->as<unsigned long long>(), tile_heads->as<uint32_t>());
             }
             launch_group_scan(L, tile_heads->as<uint32_t>(), rows, tile_base->as<uint32_t>(), total->as<uint32_t>());
-            try {
-                RJ_HIP(hipMemcpyAsync(&G, total->p, 4, hipMemcpyDeviceToHost, ctx->stream));
-                ctx->sync();
-            } catch (...) {
-                (void)hipStreamSynchronize(ctx->stream);  // `G` is the end of a copy that may still be queued
-                throw;
-            }
+            read_back(&G, total->p, 4);
             if (G == 0 || G > rows) throw_fmt(RJ_ERR_DEVICE, "group: %u groups out of %u rows", G, rows);
         }
         if (ctx->tune.diag >= 2)
             fprintf(stderr, "[rj diag] group rows=%u keys=%llu groups=%u permuted=%d columns=%zu\n", rows, (unsigned long long)n_keys, G,
                     perm ? 1 : 0, agg.size());
-        const uint32_t*           dperm = perm ? perm->as<uint32_t>() : nullptr;
-        const unsigned long long* dmasks = masks ? masks->as<unsigned long long>() : nullptr;
-        const uint32_t*           dbase = tile_base ? tile_base->as<uint32_t>() : nullptr;
+        const uint32_t*           dperm = ptr<uint32_t>(perm);
+        const unsigned long long* dmasks = ptr<unsigned long long>(masks);
+        const uint32_t*           dbase = ptr<uint32_t>(tile_base);
 
         // ---- the keys that are output: one array per distinct column
         std::map<int, DCol> key_out;
         for (const Out& o : outs) {
             if (o.func != RJ_AGG_KEY || key_out.count(o.col)) continue;
             const DCol& c = child.cols[(size_t)o.col];
-            DCol        d;
-            d.type = c.type;
-            d.kind = COL_DENSE;
-            d.width = c.width;
-            d.hold = ctx->buf((uint64_t)G * d.width);
-            d.ptr = d.hold->as<uint8_t>();
-            if (c.valid) {
-                d.hold_valid = ctx->buf(G);
-                d.valid = d.hold_valid->as<uint8_t>();
-            }
+            const DCol  d = new_col(c.type, G, c.valid != nullptr);
             launch_group_keys(L, c.ref(), dperm, rows, c.type == RJ_FP64, dmasks, dbase, G, d.hold->as<uint8_t>(),
-                              d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
+                              ptr<uint8_t>(d.hold_valid));
             key_out[o.col] = d;
         }
 
@@ -2098,7 +2090,7 @@ class Exec {
         const uint32_t max_grid = ctx->tune.group_grid > 0 ? (uint32_t)ctx->tune.group_grid : (uint32_t)ctx->compute_units() * 8u;
         BufP           rows_acc = want_rows ? ctx->buf((uint64_t)G * 8) : BufP();
         bool           rows_done = !want_rows;
-        auto           ull = [](const BufP& b) { return b ? b->as<unsigned long long>() : nullptr; };
+        using ull = unsigned long long;
         for (auto& kv : agg) {
             const DCol& c = child.cols[(size_t)kv.first];
             GroupCol&   g = kv.second;
@@ -2106,55 +2098,39 @@ class Exec {
             if (g.want_sum) g.sum = ctx->buf((uint64_t)G * 8);
             if (g.want_mn) g.mn = ctx->buf((uint64_t)G * 8);
             if (g.want_mx) g.mx = ctx->buf((uint64_t)G * 8);
-            const GroupAcc acc{rows_done ? nullptr : ull(rows_acc), ull(g.nn), ull(g.sum), ull(g.mn), ull(g.mx)};
+            const GroupAcc acc{rows_done ? nullptr : ptr<ull>(rows_acc), ptr<ull>(g.nn), ptr<ull>(g.sum), ptr<ull>(g.mn), ptr<ull>(g.mx)};
             const ColRef   ref = c.ref();
             launch_group_reduce(L, &ref, dperm, rows, c.type == RJ_FP64, dmasks, dbase, G, acc, max_grid);
             rows_done = true;
         }
         if (!rows_done) {
-            const GroupAcc acc{ull(rows_acc), nullptr, nullptr, nullptr, nullptr};
+            const GroupAcc acc{ptr<ull>(rows_acc), nullptr, nullptr, nullptr, nullptr};
             launch_group_reduce(L, nullptr, dperm, rows, false, dmasks, dbase, G, acc, max_grid);
         }
 
         // ---- the output columns
-        Rel out;
-        out.n = G;
+        Sink sink(this, root_res, G);
         for (size_t k = 0; k < outs.size(); ++k) {
-            const Out& o = outs[k];
-            if (o.func == RJ_AGG_KEY) {
-                out.cols.push_back(key_out.at(o.col));
-                continue;
-            }
-            DCol d;
-            d.type = js.out_type[k];
-            d.kind = COL_DENSE;
-            d.width = d.type == RJ_INT32 ? 4 : 8;
-            if (o.func == RJ_AGG_COUNT_STAR) {
-                d.hold = rows_acc;
-            } else if (o.func == RJ_AGG_COUNT) {
-                d.hold = agg.at(o.col).nn;
-            } else {
+            const Out&    o = outs[k];
+            const int32_t type = n.out_type[k];
+            sink.add([&] {
+                if (o.func == RJ_AGG_KEY) return key_out.at(o.col);
+                if (o.func == RJ_AGG_COUNT_STAR) return dense_col(type, rows_acc);
+                if (o.func == RJ_AGG_COUNT) return dense_col(type, agg.at(o.col).nn);
                 const GroupCol& g = agg.at(o.col);
                 const DCol&     c = child.cols[(size_t)o.col];
                 const BufP&     acc = o.func == RJ_AGG_SUM ? g.sum : (o.func == RJ_AGG_MIN ? g.mn : g.mx);
                 // NULL where the group has no non-NULL value: a nullable column, or the one row over no rows
                 const bool nullable = c.valid != nullptr || rows == 0;
                 const int  decode = o.func == RJ_AGG_SUM ? GROUP_RAW : (c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64));
-                if (decode == GROUP_RAW && !nullable) {
-                    d.hold = acc;
-                } else {
-                    d.hold = ctx->buf((uint64_t)G * d.width);
-                    if (nullable) d.hold_valid = ctx->buf(G);
-                    launch_group_column(L, acc->as<unsigned long long>(), nullable ? g.nn->as<unsigned long long>() : nullptr, G, decode,
-                                        d.width, d.hold->as<uint8_t>(), d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
-                }
-            }
-            d.ptr = d.hold->as<uint8_t>();
-            d.valid = d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr;
-            out.cols.push_back(d);
+                if (decode == GROUP_RAW && !nullable) return dense_col(type, acc);
+                const DCol d = new_col(type, G, nullable);
+                launch_group_column(L, acc->as<ull>(), nullable ? g.nn->as<ull>() : nullptr, G, decode, d.width, d.hold->as<uint8_t>(),
+                                    ptr<uint8_t>(d.hold_valid));
+                return d;
+            }());
         }
-        if (root_res) rel_to_result(out, *root_res);
-        return out;
+        return sink.out;
     }
 
     // ---------------------------------------------------------------------- window
@@ -2170,20 +2146,14 @@ class Exec {
         BufP nn, sum, mn, mx;
     };
     Rel window(Rel& child, const rj_node& n, Result* root_res) {
-        const size_t       cw = child.cols.size();
-        const uint64_t     n_keys = RJ_WINDOW_N_KEYS(&n), n_part = RJ_WINDOW_N_PART(&n);
-        const rj_sort_key* keys = RJ_WINDOW_KEYS(&n);
-        if (n_keys > (uint64_t)SORT_MAX_KEYS) throw_fmt(RJ_ERR_UNSUPPORTED, "window: more than %d keys", SORT_MAX_KEYS);
-        if (n_part > n_keys)
+        const size_t   cw = child.cols.size();
+        const uint64_t n_keys = RJ_WINDOW_N_KEYS(&n), n_part = RJ_WINDOW_N_PART(&n);
+        // (behind the limit of the key count, ahead of the other checks of the list)
+        if (n_keys <= (uint64_t)SORT_MAX_KEYS && n_part > n_keys)
             throw_fmt(RJ_ERR_ARG, "window: %llu partition keys out of %llu keys", (unsigned long long)n_part, (unsigned long long)n_keys);
-        if (n_keys && !keys) throw_fmt(RJ_ERR_ARG, "window: %llu keys but a NULL key pointer", (unsigned long long)n_keys);
+        const std::vector<rj_sort_key> keys = checked_keys("window", child, RJ_WINDOW_KEYS(&n), n_keys);
         std::vector<int> part_cols, order_cols;  // the distinct key columns; an order key that is a partition key too orders nothing
         for (uint64_t k = 0; k < n_keys; ++k) {
-            if (keys[k].column < 0 || (uint64_t)keys[k].column >= cw) throw_fmt(RJ_ERR_ARG, "window: key column out of range");
-            if (keys[k].flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST)) throw_fmt(RJ_ERR_ARG, "window: unknown key flags %d", keys[k].flags);
-            if (child.cols[(size_t)keys[k].column].type == RJ_VARCHAR)
-                throw_fmt(RJ_ERR_UNSUPPORTED, "window: VARCHAR key (child column %d): a VARCHAR value travels as a row id, its pages "
-                                              "are not read here", keys[k].column);
             const bool in_part = std::find(part_cols.begin(), part_cols.end(), keys[k].column) != part_cols.end();
             if (k < n_part) {
                 if (!in_part) part_cols.push_back(keys[k].column);
@@ -2197,9 +2167,7 @@ class Exec {
         };
         std::vector<Out>      outs;
         std::map<int, WinCol> agg;  // per distinct value column
-        std::vector<uint64_t> pass;  // the distinct passed-through columns
         bool                  want[RJ_WIN_COUNT_STAR + 1] = {false, false, false, false, false};
-        JoinSpec              js;  // (the declared types, for empty_rel)
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint32_t func = RJ_WIN_FUNC(n.out_idx[k]);
             const uint64_t col = RJ_WIN_COL(n.out_idx[k]);
@@ -2214,7 +2182,6 @@ class Exec {
                 const DCol& c = child.cols[col];
                 if (func == RJ_WIN_COL) {
                     expect = c.type;
-                    if (std::find(pass.begin(), pass.end(), col) == pass.end()) pass.push_back(col);
                 } else {
                     if (c.type == RJ_VARCHAR)
                         throw_fmt(RJ_ERR_UNSUPPORTED, "window: function over a VARCHAR column (child column %llu): a VARCHAR value "
@@ -2231,20 +2198,14 @@ class Exec {
             }
             if (n.out_type[k] != expect) throw_fmt(RJ_ERR_ARG, "window: declared type differs from the function's result type");
             outs.push_back(Out{func, (int)col});
-            js.out_type.push_back(n.out_type[k]);
         }
-        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
-        if (child.n == 0) return empty_rel(js, root_res);
+        check_rows(child);
+        if (child.n == 0) return empty_rel(n, root_res);
         const uint32_t rows = (uint32_t)child.n;
 
         // ---- the order
-        BufP perm;
-        for (uint64_t k = n_keys; k-- > 0;) {
-            bool shadowed = false;  // (as in sort(): behind the same column nothing is left to order)
-            for (uint64_t j = 0; j < k; ++j) shadowed = shadowed || keys[j].column == keys[k].column;
-            if (!shadowed) sort_column(child.cols[(size_t)keys[k].column], keys[k].flags, rows, perm);
-        }
-        const uint32_t* dperm = perm ? perm->as<uint32_t>() : nullptr;
+        const BufP      perm = order_by(child, keys);
+        const uint32_t* dperm = ptr<uint32_t>(perm);
         const bool      any_func = std::any_of(outs.begin(), outs.end(), [](const Out& o) { return o.func != RJ_WIN_COL; });
         if (ctx->tune.diag >= 2)
             fprintf(stderr, "[rj diag] window rows=%u keys=%llu partition keys=%llu permuted=%d value columns=%zu\n", rows,
@@ -2254,15 +2215,14 @@ class Exec {
         const uint32_t max_chunk = ctx->tune.win_grid > 0 ? (uint32_t)ctx->tune.win_grid : 0u;
         const uint32_t n_quarters = rows / WIN_QUARTER + (rows % WIN_QUARTER != 0);
         BufP           P, Q, rank_col[RJ_WIN_COUNT_STAR + 1], peer_end;
-        auto           ull = [](const BufP& b) { return b ? b->as<unsigned long long>() : nullptr; };
-        auto           u32 = [](const BufP& b) { return b ? b->as<uint32_t>() : nullptr; };
+        using ull = unsigned long long;
         if (any_func) {
             const uint64_t mask_bytes = ((uint64_t)rows + 63) / 64 * 8;
             P = ctx->buf(mask_bytes);
-            if (part_cols.empty()) launch_win_one_head(L, ull(P), rows);
+            if (part_cols.empty()) launch_win_one_head(L, ptr<ull>(P), rows);
             for (size_t k = 0; k < part_cols.size(); ++k) {
                 const DCol& c = child.cols[(size_t)part_cols[k]];
-                launch_group_heads(L, c.ref(), dperm, rows, c.type == RJ_FP64, k == 0, false, ull(P), nullptr);
+                launch_group_heads(L, c.ref(), dperm, rows, c.type == RJ_FP64, k == 0, false, ptr<ull>(P), nullptr);
             }
             Q = P;  // without order keys every row of a partition is a peer of every other
             if (!order_cols.empty()) {
@@ -2270,7 +2230,7 @@ class Exec {
                 RJ_HIP(hipMemcpyAsync(Q->p, P->p, mask_bytes, hipMemcpyDeviceToDevice, ctx->stream));
                 for (int col : order_cols) {
                     const DCol& c = child.cols[(size_t)col];
-                    launch_group_heads(L, c.ref(), dperm, rows, c.type == RJ_FP64, false, false, ull(Q), nullptr);
+                    launch_group_heads(L, c.ref(), dperm, rows, c.type == RJ_FP64, false, false, ptr<ull>(Q), nullptr);
                 }
             }
             for (uint32_t f = RJ_WIN_ROW_NUMBER; f <= RJ_WIN_COUNT_STAR; ++f)
@@ -2278,10 +2238,10 @@ class Exec {
             if (!agg.empty()) peer_end = ctx->buf((uint64_t)rows * 4);
             BufP           marks[4];
             for (BufP& b : marks) b = ctx->buf((uint64_t)n_quarters * 4);
-            const WinMarks m{u32(marks[0]), u32(marks[1]), u32(marks[2]), u32(marks[3])};
-            const WinRanks r{ull(rank_col[RJ_WIN_ROW_NUMBER]), ull(rank_col[RJ_WIN_RANK]), ull(rank_col[RJ_WIN_DENSE_RANK]),
-                             ull(rank_col[RJ_WIN_COUNT_STAR]), u32(peer_end)};
-            launch_win_ranks(L, ull(P), ull(Q), rows, m, r, max_chunk);
+            const WinMarks m{ptr<uint32_t>(marks[0]), ptr<uint32_t>(marks[1]), ptr<uint32_t>(marks[2]), ptr<uint32_t>(marks[3])};
+            const WinRanks r{ptr<ull>(rank_col[RJ_WIN_ROW_NUMBER]), ptr<ull>(rank_col[RJ_WIN_RANK]), ptr<ull>(rank_col[RJ_WIN_DENSE_RANK]),
+                             ptr<ull>(rank_col[RJ_WIN_COUNT_STAR]), ptr<uint32_t>(peer_end)};
+            launch_win_ranks(L, ptr<ull>(P), ptr<ull>(Q), rows, m, r, max_chunk);
         }
 
         // ---- the scans: one set of launches per distinct value column
@@ -2294,41 +2254,25 @@ class Exec {
             if (w.want_mx) w.mx = ctx->buf((uint64_t)rows * 8);
             BufP t_head = ctx->buf((uint64_t)n_quarters * 4), t_nn = ctx->buf((uint64_t)n_quarters * 4), t_sum = ctx->buf((uint64_t)n_quarters * 8),
                  t_mn = ctx->buf((uint64_t)n_quarters * 8), t_mx = ctx->buf((uint64_t)n_quarters * 8);
-            const WinTails tails{u32(t_head), u32(t_nn), ull(t_sum), ull(t_mn), ull(t_mx)};
-            const WinScan  scan{u32(w.nn), ull(w.sum), ull(w.mn), ull(w.mx)};
-            launch_win_scan(L, c.ref(), dperm, rows, c.type == RJ_FP64, ull(P), tails, scan, max_chunk);
+            const WinTails tails{ptr<uint32_t>(t_head), ptr<uint32_t>(t_nn), ptr<ull>(t_sum), ptr<ull>(t_mn), ptr<ull>(t_mx)};
+            const WinScan  scan{ptr<uint32_t>(w.nn), ptr<ull>(w.sum), ptr<ull>(w.mn), ptr<ull>(w.mx)};
+            launch_win_scan(L, c.ref(), dperm, rows, c.type == RJ_FP64, ptr<ull>(P), tails, scan, max_chunk);
         }
 
-        // ---- the passed-through columns, gathered once each
-        rj_node through = n;
-        through.n_out = pass.size();
-        through.out_idx = pass.data();
-        Result pass_res;
-        Rel    pass_rel = emit_rows(child, through, perm, dperm, rows, root_res ? &pass_res : nullptr);
-
-        // ---- the output columns
-        Rel out;
-        out.n = rows;
-        if (root_res) root_res->num_rows = rows;
-        std::map<uint64_t, DCol> made;  // a function column named several times is made once
+        // ---- the output columns: a passed-through column is gathered once; a function column named several times is
+        // made once (func_cols) and, at the root, encoded per output
+        Sink                     sink(this, root_res, rows);
+        std::map<uint64_t, DCol> func_cols;
         for (size_t k = 0; k < outs.size(); ++k) {
-            const Out& o = outs[k];
-            if (o.func == RJ_WIN_COL) {
-                const size_t at = (size_t)(std::find(pass.begin(), pass.end(), (uint64_t)o.col) - pass.begin());
-                if (root_res)
-                    root_res->cols.push_back(pass_res.cols[at]);
-                else
-                    out.cols.push_back(pass_rel.cols[at]);
+            const Out&     o = outs[k];
+            const uint64_t id = n.out_idx[k];
+            if (o.func == RJ_WIN_COL) {  // (then the id is the plain column index)
+                emit_rows(child, &id, 1, perm, dperm, sink);
                 continue;
             }
-            const uint64_t id = n.out_idx[k];
-            if (!made.count(id)) {
-                DCol d;
-                d.type = js.out_type[k];
-                d.kind = COL_DENSE;
-                d.width = d.type == RJ_INT32 ? 4 : 8;
+            if (!func_cols.count(id)) {
                 if (o.func <= RJ_WIN_COUNT_STAR) {
-                    d.hold = rank_col[o.func];
+                    func_cols[id] = dense_col(n.out_type[k], rank_col[o.func]);
                 } else {
                     const WinCol& w = agg.at(o.col);
                     const DCol&   c = child.cols[(size_t)o.col];
@@ -2338,21 +2282,15 @@ class Exec {
                     const int  decode = o.func == RJ_WIN_SUM || o.func == RJ_WIN_COUNT
                                             ? GROUP_RAW
                                             : (c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64));
-                    d.hold = ctx->buf((uint64_t)rows * d.width);
-                    if (nullable) d.hold_valid = ctx->buf(rows);
-                    launch_win_column(L, ull(src), u32(w.nn), u32(peer_end), rows, decode, d.width, d.hold->as<uint8_t>(),
-                                      d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr);
+                    const DCol d = new_col(n.out_type[k], rows, nullable);
+                    launch_win_column(L, ptr<ull>(src), ptr<uint32_t>(w.nn), ptr<uint32_t>(peer_end), rows, decode, d.width,
+                                      d.hold->as<uint8_t>(), ptr<uint8_t>(d.hold_valid));
+                    func_cols[id] = d;
                 }
-                d.ptr = d.hold->as<uint8_t>();
-                d.valid = d.hold_valid ? d.hold_valid->as<uint8_t>() : nullptr;
-                made[id] = d;
             }
-            if (root_res)
-                root_res->cols.push_back(col_to_result(made.at(id), rows));
-            else
-                out.cols.push_back(made.at(id));
+            sink.add(func_cols.at(id));
         }
-        return out;
+        return sink.out;
     }
 
     // ---------------------------------------------------------------------- map
@@ -2381,9 +2319,7 @@ class Exec {
             bool want8 = false, want4 = false;
             DCol d8, d4;
         };
-        std::vector<ExprOut>  eo(exprs.size());
-        std::vector<uint64_t> pass;  // the distinct passed-through columns
-        JoinSpec              js;    // (the declared types, for empty_rel)
+        std::vector<ExprOut> eo(exprs.size());
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint32_t func = RJ_MAP_FUNC(n.out_idx[k]);
             const uint64_t arg = RJ_MAP_ARG(n.out_idx[k]);
@@ -2391,7 +2327,6 @@ class Exec {
                 if (arg >= cw) throw_fmt(RJ_ERR_ARG, "map: output attr out of range");
                 if (child.cols[arg].type != n.out_type[k])
                     throw_fmt(RJ_ERR_ARG, "map: declared type differs from the child column's type");
-                if (std::find(pass.begin(), pass.end(), arg) == pass.end()) pass.push_back(arg);
             } else if (func == RJ_MAP_EXPR) {
                 if (arg >= exprs.size())
                     throw_fmt(RJ_ERR_ARG, "map: output %llu names expression %llu, the program holds %zu", (unsigned long long)k,
@@ -2404,12 +2339,11 @@ class Exec {
             } else {
                 throw_fmt(RJ_ERR_ARG, "map: unknown output code %u", func);
             }
-            js.out_type.push_back(n.out_type[k]);
         }
         for (size_t e = 0; e < eo.size(); ++e)
             if (!eo[e].want8 && !eo[e].want4) throw_fmt(RJ_ERR_ARG, "map: no output names expression %zu", e);
-        if (child.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
-        if (child.n == 0) return empty_rel(js, root_res);
+        check_rows(child);
+        if (child.n == 0) return empty_rel(n, root_res);
         const uint64_t rows = child.n;
 
         // ---- the device program: the columns it reads, the arrays it writes
@@ -2422,21 +2356,12 @@ class Exec {
                 if (o.op == X_COL) o.a = child.cols[(size_t)ops[k].column].ref();
                 if (o.op == X_OUT) {
                     ExprOut& x = eo[e];
-                    BufP     valid = exprs[e].nullable ? ctx->buf(rows) : BufP();
-                    auto     make = [&](DCol& d, int32_t type, int width) {
-                        d.type = type;
-                        d.kind = COL_DENSE;
-                        d.width = width;
-                        d.hold = ctx->buf(rows * (uint64_t)width);
-                        d.ptr = d.hold->as<uint8_t>();
-                        d.hold_valid = valid;
-                        d.valid = valid ? valid->as<uint8_t>() : nullptr;
-                    };
-                    if (x.want8) make(x.d8, exprs[e].f64 ? RJ_FP64 : RJ_INT64, 8);
-                    if (x.want4) make(x.d4, RJ_INT32, 4);
-                    o.out8 = x.want8 ? x.d8.hold->as<uint8_t>() : nullptr;
-                    o.out4 = x.want4 ? x.d4.hold->as<uint8_t>() : nullptr;
-                    o.valid = valid ? valid->as<uint8_t>() : nullptr;
+                    BufP     valid = exprs[e].nullable ? ctx->buf(rows) : BufP();  // (one array under both types)
+                    if (x.want8) x.d8 = dense_col(exprs[e].f64 ? RJ_FP64 : RJ_INT64, ctx->buf(rows * 8), valid);
+                    if (x.want4) x.d4 = dense_col(RJ_INT32, ctx->buf(rows * 4), valid);
+                    o.out8 = ptr<uint8_t>(x.d8.hold);
+                    o.out4 = ptr<uint8_t>(x.d4.hold);
+                    o.valid = ptr<uint8_t>(valid);
                     ++e;
                 }
                 prog.ops[k] = o;
@@ -2452,46 +2377,42 @@ class Exec {
             fprintf(stderr, "[rj diag] map rows=%llu ops=%llu expressions=%zu\n", (unsigned long long)rows, (unsigned long long)n_ops,
                     exprs.size());
 
-        // ---- the passed-through columns: the child's own (at the root through the writers of a projection)
-        rj_node through = n;
-        through.n_out = pass.size();
-        through.out_idx = pass.data();
-        Result pass_res;
-        Rel    pass_rel = emit_rows(child, through, BufP(), nullptr, rows, root_res ? &pass_res : nullptr);
-
-        // ---- the output columns
-        Rel out;
-        out.n = rows;
-        if (root_res) root_res->num_rows = rows;
-        std::map<uint64_t, ResultColumn> made_rc;  // (an expression named twice under one type is encoded once)
+        // ---- the output columns: a passed-through column is the child's own (at the root through the writers of a
+        // projection); an expression named twice under one type is encoded once: the id says which of its two arrays.
+        // The ids of the arrays lie above every column index (RJ_MAP_ARG keeps 56 bits), whatever RJ_MAP_* codes exist.
+        const uint64_t expr_ids = 1ull << 56;
+        Sink           sink(this, root_res, rows);
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint64_t arg = RJ_MAP_ARG(n.out_idx[k]);
-            if (RJ_MAP_FUNC(n.out_idx[k]) == RJ_MAP_COL) {
-                const size_t at = (size_t)(std::find(pass.begin(), pass.end(), arg) - pass.begin());
-                if (root_res)
-                    root_res->cols.push_back(pass_res.cols[at]);
-                else
-                    out.cols.push_back(pass_rel.cols[at]);
-                continue;
-            }
-            const DCol& d = n.out_type[k] == RJ_INT32 ? eo[arg].d4 : eo[arg].d8;
-            if (!root_res) {
-                out.cols.push_back(d);
-                continue;
-            }
-            const uint64_t id = arg * 2 + (n.out_type[k] == RJ_INT32);
-            if (!made_rc.count(id)) made_rc[id] = col_to_result(d, rows);
-            root_res->cols.push_back(made_rc.at(id));
+            const bool     narrow = n.out_type[k] == RJ_INT32;
+            if (RJ_MAP_FUNC(n.out_idx[k]) == RJ_MAP_COL)
+                emit_rows(child, &arg, 1, BufP(), nullptr, sink);
+            else
+                sink.add(expr_ids + arg * 2 + narrow, [&] { return narrow ? eo[arg].d4 : eo[arg].d8; });
         }
-        return out;
+        return sink.out;
     }
 
-    // a fixed-width column (paged, or dense with or without validity) as a root result column: Page
-    // images encoded on the device
+    // ------------------------------------------------------------- a node's output
+    // A column of `rows` rows as a root result column: Page images.  The strings of a VARCHAR column are
+    // gathered through its row ids, a column that emit_rows gathered into Page images is handed over, and
+    // any other fixed-width column (paged, or dense with or without validity) is encoded on the device.
     ResultColumn col_to_result(const DCol& d, uint64_t rows) {
         ResultColumn rc;
         rc.type = d.type;
-        if (rows) {
+        if (d.type == RJ_VARCHAR) {
+            BufP            rowids;
+            const uint32_t* ids = reinterpret_cast<const uint32_t*>(d.ptr);
+            if (d.kind == COL_IOTA) {  // (a projection only: every row of the base table, in order)
+                rowids = ctx->buf(rows * 4);
+                launch_gather(L, d.ref(), nullptr, rows, OutStream{rowids->as<uint8_t>(), ST_DENSE32, 0}, nullptr);
+                ids = rowids->as<uint32_t>();
+            }
+            varchar_root(ids, rows, d, rc);
+        } else if (d.kind == COL_PAGED && d.hold) {  // (a table's own pages have no holder)
+            rc.dev_pages = d.hold;
+            rc.n_pages = pages_for(rows, d.width);
+        } else if (rows) {
             rc.n_pages = pages_for(rows, d.width);
             rc.dev_pages = ctx->buf(rc.n_pages * PAGE_BYTES);
             if (d.valid) {
@@ -2504,12 +2425,6 @@ class Exec {
         }
         return rc;
     }
-    // a relation of dense columns as a root result
-    void rel_to_result(const Rel& r, Result& res) {
-        res.num_rows = r.n;
-        for (const DCol& d : r.cols) res.cols.push_back(col_to_result(d, r.n));
-    }
-
     static int stream_mode_of(bool is_root, int width, bool direct_output) {
         if (is_root && direct_output) return width == 4 ? ST_PAGED32 : ST_PAGED64;
         return width == 4 ? ST_DENSE32 : ST_DENSE64;
@@ -2585,7 +2500,7 @@ class Exec {
                 wo.values = ctx->buf(stream_bytes(wo.mode, std::max<uint64_t>(nrows, 1)));
                 if (nullable) wo.valid = ctx->buf(std::max<uint64_t>(nrows, 1));
                 sp.col[i].out = wo.values->as<uint8_t>();
-                sp.col[i].valid = wo.valid ? wo.valid->as<uint8_t>() : nullptr;
+                sp.col[i].valid = ptr<uint8_t>(wo.valid);
                 sp.col[i].word = word;
                 sp.col[i].width = col.width;
                 sp.col[i].valid_bit = (int32_t)i;
@@ -2606,12 +2521,6 @@ class Exec {
             Side&       s = is_left ? ls : rs;
             int         c = (int)(is_left ? js.out_idx[k] : js.out_idx[k] - lw);
             const DCol& src = s.rel->cols[c];
-            DCol        d;
-            d.type = src.type;
-            d.width = src.width;
-            d.kind = COL_DENSE;
-            d.vc_table = src.vc_table;
-            d.vc_col = src.vc_col;
             BufP buf;           // where this column's values/pages live
             int  buf_mode = ST_NONE;
             BufP valid;
@@ -2646,16 +2555,11 @@ class Exec {
                     buf = ctx->buf(stream_bytes(buf_mode, std::max<uint64_t>(nrows, 1)));
                     if (src.valid) valid = ctx->buf(std::max<uint64_t>(nrows, 1));
                     launch_gather(L, src.ref(), idx, nrows,
-                                  OutStream{buf->as<uint8_t>(), buf_mode, 0},
-                                  valid ? valid->as<uint8_t>() : nullptr);
+                                  OutStream{buf->as<uint8_t>(), buf_mode, 0}, ptr<uint8_t>(valid));
                 }
             }
             if (!is_root) {
-                d.hold = buf;
-                d.ptr = buf ? buf->as<uint8_t>() : nullptr;
-                d.hold_valid = valid;
-                d.valid = valid ? valid->as<uint8_t>() : nullptr;
-                out.cols.push_back(d);
+                out.cols.push_back(dense_like(src, buf, valid));
                 continue;
             }
             // ---- root: Page images (replaces Table::to_columnar, build_table.cpp:456-681)
@@ -2680,11 +2584,7 @@ class Exec {
                     launch_encode_nullable(L, buf->as<uint8_t>(), valid->as<uint8_t>(), nrows,
                                            src.width, rc.dev_pages->as<uint8_t>());
                 } else {
-                    DCol dense;
-                    dense.kind = COL_DENSE;
-                    dense.width = src.width;
-                    dense.ptr = buf->as<uint8_t>();
-                    launch_gather(L, dense.ref(), nullptr, nrows,
+                    launch_gather(L, dense_like(src, buf).ref(), nullptr, nrows,
                                   OutStream{rc.dev_pages->as<uint8_t>(),
                                             src.width == 4 ? ST_PAGED32 : ST_PAGED64, 0},
                                   nullptr);
@@ -2759,13 +2659,7 @@ class Exec {
                                ? ((1ull << ctx->tune.vkey_hash_bits) - 1ull)
                                : ~0ull);
             v.rel = *s->rel;
-            DCol h;
-            h.type = RJ_INT64;
-            h.kind = COL_DENSE;
-            h.width = 8;
-            h.ptr = v.hash->as<uint8_t>();
-            h.valid = v.valid->as<uint8_t>();
-            v.rel.cols.push_back(h);
+            v.rel.cols.push_back(dense_col(RJ_INT64, v.hash, v.valid));
             s->rel = &v.rel;
             s->key_col = v.rel.cols.size() - 1;
         }
@@ -2784,8 +2678,7 @@ class Exec {
                          bs.stream->as<uint32_t>(), ps.stream->as<uint32_t>(), n, keep->as<uint8_t>(),
                          bad->as<unsigned long long>());
         unsigned long long n_bad = 0;
-        RJ_HIP(hipMemcpyAsync(&n_bad, bad->p, 8, hipMemcpyDeviceToHost, ctx->stream));
-        ctx->sync();
+        read_back(&n_bad, bad->p, 8);
         if (n_bad == 0) return nrows;
         BufP nb = ctx->buf(std::max<uint64_t>(nrows - n_bad, 1) * 4), np = ctx->buf(std::max<uint64_t>(nrows - n_bad, 1) * 4);
         launch_vc_compact(L, keep->as<uint8_t>(), bs.stream->as<uint32_t>(), ps.stream->as<uint32_t>(), n,
@@ -2824,8 +2717,7 @@ class Exec {
             launch_vc_walk(L, vrows->as<VcRow>(), nr, pcnt->as<uint32_t>(), nullptr, nullptr);
             launch_scan_bins(L, pcnt->as<uint32_t>(), chunks, pbase->as<uint32_t>(), nullptr);
             uint32_t n_out = 0;
-            RJ_HIP(hipMemcpyAsync(&n_out, pbase->as<uint32_t>() + chunks, 4, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
+            read_back(&n_out, pbase->as<uint32_t>() + chunks, 4);
             BufP plist = ctx->buf(std::max<uint64_t>(n_out, 1) * sizeof(VcPage));
             rc.dev_pages = ctx->buf(std::max<uint64_t>(n_out, 1) * PAGE_BYTES);
             launch_vc_walk(L, vrows->as<VcRow>(), nr, pcnt->as<uint32_t>(), pbase->as<uint32_t>(),
@@ -2843,8 +2735,7 @@ class Exec {
             return;
         }
         std::vector<uint32_t> ids(n);
-        RJ_HIP(hipMemcpyAsync(ids.data(), dev_rowids, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        ctx->sync();
+        read_back(ids.data(), dev_rowids, n * 4);
         auto tv1 = std::chrono::steady_clock::now();
         const std::vector<uint64_t>& dir = vc_directory(src.vc_table, src.vc_col, t);
         auto tv2 = std::chrono::steady_clock::now();
@@ -2983,24 +2874,7 @@ class ShardedExec {
                 });
             return r;
         }
-        if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER || n.kind == RJ_NODE_FULL)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: %s join nodes run on one device",
-                      n.kind == RJ_NODE_SEMI    ? "semi (RJ_NODE_SEMI)"
-                      : n.kind == RJ_NODE_ANTI  ? "anti (RJ_NODE_ANTI)"
-                      : n.kind == RJ_NODE_OUTER ? "outer (RJ_NODE_OUTER)"
-                                                : "full outer (RJ_NODE_FULL)");
-        if (n.kind == RJ_NODE_AGG)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: aggregation (RJ_NODE_AGG) nodes run on one device");
-        if (n.kind == RJ_NODE_SELECT)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: selection (RJ_NODE_SELECT) nodes run on one device");
-        if (n.kind == RJ_NODE_SORT)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: sort (RJ_NODE_SORT) nodes run on one device");
-        if (n.kind == RJ_NODE_GROUP)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: grouping (RJ_NODE_GROUP) nodes run on one device");
-        if (n.kind == RJ_NODE_WINDOW)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: window (RJ_NODE_WINDOW) nodes run on one device");
-        if (n.kind == RJ_NODE_MAP)
-            throw_fmt(RJ_ERR_UNSUPPORTED, "sharded execution: map (RJ_NODE_MAP) nodes run on one device");
+        // (execute_sharded has refused the kinds that do not run sharded: first_unshardable)
         if (n.kind != RJ_NODE_JOIN) throw_fmt(RJ_ERR_ARG, "bad node kind");
         std::vector<Rel> L = node(n.left, nullptr, depth + 1);
         std::vector<Rel> R = node(n.right, nullptr, depth + 1);
@@ -3363,6 +3237,20 @@ class ShardedExec {
     }
 };
 
+// The first node, in the order of the plan walk, of a kind that does not run sharded (found before
+// any rank moves data); nullptr = none.  A malformed plan is the plan walk's to report.
+const NodeKind* first_unshardable(const rj_plan* plan, uint64_t idx, int depth) {
+    if (!plan || idx >= plan->n_nodes || depth > 4096) return nullptr;
+    const rj_node&  n = plan->nodes[idx];
+    const NodeKind* K = node_kind(n.kind);
+    if (!K || !K->sharded) return K;
+    const NodeKind* below = nullptr;
+    if (K->children >= 1) below = first_unshardable(plan, n.left, depth + 1);
+    if (!below && K->children >= 2) below = first_unshardable(plan, n.right, depth + 1);
+    return below;
+}
+std::string one_device_only(const NodeKind& K) { return std::string(K.name) + " node (" + K.token + ") runs on one device"; }
+
 bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* why) {
     if (idx >= plan->n_nodes || depth > 4096) return false;
     const rj_node& n = plan->nodes[idx];
@@ -3374,45 +3262,7 @@ bool node_shardable(const rj_plan* plan, uint64_t idx, int depth, std::string* w
             }
         return true;
     }
-    if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI) {
-        if (why)
-            *why = n.kind == RJ_NODE_SEMI ? "a semi join node (RJ_NODE_SEMI) runs on one device"
-                                          : "an anti join node (RJ_NODE_ANTI) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_OUTER) {
-        if (why) *why = "an outer join node (RJ_NODE_OUTER) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_FULL) {
-        if (why) *why = "a full outer join node (RJ_NODE_FULL) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_AGG) {
-        if (why) *why = "an aggregation node (RJ_NODE_AGG) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_SELECT) {
-        if (why) *why = "a selection node (RJ_NODE_SELECT) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_SORT) {
-        if (why) *why = "a sort node (RJ_NODE_SORT) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_GROUP) {
-        if (why) *why = "a grouping node (RJ_NODE_GROUP) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_WINDOW) {
-        if (why) *why = "a window node (RJ_NODE_WINDOW) runs on one device";
-        return false;
-    }
-    if (n.kind == RJ_NODE_MAP) {
-        if (why) *why = "a map node (RJ_NODE_MAP) runs on one device";
-        return false;
-    }
-    if (n.kind != RJ_NODE_JOIN) return false;
+    if (n.kind != RJ_NODE_JOIN) return false;  // (plan_shardable has named the kind: first_unshardable)
     if (!node_shardable(plan, n.left, depth + 1, why) || !node_shardable(plan, n.right, depth + 1, why))
         return false;
     if (n.left >= plan->n_nodes || n.right >= plan->n_nodes) return false;
@@ -3637,51 +3487,20 @@ Result* join_tuples(Context* ctx, const rj_tuples* build, const rj_tuples* probe
     return e.run_tuples(build, probe, skip_rank_bits);
 }
 
-// the node kinds ShardedExec refuses, found before any rank moves data
-static void refuse_filter_nodes(const rj_plan* plan, uint64_t idx, int depth) {
-    if (!plan || idx >= plan->n_nodes || depth > 4096) return;  // (the plan walk reports it)
-    const rj_node& n = plan->nodes[idx];
-    if (n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI)
-        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds %s join node; semi and anti joins run on one device",
-                  n.kind == RJ_NODE_SEMI ? "a semi (RJ_NODE_SEMI)" : "an anti (RJ_NODE_ANTI)");
-    if (n.kind == RJ_NODE_OUTER)
-        throw_fmt(RJ_ERR_UNSUPPORTED,
-                  "rj_execute_sharded: the plan holds an outer (RJ_NODE_OUTER) join node; outer joins run on one device");
-    if (n.kind == RJ_NODE_FULL)
-        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds a full outer (RJ_NODE_FULL) join node; full "
-                                      "outer joins run on one device");
-    if (n.kind == RJ_NODE_AGG)
-        throw_fmt(RJ_ERR_UNSUPPORTED,
-                  "rj_execute_sharded: the plan holds an aggregation (RJ_NODE_AGG) node; aggregations run on one device");
-    if (n.kind == RJ_NODE_SELECT)
-        throw_fmt(RJ_ERR_UNSUPPORTED,
-                  "rj_execute_sharded: the plan holds a selection (RJ_NODE_SELECT) node; selections run on one device");
-    if (n.kind == RJ_NODE_SORT)
-        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: the plan holds a sort (RJ_NODE_SORT) node; sorts run on one device");
-    if (n.kind == RJ_NODE_GROUP)
-        throw_fmt(RJ_ERR_UNSUPPORTED,
-                  "rj_execute_sharded: the plan holds a grouping (RJ_NODE_GROUP) node; groupings run on one device");
-    if (n.kind == RJ_NODE_WINDOW)
-        throw_fmt(RJ_ERR_UNSUPPORTED,
-                  "rj_execute_sharded: the plan holds a window (RJ_NODE_WINDOW) node; window functions run on one device");
-    if (n.kind == RJ_NODE_MAP)
-        throw_fmt(RJ_ERR_UNSUPPORTED,
-                  "rj_execute_sharded: the plan holds a map (RJ_NODE_MAP) node; computed columns run on one device");
-    if (n.kind == RJ_NODE_JOIN) {
-        refuse_filter_nodes(plan, n.left, depth + 1);
-        refuse_filter_nodes(plan, n.right, depth + 1);
-    }
-}
-
 void execute_sharded(Context* group, const rj_plan* plan, Table* const* tables, uint64_t n_inputs,
                      int flags, Result** out) {
-    if (plan) refuse_filter_nodes(plan, plan->root, 0);
+    if (const NodeKind* K = plan ? first_unshardable(plan, plan->root, 0) : nullptr)
+        throw_fmt(RJ_ERR_UNSUPPORTED, "rj_execute_sharded: %s", one_device_only(*K).c_str());
     ShardedExec e(group, plan, tables, n_inputs, flags);
     e.run(out);
 }
 
 bool plan_shardable(const rj_plan* plan, std::string* why) {
     if (!plan || plan->root >= plan->n_nodes) return false;
+    if (const NodeKind* K = first_unshardable(plan, plan->root, 0)) {
+        if (why) *why = one_device_only(*K);
+        return false;
+    }
     return node_shardable(plan, plan->root, 0, why);
 }
 

@@ -319,6 +319,15 @@ void    execute_sharded(Context* group, const rj_plan* plan, Table* const* table
                         int flags, Result** out);
 // Can every JoinNode of the plan run sharded (at most one fixed-width non-key column per side)?
 bool    plan_shardable(const rj_plan* plan, std::string* why);
+// One line per RJ_NODE_* kind (the table is in rj_exec.hip); nullptr = no such kind
+struct NodeKind {
+    int         kind;      // RJ_NODE_*
+    const char* name;      // in messages, with its article
+    const char* token;     // the RJ_NODE_* spelling
+    int         children;  // 0 = a scan, 1 = left, 2 = left and right
+    bool        sharded;   // runs across the ranks of a job (else on one device only)
+};
+const NodeKind* node_kind(int kind);
 void    shard_partition(Context* ctx, const Table* t, uint64_t key_col, uint64_t carry_col,
                         uint32_t n_ranks, rj_tuples* out, uint64_t* counts);
 

@@ -299,13 +299,9 @@ static void scan_order(const rj_plan* plan, uint64_t idx, int depth, std::vector
             seen[n.base_table_id] = true;
             order.push_back(n.base_table_id);
         }
-    } else if (n.kind == RJ_NODE_JOIN || n.kind == RJ_NODE_SEMI || n.kind == RJ_NODE_ANTI || n.kind == RJ_NODE_OUTER ||
-               n.kind == RJ_NODE_FULL) {
-        scan_order(plan, n.left, depth + 1, seen, order);
-        scan_order(plan, n.right, depth + 1, seen, order);
-    } else if (n.kind == RJ_NODE_AGG || n.kind == RJ_NODE_SELECT || n.kind == RJ_NODE_SORT || n.kind == RJ_NODE_GROUP ||
-               n.kind == RJ_NODE_WINDOW || n.kind == RJ_NODE_MAP) {
-        scan_order(plan, n.left, depth + 1, seen, order);
+    } else if (const NodeKind* K = node_kind(n.kind)) {
+        if (K->children >= 1) scan_order(plan, n.left, depth + 1, seen, order);
+        if (K->children >= 2) scan_order(plan, n.right, depth + 1, seen, order);
     }
 }
 

@@ -318,7 +318,7 @@ def test_nullable_agg_outputs(dt, pat):
         # MAX of an INT32 column are narrowed by k_agg_column<4> and written by k_encode_nullable<4>
         want = {"k_agg_column<8>", "k_encode_nullable<8>"} | ({"k_agg_column<4>", "k_encode_nullable<4>"} if dt == I32 else set())
         assert want <= set(ran), (what, sorted(ran))
-        # COUNT has no NULLs: k_gather into page images + k_finish_pages (rel_to_result)
+        # COUNT has no NULLs: k_gather into page images + k_finish_pages (col_to_result)
         assert "k_finish_pages" in fams(ran), (what, sorted(ran))
 
 
