@@ -286,7 +286,7 @@ int Context::compute_units() {
 // What the first rj_execute of a fresh context would otherwise pay (job/1a: 44 ms against 1.4 ms
 // for the calls after it): pinned staging in both directions, the upload stream, the host worker
 // threads, and the code objects of the kernels, which HIP loads when a kernel of a translation
-// unit is first launched.
+// unit is first used.
 void Context::prewarm() {
     RJ_HIP(hipSetDevice(device));
     constexpr size_t STAGE = (size_t)2 * 4096 * PAGE_BYTES;  // rj_table.hip: two 32 MiB halves
@@ -305,8 +305,13 @@ void Context::prewarm() {
     RJ_HIP(hipMemcpyAsync(pinned, b->p, 256, hipMemcpyDeviceToHost, stream));
     RJ_HIP(hipMemcpyAsync(pinned_small, b->p, 64, hipMemcpyDeviceToHost, stream));
     RJ_HIP(hipMemsetAsync(b->p, 0, 256, stream));
-    launch_scan_bins(L, b->as<uint32_t>(), 1, b->as<uint32_t>() + 8, nullptr);  // rj_kernels.hip's code object
-    prewarm_varchar_dev(L, b->as<uint32_t>());                                    // rj_varchar_dev.hip's
+    // the code objects of the join path's four kernel files, then rj_varchar_dev.hip's
+    uint32_t* const zeroed = b->as<uint32_t>();
+    prewarm_kernels(L, zeroed);
+    prewarm_join(L, zeroed);
+    prewarm_outer(L, zeroed);
+    prewarm_full(L, zeroed);
+    prewarm_varchar_dev(L, zeroed);
     sync();
 }
 

@@ -10,6 +10,7 @@
 //   K5/6 build + probe      per-partition bucketised hash table in LDS (one 16-byte read per
 //                           probe), ballot/mbcnt output offsets, one global reservation per
 //                           4096 probe tuples, streams written straight into Page images
+//                           (partitioned: rj_join.hip; the broadcast form is here)
 //   K7  gather              row-id -> column value (generic late materialisation)
 //   K8  page finish/encode  Page headers + validity bitmaps of the result
 //
@@ -18,84 +19,12 @@
 
 #include "rj_kernels.hpp"
 #include "rj_kernel_util.hpp"
+#include "rj_tuple_util.hpp"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace rj {
-
-// ============================================================== small helpers
-// Bijective finalisers (murmur3 fmix32 / fmix64).  The reference hashes with
-// fmix64 (src/execute.cpp:21-27); the hash is not observable in results
-// (SURVEY.md §2 #11), so INT32 keys use the cheaper 32-bit mix.  Because both
-// are bijections the partitions store HASHED keys and the probe un-hashes on
-// emit; equal hashed keys <=> equal keys.
-__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-__device__ __forceinline__ uint32_t unfmix32(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x7ed1b41du;  // inverse of 0xc2b2ae35 mod 2^32
-    h ^= (h >> 13) ^ (h >> 26);
-    h *= 0xa5cb9243u;  // inverse of 0x85ebca6b mod 2^32
-    h ^= h >> 16;
-    return h;
-}
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {
-    k ^= k >> 33;
-    k *= 0xff51afd7ed558ccdULL;
-    k ^= k >> 33;
-    k *= 0xc4ceb9fe1a85ec53ULL;
-    k ^= k >> 33;
-    return k;
-}
-__device__ __forceinline__ uint64_t unfmix64(uint64_t k) {
-    k ^= k >> 33;
-    k *= 0x9cb4b2f8129337dbULL;  // inverse of 0xc4ceb9fe1a85ec53 mod 2^64
-    k ^= k >> 33;
-    k *= 0x4f74430c22a54005ULL;  // inverse of 0xff51afd7ed558ccd mod 2^64
-    k ^= k >> 33;
-    return k;
-}
-
-// 16-byte vector of four tuples' words.  Tuple runs start at arbitrary (4-byte aligned)
-// offsets; gfx950 global loads only need dword alignment, so one dwordx4 replaces four
-// dword loads and their address arithmetic.
-typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ void stream_store(const OutStream& o, uint64_t row, uint32_t lo,
-                                             uint32_t hi, uint32_t x2 = 0u) {
-    switch (o.mode) {
-    case ST_DENSE96: {
-        uint32_t* r = reinterpret_cast<uint32_t*>(o.base) + row * 3u;
-        r[0] = lo;
-        r[1] = hi;
-        r[2] = x2;
-        break;
-    }
-    case ST_DENSE32: reinterpret_cast<uint32_t*>(o.base)[row] = lo; break;
-    case ST_DENSE64:
-        reinterpret_cast<uint64_t*>(o.base)[row] = (uint64_t)lo | ((uint64_t)hi << 32);
-        break;
-    case ST_PAGED32: {
-        uint32_t r = (uint32_t)row, p = r / ROWS32, i = r - p * ROWS32;
-        *reinterpret_cast<uint32_t*>(o.base + (size_t)p * PAGE_BYTES + HDR32 + i * 4u) = lo;
-        break;
-    }
-    case ST_PAGED64: {
-        uint32_t r = (uint32_t)row, p = r / ROWS64, i = r - p * ROWS64;
-        *reinterpret_cast<uint64_t*>(o.base + (size_t)p * PAGE_BYTES + HDR64 + i * 8u) =
-            (uint64_t)lo | ((uint64_t)hi << 32);
-        break;
-    }
-    default: break;
-    }
-}
 
 // ================================================================= K0 headers
 // One wave per page: reads `u16 n_rows @0` and the validity bitmap in the last
@@ -1442,637 +1371,6 @@ __global__ void k_heavy_tasks(const uint32_t* offR, const uint32_t* offS, uint32
     }
 }
 
-// ============================================= tuples of a partitioned relation
-// One tuple of a partitioned relation (the layouts partition() writes: 12-byte tuples, 8-byte
-// pairs, or word arrays whose last two carry words are one pair array).
-template <int KW, int CW>
-__device__ __forceinline__ void part_tuple(const Words& W, int pack, int aos, uint32_t idx, uint32_t (&t)[KW + CW]) {
-    constexpr int NW = KW + CW;
-    if constexpr (KW == 1 && CW == 2) {
-        if (aos) {
-            const uint32_t* p = W.w[0] + (size_t)idx * 3u;
-            t[0] = p[0];
-            t[1] = p[1];
-            t[2] = p[2];
-            return;
-        }
-    }
-    if constexpr (KW == 1 && CW == 1) {
-        if (pack) {
-            const uint2 v = reinterpret_cast<const uint2*>(W.w[0])[idx];
-            t[0] = v.x;
-            t[1] = v.y;
-            return;
-        }
-    }
-    constexpr int NA = CW >= 2 ? NW - 2 : NW;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) t[a] = W.w[a][idx];
-    if constexpr (CW >= 2) {
-        const uint2 v = reinterpret_cast<const uint2*>(W.w[NA])[idx];
-        t[NA] = v.x;
-        t[NA + 1] = v.y;
-    }
-}
-
-// The carry words behind the key of such a tuple (words the shape does not have: zero).
-template <int KW, int CW>
-__device__ __forceinline__ void tuple_carry(const uint32_t (&t)[KW + CW], uint32_t& c0, uint32_t& c1, uint32_t& c2) {
-    constexpr int W = KW + CW;
-    c0 = CW >= 1 ? t[KW < W ? KW : 0] : 0u;
-    c1 = CW >= 2 ? t[KW + 1 < W ? KW + 1 : 0] : 0u;
-    c2 = CW == 3 ? t[W - 1] : 0u;
-}
-
-// A hashed key (lo, hi: KW words) back to the key the source column held.
-template <int KW>
-__device__ __forceinline__ void unhash_key(uint32_t lo, uint32_t hi, uint32_t& k0, uint32_t& k1) {
-    if constexpr (KW == 1) {
-        k0 = unfmix32(lo);
-    } else {
-        const uint64_t k64 = unfmix64((uint64_t)lo | ((uint64_t)hi << 32));
-        k0 = (uint32_t)k64;
-        k1 = (uint32_t)(k64 >> 32);
-    }
-}
-
-// ========================================================== K5/K6 build + probe
-// Replaces the per-bucket table of the reference (src/execute.cpp:203-248):
-//   build  — bucketised table in LDS: a tuple takes the next free slot of its 4-slot home
-//            bucket (one LDS counter atomic), a full bucket overflows into the next one;
-//            duplicate build keys simply occupy further slots;
-//   probe  — one 16-byte read per bucket, four register compares; a bucket whose last slot
-//            is EMPTY ends the walk; every equal key is a match (so duplicates multiply,
-//            reference :232-243);
-//   emit   — ballot/mbcnt offsets inside the wave, one global atomic per 4096
-//            probe tuples reserves the output rows; lanes of a wave then write
-//            consecutive rows of each output stream (coalesced).
-// Bucket index uses hash bits ABOVE the radix bits (the reference reuses the low
-// bits for both, SURVEY.md §3.2 — not copied).  EMPTY is a word whose radix bits
-// differ from the partition's, so it cannot collide with a stored hashed key.
-// A build partition larger than JN_RMAX is processed in table-sized chunks
-// (block nested loop), which keeps any duplicate-heavy input correct.
-// OM (output mode) fixes the stream layout at compile time for the two hot shapes, so the
-// emit code is straight-line stores instead of a per-store mode switch:
-//   OM_PAGED32  key/bc/pc are all INT32 Page images (root of a plan, BASELINE config)
-//   OM_DENSE32  all present streams are dense 32-bit arrays (inner joins, row-index carries)
-//   OM_GENERIC  anything else (64-bit streams, mixed layouts, no key stream)
-//   OM_P32_64_64 INT32 key pages + INT64/FP64 pages for both carries (root of BASELINE config 3)
-enum { OM_GENERIC = 0, OM_PAGED32 = 1, OM_DENSE32 = 2, OM_P32_64_64 = 3 };
-
-// Diagnostic phase stamps (RJ_DIAG=1): thread 0 of every workgroup adds the cycles between
-// consecutive stamps to jp.diag[phase].  Shares only — the stamps perturb the timing.
-#define RJ_STAMP(PHASE)                                                         \
-    do {                                                                        \
-        if (jp.diag) {                                                          \
-            unsigned long long _t = __builtin_amdgcn_s_memtime();               \
-            if (threadIdx.x == 0) atomicAdd(&jp.diag[PHASE], _t - diag_t);      \
-            diag_t = _t;                                                        \
-        }                                                                       \
-    } while (0)
-
-// PK: bit 0 = the build side, bit 1 = the probe side is a packed {hashed key, carry} array
-// TG: "tagged" table for one key word + a two-word build carry when the plan has >= 14 radix
-//     bits.  All hashed keys of a partition share their low radix bits, so the remaining
-//     (<= 18) high bits identify a key inside its partition: a slot is ONE word
-//     {tag (19 bits) | build tuple index << 19} and the carries sit densely, indexed by build tuple.
-//     Table = 32 KiB of slots + 32 KiB of carries (instead of three 32 KiB word arrays), so
-//     two 512-thread workgroups share a CU and overlap their phases like the two-word join.
-template <int KW, int CWR, int CWS, int OM, int PK, int TG>
-__global__ __launch_bounds__(jn_threads(TG ? 2 : KW + CWR), jn_min_waves(TG ? 2 : KW + CWR)) void k_join(JoinParams jp) {
-    // Tables of three or four word arrays (64-bit keys, two-word build carries) leave room for
-    // ONE workgroup per CU; it then runs 1024 threads, so the CU holds the same 16 waves as with
-    // two 512-thread workgroups.  (Fetching wide build carries from the partitioned arrays on
-    // emit instead — a two-array table — cost 7 of 17 ms at 1 B rows: 2 random 4-byte reads per
-    // match are bound by the request rate of the vector memory path.)
-    static_assert(!TG || (KW == 1 && CWR == 2), "tagged table: one key word + two-word build carry");
-    constexpr int      TH = jn_threads(TG ? 2 : KW + CWR);
-    constexpr int      RPT = (JN_RMAX + TH - 1) / TH;  // build tuples per thread
-    constexpr int      SPT = JN_SUB / TH;          // probe tuples per thread per sub-chunk
-    constexpr int      SUB = JN_SUB;
-    static_assert(RPT % 4 == 0 && SPT % 4 == 0, "tuples are loaded as 16-byte vectors");
-    constexpr int      RW = KW + CWR;  // LDS table arrays (one per word)
-    constexpr int      SW = KW + CWS;
-    // Bucketised table: JN_CAP slots = JN_CAP/4 buckets of 4 consecutive slots.  A probe
-    // reads a whole bucket with ONE 16-byte LDS read and compares in registers, an insert
-    // takes its slot from ONE LDS counter atomic — so nearly every lane finishes in a single
-    // iteration and the wave does not pay the longest linear-probing chain of its 64 lanes.
-    // A full bucket (4th slot used) sends probe and insert on to the next bucket.
-    __shared__ __attribute__((aligned(16))) uint32_t t_w[TG ? 1 : RW][JN_CAP];
-    __shared__ __attribute__((aligned(16))) uint2    t_c2[TG ? JN_RMAX : 1];  // TG: carries by build tuple
-    __shared__ __attribute__((aligned(16))) uint32_t t_cnt[JN_CAP / 4];
-    __shared__ uint32_t s_wtot[TH / 64];
-    __shared__ unsigned long long s_obase;
-
-    const uint32_t     lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    constexpr uint32_t SMASK = JN_CAP - 1;
-    constexpr uint32_t BMASK = JN_CAP / 4 - 1;
-
-    // A workgroup joins PPW consecutive partitions (main pass) or one heavy task.
-    constexpr int PPW = jn_ppw(TG ? 2 : KW + CWR);
-    struct Task {
-        uint32_t q, rbeg, rend, sbeg, send;
-        bool     active;
-    };
-    // The first jp.heavy_grid workgroups of the launch take the heavy tasks (they start first:
-    // with a skewed probe side they are the long pole), the others one partition each.
-    const bool     heavy_wg = blockIdx.x < jp.heavy_grid;
-    const uint32_t wg = heavy_wg ? blockIdx.x : blockIdx.x - jp.heavy_grid;
-    auto get_task = [&](uint32_t k) {
-        Task t{0, 0, 0, 0, 0, false};
-        if (heavy_wg) {
-            if (k == 0 && wg < *jp.n_heavy) {
-                t.q = jp.heavy_tasks[3 * wg + 0];
-                t.sbeg = jp.heavy_tasks[3 * wg + 1];
-                t.send = jp.heavy_tasks[3 * wg + 2];
-                t.rbeg = jp.offR[t.q];
-                t.rend = jp.offR[t.q + 1];
-                t.active = t.rbeg < t.rend && t.sbeg < t.send;
-            }
-            return t;
-        }
-        t.q = wg * PPW + k;
-        if (k < (uint32_t)PPW && t.q < jp.NP) {
-            t.rbeg = jp.offR[t.q];
-            t.rend = jp.offR[t.q + 1];
-            t.sbeg = jp.offS[t.q];
-            t.send = jp.offS[t.q + 1];
-            // partitions above JN_HEAVY probe tuples are split into tasks (k_heavy_tasks)
-            t.active = t.rbeg < t.rend && t.sbeg < t.send && t.send - t.sbeg <= JN_HEAVY;
-        }
-        return t;
-    };
-
-    // item j of a thread is element ((j/4)*TH + tid)*4 + j%4: four consecutive
-    // tuples per 16-byte load
-    uint32_t rw[RPT][RW];
-    uint32_t sw[SPT][SW];
-    // item j of a thread holds element item_index(j): four consecutive tuples per 16-byte load
-    // of a word array, two consecutive {key, carry} pairs per load of a packed array
-    auto item_index = [&](int j, bool packed) -> uint32_t {
-        return packed ? ((j / 2) * TH + threadIdx.x) * 2 + (j % 2)
-                      : ((j / 4) * TH + threadIdx.x) * 4 + (j % 4);
-    };
-    constexpr bool packR = (PK & 1) != 0, packS = (PK & 2) != 0;
-    constexpr bool aosR = (PK & 4) != 0, aosS = (PK & 8) != 0;
-    static_assert(!aosR || (KW == 1 && CWR == 2), "12-byte build tuples: key + two-word carry");
-    static_assert(!aosS || (KW == 1 && CWS == 2), "12-byte probe tuples: key + two-word carry");
-    // four consecutive 12-byte tuples = three 16-byte loads (dword aligned)
-    auto load_aos3 = [&](const uint32_t* base, uint32_t n, auto& regs, auto n_items) {
-        constexpr int NI = decltype(n_items)::value;
-#pragma unroll
-        for (int v = 0; v < NI / 4; ++v) {
-            const uint32_t  i0 = (v * TH + threadIdx.x) * 4;
-            const uint32_t* p = base + (size_t)i0 * 3;
-            if (i0 + 3 < n) {
-                const u32x4a x = *reinterpret_cast<const u32x4a*>(p), y = *reinterpret_cast<const u32x4a*>(p + 4),
-                             z = *reinterpret_cast<const u32x4a*>(p + 8);
-                regs[4 * v + 0][0] = x[0];
-                regs[4 * v + 0][1] = x[1];
-                regs[4 * v + 0][2] = x[2];
-                regs[4 * v + 1][0] = x[3];
-                regs[4 * v + 1][1] = y[0];
-                regs[4 * v + 1][2] = y[1];
-                regs[4 * v + 2][0] = y[2];
-                regs[4 * v + 2][1] = y[3];
-                regs[4 * v + 2][2] = z[0];
-                regs[4 * v + 3][0] = z[1];
-                regs[4 * v + 3][1] = z[2];
-                regs[4 * v + 3][2] = z[3];
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) regs[4 * v + e][a] = i0 + e < n ? p[e * 3 + a] : 0u;
-            }
-        }
-    };
-    static_assert(!packR || (KW == 1 && CWR == 1), "packed build side: key + one carry word");
-    static_assert(!packS || (KW == 1 && CWS == 1), "packed probe side: key + one carry word");
-    auto load_build = [&](uint32_t rc, uint32_t rn) {
-        constexpr int LW = RW;
-        if constexpr (aosR) {
-            load_aos3(jp.R.w[0] + (size_t)rc * 3, rn, rw, std::integral_constant<int, RPT>{});
-            return;
-        }
-        if constexpr (packR) {
-            {
-                const uint2* rp = reinterpret_cast<const uint2*>(jp.R.w[0]) + rc;
-#pragma unroll
-                for (int v = 0; v < RPT / 2; ++v) {
-                    const uint32_t i0 = (v * TH + threadIdx.x) * 2;
-                    if (i0 + 1 < rn) {
-                        u32x4a x = *reinterpret_cast<const u32x4a*>(rp + i0);
-                        rw[2 * v][0] = x[0];
-                        rw[2 * v][1] = x[1];
-                        rw[2 * v + 1][0] = x[2];
-                        rw[2 * v + 1][1] = x[3];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 2; ++e) {
-                            uint2 t = i0 + e < rn ? rp[i0 + e] : make_uint2(0u, 0u);
-                            rw[2 * v + e][0] = t.x;
-                            rw[2 * v + e][1] = t.y;
-                        }
-                    }
-                }
-                return;
-            }
-        }
-        constexpr int NA = CWR >= 2 ? KW + CWR - 2 : LW;  // plain word arrays; the last two carry words are a pair array
-#pragma unroll
-        for (int v = 0; v < RPT / 4; ++v) {
-            const uint32_t i0 = (v * TH + threadIdx.x) * 4;
-            if (i0 + 3 < rn) {
-#pragma unroll
-                for (int a = 0; a < NA; ++a) {
-                    u32x4a x = *reinterpret_cast<const u32x4a*>(jp.R.w[a] + rc + i0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) rw[4 * v + e][a] = x[e];
-                }
-                if constexpr (CWR >= 2) {
-                    const uint32_t* p2 = jp.R.w[NA] + ((size_t)rc + i0) * 2;
-                    u32x4a x = *reinterpret_cast<const u32x4a*>(p2), y = *reinterpret_cast<const u32x4a*>(p2 + 4);
-                    rw[4 * v + 0][NA] = x[0];
-                    rw[4 * v + 0][NA + 1] = x[1];
-                    rw[4 * v + 1][NA] = x[2];
-                    rw[4 * v + 1][NA + 1] = x[3];
-                    rw[4 * v + 2][NA] = y[0];
-                    rw[4 * v + 2][NA + 1] = y[1];
-                    rw[4 * v + 3][NA] = y[2];
-                    rw[4 * v + 3][NA + 1] = y[3];
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int a = 0; a < NA; ++a)
-                        rw[4 * v + e][a] = i0 + e < rn ? jp.R.w[a][rc + i0 + e] : 0u;
-                    if constexpr (CWR >= 2) {
-                        uint2 t = i0 + e < rn ? reinterpret_cast<const uint2*>(jp.R.w[NA])[rc + i0 + e]
-                                              : make_uint2(0u, 0u);
-                        rw[4 * v + e][NA] = t.x;
-                        rw[4 * v + e][NA + 1] = t.y;
-                    }
-                }
-            }
-        }
-    };
-    auto load_probe = [&](uint32_t sc, uint32_t sn) {
-        if constexpr (aosS) {
-            load_aos3(jp.S.w[0] + (size_t)sc * 3, sn, sw, std::integral_constant<int, SPT>{});
-            return;
-        }
-        if constexpr (packS) {
-            {
-                const uint2* sp = reinterpret_cast<const uint2*>(jp.S.w[0]) + sc;
-#pragma unroll
-                for (int v = 0; v < SPT / 2; ++v) {
-                    const uint32_t i0 = (v * TH + threadIdx.x) * 2;
-                    if (i0 + 1 < sn) {
-                        u32x4a x = *reinterpret_cast<const u32x4a*>(sp + i0);
-                        sw[2 * v][0] = x[0];
-                        sw[2 * v][1] = x[1];
-                        sw[2 * v + 1][0] = x[2];
-                        sw[2 * v + 1][1] = x[3];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 2; ++e) {
-                            uint2 t = i0 + e < sn ? sp[i0 + e] : make_uint2(0u, 0u);
-                            sw[2 * v + e][0] = t.x;
-                            sw[2 * v + e][1] = t.y;
-                        }
-                    }
-                }
-                return;
-            }
-        }
-        constexpr int NA = CWS >= 2 ? KW + CWS - 2 : SW;  // plain word arrays; the last two carry words are a pair array
-#pragma unroll
-        for (int v = 0; v < SPT / 4; ++v) {
-            const uint32_t i0 = (v * TH + threadIdx.x) * 4;
-            if (i0 + 3 < sn) {
-#pragma unroll
-                for (int a = 0; a < NA; ++a) {
-                    u32x4a x = *reinterpret_cast<const u32x4a*>(jp.S.w[a] + sc + i0);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) sw[4 * v + e][a] = x[e];
-                }
-                if constexpr (CWS >= 2) {
-                    const uint32_t* p2 = jp.S.w[NA] + ((size_t)sc + i0) * 2;
-                    u32x4a x = *reinterpret_cast<const u32x4a*>(p2), y = *reinterpret_cast<const u32x4a*>(p2 + 4);
-                    sw[4 * v + 0][NA] = x[0];
-                    sw[4 * v + 0][NA + 1] = x[1];
-                    sw[4 * v + 1][NA] = x[2];
-                    sw[4 * v + 1][NA + 1] = x[3];
-                    sw[4 * v + 2][NA] = y[0];
-                    sw[4 * v + 2][NA + 1] = y[1];
-                    sw[4 * v + 3][NA] = y[2];
-                    sw[4 * v + 3][NA + 1] = y[3];
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int a = 0; a < NA; ++a)
-                        sw[4 * v + e][a] = i0 + e < sn ? jp.S.w[a][sc + i0 + e] : 0u;
-                    if constexpr (CWS >= 2) {
-                        uint2 t = i0 + e < sn ? reinterpret_cast<const uint2*>(jp.S.w[NA])[sc + i0 + e]
-                                              : make_uint2(0u, 0u);
-                        sw[4 * v + e][NA] = t.x;
-                        sw[4 * v + e][NA + 1] = t.y;
-                    }
-                }
-            }
-        }
-    };
-    // one output row: key + build carry + probe carry
-    auto emit_row = [&](uint64_t row, uint32_t klo, uint32_t khi, uint32_t b0, uint32_t b1,
-                        uint32_t p0, uint32_t p1, uint32_t b2 = 0u, uint32_t p2 = 0u) {
-        if constexpr (OM == OM_PAGED32) {
-            // one page/slot computation serves all three streams
-            uint32_t r = (uint32_t)row, p = r / ROWS32;
-            size_t   off = (size_t)p * PAGE_BYTES + HDR32 + (r - p * ROWS32) * 4u;
-            *reinterpret_cast<uint32_t*>(jp.key.base + off) = klo;
-            if constexpr (CWR >= 1) *reinterpret_cast<uint32_t*>(jp.bc.base + off) = b0;
-            if constexpr (CWS >= 1) *reinterpret_cast<uint32_t*>(jp.pc.base + off) = p0;
-        } else if constexpr (OM == OM_P32_64_64) {
-            // one page/slot computation serves both 64-bit streams
-            const uint32_t r = (uint32_t)row, p4 = r / ROWS32, p8 = r / ROWS64;
-            *reinterpret_cast<uint32_t*>(jp.key.base + (size_t)p4 * PAGE_BYTES + HDR32 + (r - p4 * ROWS32) * 4u) = klo;
-            const size_t off8 = (size_t)p8 * PAGE_BYTES + HDR64 + (r - p8 * ROWS64) * 8u;
-            *reinterpret_cast<uint2*>(jp.bc.base + off8) = make_uint2(b0, b1);
-            *reinterpret_cast<uint2*>(jp.pc.base + off8) = make_uint2(p0, p1);
-        } else if constexpr (OM == OM_DENSE32) {
-            reinterpret_cast<uint32_t*>(jp.key.base)[row] = klo;
-            if constexpr (CWR >= 1) reinterpret_cast<uint32_t*>(jp.bc.base)[row] = b0;
-            if constexpr (CWS >= 1) reinterpret_cast<uint32_t*>(jp.pc.base)[row] = p0;
-        } else {
-            stream_store(jp.key, row, klo, khi);
-            if constexpr (CWR >= 1) stream_store(jp.bc, row, b0, b1, b2);
-            if constexpr (CWS >= 1) stream_store(jp.pc, row, p0, p1, p2);
-        }
-    };
-
-    unsigned long long diag_t = jp.diag ? __builtin_amdgcn_s_memtime() : 0ull;
-    const uint32_t     n_tasks = heavy_wg ? 1u : (uint32_t)PPW;
-    Task               cur = get_task(0);
-    // haveR / haveS: the first build chunk / first probe sub-chunk of `cur` already sit in
-    // rw / sw (prefetched while the previous partition was being probed / before its build)
-    bool haveR = false, haveS = false;
-    for (uint32_t k = 0; k < n_tasks; ++k) {
-        const Task nxt = get_task(k + 1);
-        if (!cur.active) {
-            cur = nxt;
-            haveR = haveS = false;
-            continue;
-        }
-        if (!haveR) load_build(cur.rbeg, min((uint32_t)JN_RMAX, cur.rend - cur.rbeg));
-        if (!haveS) load_probe(cur.sbeg, min((uint32_t)SUB, cur.send - cur.sbeg));
-        uint32_t sw_pos = cur.sbeg;  // which probe sub-chunk sw holds
-        RJ_STAMP(0);  // loads issued
-
-        // The low radix bits every hashed key of partition q shares, rebuilt from q
-        // (q = ((d1*F2)+d2)*F3+d3, hash low bits = d1 | d2<<b1 | d3<<(b1+b2)); EMPTY differs
-        // from them in bit 0, so no stored key can equal it.
-        uint32_t qbits = 0;
-        {
-            uint32_t rem = cur.q, sh = jp.radix_bits;
-            for (int p = (int)jp.n_pass - 1; p >= 0; --p) {
-                uint32_t b = jp.pass_bits[p];
-                sh -= b;
-                qbits |= (rem & ((1u << b) - 1u)) << sh;
-                rem >>= b;
-            }
-        }
-        // TG: no build index reaches 0x1fff (a table holds JN_RMAX = 4096 tuples), so no slot equals
-        // the all-ones word, and with >= 14 radix bits no tag (<= 18 bits) equals its 19 tag bits
-        constexpr uint32_t TGB = 19, TGM = (1u << TGB) - 1u;
-        static_assert(JN_RMAX <= (1u << (32 - TGB)) - 1u, "build index field of a tagged slot");
-        const uint32_t EMPTY = TG ? 0xffffffffu : (qbits ^ 1u);
-
-        for (uint32_t rc = cur.rbeg; rc < cur.rend; rc += JN_RMAX) {
-            const uint32_t rn = min((uint32_t)JN_RMAX, cur.rend - rc);
-            if (rc != cur.rbeg) load_build(rc, rn);
-            {  // clear the key array, 16 bytes per store
-                const uint4 e4 = make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
-                uint4*      t4 = reinterpret_cast<uint4*>(&t_w[0][0]);
-                for (uint32_t i = threadIdx.x; i < JN_CAP / 4; i += TH) t4[i] = e4;
-                uint4* c4 = reinterpret_cast<uint4*>(&t_cnt[0]);
-                for (uint32_t i = threadIdx.x; i < JN_CAP / 16; i += TH)
-                    c4[i] = make_uint4(0, 0, 0, 0);
-            }
-            lds_barrier();
-            RJ_STAMP(1);  // table cleared
-            // ---- build
-#pragma unroll
-            for (int j = 0; j < RPT; ++j) {
-                uint32_t i = item_index(j, packR);
-                if (i < rn) {
-                    uint32_t b = (rw[j][0] >> jp.radix_bits) & BMASK;
-                    if constexpr (TG) t_c2[i] = make_uint2(rw[j][1], rw[j][2]);
-                    while (true) {
-                        uint32_t pos = atomicAdd(&t_cnt[b], 1u);
-                        if (pos < 4) {
-                            const uint32_t slot = b * 4 + pos;
-                            if constexpr (TG) {
-                                t_w[0][slot] = (rw[j][0] >> jp.radix_bits) | (i << TGB);
-                            } else {
-#pragma unroll
-                                for (int a = 0; a < RW; ++a) t_w[a][slot] = rw[j][a];
-                            }
-                            break;
-                        }
-                        b = (b + 1) & BMASK;  // bucket full: overflow to the next one
-                    }
-                }
-            }
-            lds_barrier();
-            RJ_STAMP(2);  // built
-            // rw is dead now: start the NEXT partition's build loads behind this probe
-            const bool last_chunk = rc + JN_RMAX >= cur.rend;
-            if (last_chunk && nxt.active)
-                load_build(nxt.rbeg, min((uint32_t)JN_RMAX, nxt.rend - nxt.rbeg));
-
-            // ---- probe, SUB tuples at a time
-            for (uint32_t sc = cur.sbeg; sc < cur.send; sc += SUB) {
-                const uint32_t sn = min((uint32_t)SUB, cur.send - sc);
-                if (sw_pos != sc) {
-                    load_probe(sc, sn);
-                    sw_pos = sc;
-                }
-                uint32_t m[SPT], f[SPT];
-                // count matches, remember the first matching slot
-#pragma unroll
-                for (int j = 0; j < SPT; ++j) {
-                    uint32_t i = item_index(j, packS);
-                    m[j] = 0;
-                    f[j] = 0;
-                    if (i < sn) {
-                        uint32_t b = (sw[j][0] >> jp.radix_bits) & BMASK;
-                        while (true) {
-                            const uint4 kv = *reinterpret_cast<const uint4*>(&t_w[0][b * 4]);
-                            if constexpr (TG) {
-                                const uint32_t tag = sw[j][0] >> jp.radix_bits;
-                                const uint32_t eq = (uint32_t)((kv.x & TGM) == tag) | ((uint32_t)((kv.y & TGM) == tag) << 1) |
-                                                    ((uint32_t)((kv.z & TGM) == tag) << 2) | ((uint32_t)((kv.w & TGM) == tag) << 3);
-                                if (eq) {
-                                    // f = build tuple index of the FIRST match (its carries: t_c2[f])
-                                    if (m[j] == 0) f[j] = ((eq & 1u) ? kv.x : (eq & 2u) ? kv.y : (eq & 4u) ? kv.z : kv.w) >> TGB;
-                                    m[j] += (uint32_t)__popc(eq);
-                                }
-                                if (kv.w == EMPTY) break;
-                                b = (b + 1) & BMASK;
-                                continue;
-                            }
-                            uint32_t    eq = (uint32_t)(kv.x == sw[j][0]) | ((uint32_t)(kv.y == sw[j][0]) << 1) |
-                                          ((uint32_t)(kv.z == sw[j][0]) << 2) | ((uint32_t)(kv.w == sw[j][0]) << 3);
-                            if (KW == 2 && eq) {
-                                const uint4 hv = *reinterpret_cast<const uint4*>(&t_w[KW - 1][b * 4]);
-                                eq &= (uint32_t)(hv.x == sw[j][KW - 1]) | ((uint32_t)(hv.y == sw[j][KW - 1]) << 1) |
-                                      ((uint32_t)(hv.z == sw[j][KW - 1]) << 2) | ((uint32_t)(hv.w == sw[j][KW - 1]) << 3);
-                            }
-                            if (eq) {
-                                if (m[j] == 0) f[j] = b * 4 + (uint32_t)__builtin_ctz(eq);
-                                m[j] += (uint32_t)__popc(eq);
-                            }
-                            if (kv.w == EMPTY) break;  // bucket not full: nothing overflowed
-                            b = (b + 1) & BMASK;
-                        }
-                    }
-                }
-                RJ_STAMP(3);  // counted
-                // offsets inside the wave: ballot + mbcnt when every lane has <= 1 match
-                // (the PK-FK case), shuffle scan otherwise
-                uint32_t pre[SPT];
-                uint32_t wave_total = 0;
-#pragma unroll
-                for (int j = 0; j < SPT; ++j) {
-                    uint32_t tot;
-                    if (__ballot(m[j] > 1) == 0) {
-                        uint64_t mk = __ballot(m[j] == 1);
-                        pre[j] = lane_prefix(mk);
-                        tot = (uint32_t)__popcll(mk);
-                    } else {
-                        uint32_t incl = m[j];
-#pragma unroll
-                        for (int off = 1; off < 64; off <<= 1) {
-                            uint32_t t = __shfl_up(incl, off);
-                            if (lane >= (uint32_t)off) incl += t;
-                        }
-                        pre[j] = incl - m[j];
-                        tot = __shfl(incl, 63);
-                    }
-                    pre[j] += wave_total;
-                    wave_total += tot;
-                }
-                if (lane == 0) s_wtot[wid] = wave_total;
-                lds_barrier();
-                RJ_STAMP(4);  // wave prefixes + barrier
-                if (threadIdx.x == 0) {
-                    uint32_t tot = 0;
-                    for (int w = 0; w < TH / 64; ++w) tot += s_wtot[w];
-                    s_obase = tot ? atomicAdd(jp.out_cursor, (unsigned long long)tot) : 0ull;
-                }
-                lds_barrier();
-                RJ_STAMP(5);  // output reservation
-                const uint64_t gbase = s_obase;
-                uint64_t       obase = gbase;
-                uint32_t       block_total = 0;
-                for (uint32_t w = 0; w < TH / 64; ++w) {
-                    uint32_t t = s_wtot[w];
-                    if (w < wid) obase += t;
-                    block_total += t;
-                }
-                // rows beyond the stream capacity are counted but not written; the host
-                // re-runs the join with exact-size buffers (out_cursor = rows needed)
-                const bool fits = gbase + block_total <= jp.out_cap;
-                if (fits) {
-                    // the build carry of a tuple's FIRST match sits at the remembered slot
-                    // f[j]: issue those reads for all tuples before the first store
-                    // (TG reads them row by row instead: its registers are spoken for)
-                    uint32_t c0[TG ? 1 : SPT], c1[TG ? 1 : SPT], c2[CWR == 3 ? SPT : 1];
-                    if constexpr (!TG) {
-#pragma unroll
-                        for (int j = 0; j < SPT; ++j) {
-                            c0[j] = 0;
-                            c1[j] = 0;
-                            if constexpr (CWR >= 1) c0[j] = m[j] ? t_w[KW][f[j]] : 0u;
-                            if constexpr (CWR >= 2) c1[j] = m[j] ? t_w[KW + 1][f[j]] : 0u;
-                            if constexpr (CWR == 3) c2[j] = m[j] ? t_w[KW + 2][f[j]] : 0u;
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < SPT; ++j) {
-                        if (m[j] == 0) continue;
-                        uint64_t row = obase + pre[j];
-                        uint32_t klo, khi = 0;
-                        unhash_key<KW>(sw[j][0], sw[j][KW - 1], klo, khi);
-                        const uint32_t p0 = CWS >= 1 ? sw[j][KW < SW ? KW : 0] : 0u;
-                        const uint32_t p1 = CWS >= 2 ? sw[j][KW + 1 < SW ? KW + 1 : 0] : 0u;
-                        const uint32_t p2 = CWS == 3 ? sw[j][SW - 1] : 0u;
-                        if constexpr (TG) {
-                            const uint2 c = t_c2[f[j]];
-                            emit_row(row, klo, khi, c.x, c.y, p0, p1, 0u, p2);
-                        } else {
-                            emit_row(row, klo, khi, c0[j], c1[j], p0, p1, CWR == 3 ? c2[CWR == 3 ? j : 0] : 0u, p2);
-                        }
-                        if constexpr (TG) {
-                            // duplicates of the build key (rare): walk the buckets again from the
-                            // home bucket and emit every match but the first
-                            if (m[j] > 1) {
-                                const uint32_t tag = sw[j][0] >> jp.radix_bits;
-                                uint32_t       left = m[j], b = tag & BMASK;
-                                while (left) {
-                                    const uint4 kv = *reinterpret_cast<const uint4*>(&t_w[0][b * 4]);
-                                    const uint32_t sv[4] = {kv.x, kv.y, kv.z, kv.w};
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) {
-                                        if ((sv[e] & TGM) == tag && left) {
-                                            if (left != m[j]) {  // the first match went out above
-                                                ++row;
-                                                const uint2 c = t_c2[sv[e] >> TGB];
-                                                emit_row(row, klo, khi, c.x, c.y, p0, p1, 0u, p2);
-                                            }
-                                            --left;
-                                        }
-                                    }
-                                    b = (b + 1) & BMASK;
-                                }
-                            }
-                            continue;
-                        }
-                        // duplicates of the build key occupy further slots of the same run
-                        uint32_t left = m[j] - 1;
-                        uint32_t slot = (f[j] + 1) & SMASK;
-                        while (left) {
-                            bool eq = t_w[0][slot] == sw[j][0];
-                            if (KW == 2) eq = eq && t_w[KW - 1][slot] == sw[j][KW - 1];
-                            if (eq) {
-                                ++row;
-                                uint32_t b0 = 0, b1 = 0, b2 = 0;
-                                if constexpr (CWR >= 1) b0 = t_w[KW][slot];
-                                if constexpr (CWR >= 2) b1 = t_w[KW + 1][slot];
-                                if constexpr (CWR == 3) b2 = t_w[KW + 2][slot];
-                                emit_row(row, klo, khi, b0, b1, p0, p1, b2, p2);
-                                --left;
-                            }
-                            slot = (slot + 1) & SMASK;
-                        }
-                    }
-                }
-                RJ_STAMP(6);  // emitted
-                lds_barrier();  // s_wtot / s_obase are reused by the next sub-chunk
-            }
-            lds_barrier();  // table is cleared for the next build chunk
-        }
-        // sw is dead now: start the next partition's probe loads behind its table build
-        if (nxt.active) load_probe(nxt.sbeg, min((uint32_t)SUB, nxt.send - nxt.sbeg));
-        haveR = haveS = nxt.active;
-        cur = nxt;
-    }
-}
-
 // ============================================================ broadcast join
 // A build side of at most JN_RMAX rows (the filtered dimension tables of the JOB plans: a
 // handful of rows against millions) needs no partitioning: every workgroup builds the SAME
@@ -2083,53 +1381,6 @@ __global__ __launch_bounds__(jn_threads(TG ? 2 : KW + CWR), jn_min_waves(TG ? 2 
 // The table keeps key words + the build ROW; build carries are fetched from the build
 // columns on emit (a few KB: cache resident).  With no radix digit to derive an EMPTY
 // sentinel from, a slot is valid when its index is below its bucket's insert counter.
-template <int KW>
-__device__ __forceinline__ bool src_key(const TupleSrc& s, uint32_t row, uint32_t& lo, uint32_t& hi) {
-    bool ok = s.key.valid ? s.key.valid[row] != 0 : true;
-    if constexpr (KW == 1) {
-        uint32_t v = col_load32(s.key, row);
-        lo = s.prehashed ? v : fmix32(v);
-        hi = 0;
-    } else {
-        uint64_t k = col_load64(s.key, row);
-        if (s.key_f64 && (k & 0x7ff0000000000000ull) == 0x7ff0000000000000ull &&
-            (k & 0x000fffffffffffffull))
-            ok = false;  // NaN never matches (see SrcLoader::hash_keys)
-        uint64_t h = fmix64(k);
-        lo = (uint32_t)h;
-        hi = (uint32_t)(h >> 32);
-    }
-    return ok;
-}
-template <int CW>
-__device__ __forceinline__ void src_carry(const TupleSrc& s, uint32_t row, uint32_t& c0, uint32_t& c1, uint32_t& c2) {
-    c0 = c1 = c2 = 0;
-    if constexpr (CW >= 1) {
-        if (s.carry_mode == CARRY_WIDE) {
-            if constexpr (CW >= 2) {
-                if (s.wide == WIDE_64_32) {
-                    const uint64_t v = col_load64(s.carry, row);
-                    c0 = (uint32_t)v;
-                    c1 = (uint32_t)(v >> 32);
-                    c2 = col_load32(s.carry2, row);
-                } else {
-                    c0 = col_load32(s.carry, row);
-                    c1 = col_load32(s.carry2, row);
-                    if constexpr (CW == 3) c2 = col_load32(s.carry3, row);
-                }
-            }
-        } else if (s.carry_mode == CARRY_ROWIDX) {
-            c0 = row;
-        } else if constexpr (CW == 1) {
-            c0 = col_load32(s.carry, row);
-        } else {
-            uint64_t v = col_load64(s.carry, row);
-            c0 = (uint32_t)v;
-            c1 = (uint32_t)(v >> 32);
-        }
-    }
-}
-
 template <int KW, int CWR, int CWS>
 __global__ __launch_bounds__(JN_THREADS) void k_join_bcast(BcastParams bp) {
     constexpr int RW = KW + 1;  // key words + build row
@@ -2281,7 +1532,6 @@ __global__ __launch_bounds__(JN_THREADS) void k_join_bcast(BcastParams bp) {
 // EMPTY is the all-ones word; a filter key whose hash is all ones sets a flag instead of a slot.
 // The home slot is the multiplicative hash of the key words: their low radix bits are the same for
 // a whole partition, the product's high bits are not.
-constexpr uint32_t ilog2_u32(uint32_t v) { return v > 1 ? 1 + ilog2_u32(v / 2) : 0; }
 static_assert((JN_CAP & (JN_CAP - 1)) == 0, "set slots: a power of two");
 
 template <int KW>
@@ -2549,376 +1799,6 @@ __global__ __launch_bounds__(JN_THREADS) void k_filter_join(FilterParams fp) {
         filter_emit<KW, SPT>(fp, e, klo, khi, s_wtot, &s_obase, [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
             tuple_carry<KW, CWS>(sw[j], p0, p1, p2);
         });
-    }
-}
-
-// ============================================================ outer joins
-// RJ_NODE_OUTER: the inner join's rows (duplicates multiply) plus, ONCE, every preserved row that
-// has no partner, with NULL in the optional (build) side's columns.  Both halves come out of one
-// pass over the preserved tuples and through one output cursor.
-// The LDS table is k_join_bcast's: buckets of four slots with an insert counter each (a slot is
-// valid when its index is below the counter; a counter above 4 sends the walk on to the next
-// bucket), key words + a REFERENCE to the build tuple (its row in the child for k_outer_bcast, its
-// index in the partitioned arrays for k_outer_join).  The optional side's carry is fetched through
-// the reference on emit: a few KB per table, cache resident.  (KW + 1) * 32 KiB + 8 KiB of LDS:
-// 72 KiB (two workgroups per CU) for 32-bit keys, 104 KiB (one) for 64-bit keys.
-// The home bucket is the multiplicative hash of the key words: their low radix bits are the same
-// for a whole partition, the product's high bits are not.
-// A padded row carries "NULL" in-band (rj_device.hpp, OuterParams): the build carry's first word is
-// op.pad_bc, the others zero.
-template <int KW>
-struct OuterTable {
-    static constexpr uint32_t NB = JN_CAP / 4, BMASK = NB - 1, LOG2 = ilog2_u32(NB);
-    uint32_t (*w)[JN_CAP];  // [KW + 1]
-    uint32_t* cnt;          // [NB]
-
-    __device__ __forceinline__ static uint32_t home(uint32_t lo, uint32_t hi) {
-        return ((lo ^ hi) * 0x9e3779b1u) >> (32 - LOG2);
-    }
-    // every thread of the workgroup; the caller puts a barrier behind it
-    __device__ __forceinline__ void clear() const {
-        for (uint32_t i = threadIdx.x; i < NB; i += blockDim.x) cnt[i] = 0;
-    }
-    // at most JN_RMAX inserts per table (load <= 50 %), so the walk ends
-    __device__ __forceinline__ void insert(uint32_t lo, uint32_t hi, uint32_t ref) const {
-        uint32_t b = home(lo, hi);
-        while (true) {
-            const uint32_t pos = atomicAdd(&cnt[b], 1u);
-            if (pos < 4) {
-                const uint32_t slot = b * 4 + pos;
-                w[0][slot] = lo;
-                if constexpr (KW == 2) w[1][slot] = hi;
-                w[KW][slot] = ref;
-                return;
-            }
-            b = (b + 1) & BMASK;
-        }
-    }
-    // matches of one key in bucket b: bit mask over its valid slots; `more`: the bucket overflowed
-    __device__ __forceinline__ uint32_t match(uint32_t b, uint32_t lo, uint32_t hi, bool& more) const {
-        const uint32_t c = cnt[b];
-        const uint4    kv = *reinterpret_cast<const uint4*>(&w[0][b * 4]);
-        uint32_t       eq = (uint32_t)(kv.x == lo) | ((uint32_t)(kv.y == lo) << 1) | ((uint32_t)(kv.z == lo) << 2) |
-                      ((uint32_t)(kv.w == lo) << 3);
-        if constexpr (KW == 2) {
-            const uint4 hv = *reinterpret_cast<const uint4*>(&w[1][b * 4]);
-            eq &= (uint32_t)(hv.x == hi) | ((uint32_t)(hv.y == hi) << 1) | ((uint32_t)(hv.z == hi) << 2) |
-                  ((uint32_t)(hv.w == hi) << 3);
-        }
-        more = c > 4;
-        return eq & ((1u << min(c, 4u)) - 1u);
-    }
-};
-
-// Probe SPT items per thread against the table and emit: every match of an item with probe[j]
-// set, and one padded row for an item with padrow[j] set that has no match now and had none
-// before (hit[j], which is updated).  Offsets from the wave ballots (a shuffle scan where some lane
-// has several matches), ONE global reservation for the workgroup; rows beyond the stream capacity
-// are counted, not written (the host runs the probe again with exact-size streams).
-// bcarry(ref, b0, b1, b2) / pcarry(j, p0, p1, p2) deliver the carries.  Contains barriers: every
-// thread of the workgroup calls it.
-// FULL (RJ_NODE_FULL, compile time): every matched build tuple is also recorded — bit
-// (ref - flag_base) of the workgroup's LDS words s_flag, which the caller merges into the node's
-// flags in HBM — and no key stream is written (a full outer join has none).  The counting loop
-// records, not the emitting one: a run that only counts (streams too small) flags all the same.
-template <bool FULL, int KW, int CWB, int CWP, int SPT, class BCarry, class PCarry>
-__device__ __forceinline__ void outer_emit(const OuterParams& op, const OuterTable<KW>& T, const bool (&probe)[SPT],
-                                           const bool (&padrow)[SPT], bool (&hit)[SPT], const uint32_t (&klo)[SPT],
-                                           const uint32_t (&khi)[SPT], uint32_t* s_wtot, unsigned long long* s_obase,
-                                           BCarry bcarry, PCarry pcarry, uint32_t* s_flag = nullptr,
-                                           uint32_t flag_base = 0) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t       m[SPT], cnt[SPT], pre[SPT], wave_total = 0;
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-        m[j] = 0;
-        if (probe[j]) {
-            uint32_t b = OuterTable<KW>::home(klo[j], khi[j]);
-            bool     more;
-            do {
-                uint32_t eq = T.match(b, klo[j], khi[j], more);
-                m[j] += (uint32_t)__popc(eq);
-                if constexpr (FULL) {
-                    while (eq) {
-                        const uint32_t bit = T.w[KW][b * 4 + (uint32_t)__builtin_ctz(eq)] - flag_base;
-                        eq &= eq - 1;
-                        // (a hot build tuple is flagged by many probes: look before the atomic)
-                        if (!((s_flag[bit >> 5] >> (bit & 31u)) & 1u)) atomicOr(&s_flag[bit >> 5], 1u << (bit & 31u));
-                    }
-                }
-                b = (b + 1) & OuterTable<KW>::BMASK;
-            } while (more);
-        }
-        hit[j] = hit[j] || m[j] != 0;
-        cnt[j] = m[j] ? m[j] : ((padrow[j] && !hit[j]) ? 1u : 0u);
-    }
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-        uint32_t tot;
-        if (__ballot(cnt[j] > 1) == 0) {
-            const uint64_t mk = __ballot(cnt[j] == 1);
-            pre[j] = lane_prefix(mk);
-            tot = (uint32_t)__popcll(mk);
-        } else {
-            uint32_t incl = cnt[j];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t t = __shfl_up(incl, off);
-                if (lane >= (uint32_t)off) incl += t;
-            }
-            pre[j] = incl - cnt[j];
-            tot = __shfl(incl, 63);
-        }
-        pre[j] += wave_total;
-        wave_total += tot;
-    }
-    if (lane == 0) s_wtot[wid] = wave_total;
-    lds_barrier();
-    if (threadIdx.x == 0) {
-        uint32_t tot = 0;
-        for (uint32_t w = 0; w < nw; ++w) tot += s_wtot[w];
-        *s_obase = tot ? atomicAdd(op.out_cursor, (unsigned long long)tot) : 0ull;
-    }
-    lds_barrier();
-    const uint64_t gbase = *s_obase;
-    uint64_t       obase = gbase;
-    uint32_t       block_total = 0;
-    for (uint32_t w = 0; w < nw; ++w) {
-        const uint32_t t = s_wtot[w];
-        if (w < wid) obase += t;
-        block_total += t;
-    }
-    if (gbase + block_total <= op.out_cap) {
-#pragma unroll
-        for (int j = 0; j < SPT; ++j) {
-            if (cnt[j] == 0) continue;
-            uint64_t row = obase + pre[j];
-            uint32_t k0 = 0, k1 = 0;
-            if (!FULL && op.key.mode != ST_NONE) unhash_key<KW>(klo[j], khi[j], k0, k1);
-            uint32_t p0 = 0, p1 = 0, p2 = 0;
-            if constexpr (CWP >= 1) pcarry(j, p0, p1, p2);
-            if (m[j] == 0) {  // no partner in any round: the padded row
-                if constexpr (!FULL) stream_store(op.key, row, k0, k1);
-                if constexpr (CWB >= 1) stream_store(op.bc, row, op.pad_bc, 0u, 0u);
-                if constexpr (CWP >= 1) stream_store(op.pc, row, p0, p1, p2);
-                continue;
-            }
-            uint32_t b = OuterTable<KW>::home(klo[j], khi[j]);
-            bool     more;
-            do {
-                uint32_t eq = T.match(b, klo[j], khi[j], more);
-                while (eq) {
-                    const uint32_t slot = b * 4 + (uint32_t)__builtin_ctz(eq);
-                    eq &= eq - 1;
-                    if constexpr (!FULL) stream_store(op.key, row, k0, k1);
-                    if constexpr (CWB >= 1) {
-                        uint32_t b0, b1, b2;
-                        bcarry(T.w[KW][slot], b0, b1, b2);
-                        stream_store(op.bc, row, b0, b1, b2);
-                    }
-                    if constexpr (CWP >= 1) stream_store(op.pc, row, p0, p1, p2);
-                    ++row;
-                }
-                b = (b + 1) & OuterTable<KW>::BMASK;
-            } while (more);
-        }
-    }
-    lds_barrier();  // s_wtot / s_obase are reused by the next call
-}
-
-// Broadcast form: an optional side of at most JN_RMAX rows.  Every workgroup builds the SAME table
-// straight from the optional child's key column (page decode, NULL / NaN drop, hashing on the way)
-// and streams a grid-strided slice of the preserved child past it.  A preserved row whose key is
-// NULL or NaN has no partner and comes out padded here.  keyless (the key types differ) or an
-// empty optional side: no key is read or no tuple inserted, every row comes out padded.
-// The body (rj_outer_bcast_body.inc) is shared with k_full_bcast (FULL, compile time): there the workgroup also keeps one
-// matched bit per build row in LDS (JN_RMAX bits) and ORs its non-zero words into gflags at the end.
-template <int KW, int CWB, int CWP>
-__global__ __launch_bounds__(JN_THREADS) void k_outer_bcast(OuterParams op) {
-    constexpr bool FULL = false;
-    uint32_t* const gflags = nullptr;
-#include "rj_outer_bcast_body.inc"
-}
-
-// The partitioned path's leftovers: the preserved rows the first radix pass drops (NULL key; FP64
-// NaN key) have no partner, so they come out padded.  Grid-strided over the preserved child, the
-// same tuple formation (src_key / src_carry over the TupleSrc) and output cursor as the probe.
-template <int KW, int CWP>
-__global__ __launch_bounds__(JN_THREADS) void k_outer_nullkeys(OuterParams op) {
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const OuterTable<KW> T{nullptr, nullptr};  // (nothing is probed)
-    const uint32_t       n = op.P.n_rows;
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t klo[JN_SPT], khi[JN_SPT];
-        bool     probe[JN_SPT], padrow[JN_SPT], hit[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            klo[j] = khi[j] = 0;
-            probe[j] = hit[j] = false;
-            padrow[j] = row < n && !src_key<KW>(op.P, (uint32_t)row, klo[j], khi[j]);
-        }
-        // (the build carry's width is a run-time property of op.bc here: 1 stands for "some")
-        outer_emit<false, KW, 1, CWP, JN_SPT>(
-            op, T, probe, padrow, hit, klo, khi, s_wtot, &s_obase,
-            [&](uint32_t, uint32_t& b0, uint32_t& b1, uint32_t& b2) { b0 = b1 = b2 = 0; },
-            [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-                src_carry<CWP>(op.P, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), p0, p1, p2);
-            });
-    }
-}
-
-// Partitioned form: one workgroup per co-partition, or per heavy task of a preserved partition
-// above JN_HEAVY tuples (k_heavy_tasks; every task sees its partition's whole build side, and a
-// partition WITHOUT build tuples stays with its main workgroup, which pads it whole).  The loop
-// order is k_filter_join's: a JN_SUB-tuple chunk of preserved tuples stays in registers while the
-// partition's build tuples pass by in table rounds of JN_RMAX tuples; every round emits its
-// matches, a per-tuple "matched in some round" flag is OR-ed over the rounds, and the LAST round
-// also emits the padded rows of the tuples that never matched.  The usual partition needs one
-// round, i.e. one reservation per chunk.  No memory outside the registers holds a flag.
-// The body (rj_outer_join_body.inc) is shared with k_full_join (FULL, compile time).  There the build tuples that matched
-// must be known AFTER the launch, across the heavy tasks of a partition and across table rounds:
-// the workgroup collects one bit per build tuple of the current round in LDS (FW words: JN_RMAX
-// bits from the 32-aligned index below the round's first tuple) and ORs the non-zero words into
-// gflags (one bit per tuple of the partitioned build arrays) before the table is rebuilt and when
-// the task ends — a few hundred vector atomics per task, not one per match.
-template <int KW, int CWB, int CWP>
-__global__ __launch_bounds__(JN_THREADS) void k_outer_join(OuterParams op) {
-    constexpr bool FULL = false;
-    uint32_t* const gflags = nullptr;
-#include "rj_outer_join_body.inc"
-}
-
-// ======================================================= full outer joins
-// RJ_NODE_FULL: an outer join's rows plus, ONCE, every build row without a partner, with NULL in
-// the probed side's columns.  The probe kernels are the outer join's bodies with FULL set: they
-// write no key stream and leave one matched bit per build tuple in fp.flags.  The kernels below
-// run AFTER them in the same stream — the launch boundary makes every flag visible — and emit
-// the build rows through the same cursor and streams.
-template <int KW, int CWB, int CWP>
-__global__ __launch_bounds__(JN_THREADS) void k_full_bcast(FullParams fp) {
-    constexpr bool     FULL = true;
-    const OuterParams& op = fp.o;
-    uint32_t* const    gflags = fp.flags;
-#include "rj_outer_bcast_body.inc"
-}
-template <int KW, int CWB, int CWP>
-__global__ __launch_bounds__(JN_THREADS) void k_full_join(FullParams fp) {
-    constexpr bool     FULL = true;
-    const OuterParams& op = fp.o;
-    uint32_t* const    gflags = fp.flags;
-#include "rj_outer_join_body.inc"
-}
-
-// Rows for the items of one chunk a workgroup wants to emit: bit j of `emit` is the thread's item
-// j (lane-strided: item j of thread t is element j * JN_THREADS + t of the chunk).  Positions come
-// from the wave ballots, so the lanes of a wave write consecutive rows for each j; ONE reservation
-// on the output cursor per chunk.  Item j goes to row `first + pre[j]`; returns false when the
-// chunk's rows would pass the stream capacity (they are counted only).  Contains barriers: every
-// thread of the workgroup calls it.
-template <int SPT>
-__device__ __forceinline__ bool full_reserve(const OuterParams& op, uint32_t emit, uint32_t* s_wtot,
-                                             unsigned long long* s_obase, uint32_t (&pre)[SPT], uint64_t& first) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t       wave_total = 0;
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-        const uint64_t mk = __ballot((emit >> j) & 1u);
-        pre[j] = wave_total + lane_prefix(mk);
-        wave_total += (uint32_t)__popcll(mk);
-    }
-    if (lane == 0) s_wtot[wid] = wave_total;
-    lds_barrier();
-    if (threadIdx.x == 0) {
-        uint32_t tot = 0;
-        for (uint32_t w = 0; w < nw; ++w) tot += s_wtot[w];
-        *s_obase = tot ? atomicAdd(op.out_cursor, (unsigned long long)tot) : 0ull;
-    }
-    lds_barrier();
-    const uint64_t gbase = *s_obase;
-    uint32_t       before = 0, total = 0;
-    for (uint32_t w = 0; w < nw; ++w) {
-        const uint32_t t = s_wtot[w];
-        if (w < wid) before += t;
-        total += t;
-    }
-    first = gbase + before;
-    lds_barrier();  // s_wtot / s_obase are reused by the next call
-    return gbase + total <= op.out_cap;
-}
-
-// The build tuples nobody matched (partitioned path): a grid-strided walk over the partitioned
-// build arrays and the flags, lane-strided so that a wave reads 64 consecutive tuples and two flag
-// words per item and writes consecutive rows.  A tuple whose bit is clear comes out with its
-// carry as it is and the pad value (fp.pad_pc, then zeros) as the probed carry; which words the
-// probed carry stream takes is a run-time property of o.pc.
-template <int KW, int CWB>
-__global__ __launch_bounds__(JN_THREADS) void k_full_unmatched(FullParams fp) {
-    constexpr int BW = KW + CWB;
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const OuterParams& op = fp.o;
-    const uint32_t     n = op.offB[op.NP];
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t emit = 0, pre[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t i = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            if (i < n) emit |= (uint32_t)!((fp.flags[i >> 5] >> (i & 31u)) & 1u) << j;
-        }
-        uint64_t first;
-        if (!full_reserve<JN_SPT>(op, emit, s_wtot, &s_obase, pre, first)) continue;
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            if (!((emit >> j) & 1u)) continue;
-            const uint64_t row = first + pre[j];
-            if constexpr (CWB >= 1) {
-                uint32_t t[BW];
-                part_tuple<KW, CWB>(op.Bw, op.packB, op.aosB, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), t);
-                uint32_t b0, b1, b2;
-                tuple_carry<KW, CWB>(t, b0, b1, b2);
-                stream_store(op.bc, row, b0, b1, b2);
-            }
-            stream_store(op.pc, row, fp.pad_pc, 0u, 0u);
-        }
-    }
-}
-
-// Build rows straight from the built child's column: those whose key is missing (NULL; FP64 NaN;
-// any key when the key types differ) have no partner — the first radix pass dropped them, or the
-// broadcast table never held them — and, with fp.use_flags (broadcast path, flags by child row),
-// the rows whose flag stayed clear go out in the same sweep.
-template <int KW, int CWB>
-__global__ __launch_bounds__(JN_THREADS) void k_full_buildrows(FullParams fp) {
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const OuterParams& op = fp.o;
-    const uint32_t     n = op.B.n_rows;
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t emit = 0, pre[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t r = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            if (r >= n) continue;
-            uint32_t lo, hi;
-            bool     unmatched = op.keyless || !src_key<KW>(op.B, (uint32_t)r, lo, hi);
-            if (!unmatched && fp.use_flags) unmatched = !((fp.flags[r >> 5] >> (r & 31u)) & 1u);
-            emit |= (uint32_t)unmatched << j;
-        }
-        uint64_t first;
-        if (!full_reserve<JN_SPT>(op, emit, s_wtot, &s_obase, pre, first)) continue;
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            if (!((emit >> j) & 1u)) continue;
-            const uint64_t row = first + pre[j];
-            if constexpr (CWB >= 1) {
-                uint32_t b0, b1, b2;
-                src_carry<CWB>(op.B, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), b0, b1, b2);
-                stream_store(op.bc, row, b0, b1, b2);
-            }
-            stream_store(op.pc, row, fp.pad_pc, 0u, 0u);
-        }
     }
 }
 
@@ -3603,34 +2483,6 @@ __global__ __launch_bounds__(SEL_THREADS) void k_select(const SelectProg* __rest
 }
 
 // ================================================================== launchers
-// The one shape rule of the tuple kernels: one or two key words, zero to three carry words,
-// KW + CW <= MAX_WORDS.  for_shape turns run-time word counts into compile-time ones: it walks the
-// shapes in the order (KW, CW) and calls f(int_c<KW>, int_c<CW>) for the match, so a launcher
-// instantiates exactly the kernels of the rule; any other count is an unsupported launch.
-template <int N>
-using int_c = std::integral_constant<int, N>;
-
-template <int KW = 1, int CW = 0, class F>
-static void for_shape(const char* name, int kw, int cw, F&& f) {
-    if constexpr (KW > 2) {
-        launch_failed(name, "no kernel for this key/carry word count", true);
-    } else {
-        if constexpr (KW + CW <= MAX_WORDS)
-            if (kw == KW && cw == CW) return f(int_c<KW>{}, int_c<CW>{});
-        for_shape<(CW < 3 ? KW : KW + 1), (CW < 3 ? CW + 1 : 0)>(name, kw, cw, f);
-    }
-}
-
-// two carries behind the same key: f(int_c<KW>, int_c<CWA>, int_c<CWB>)
-template <class F>
-static void for_shape2(const char* name, int kw, int cwa, int cwb, F&& f) {
-    for_shape(name, kw, cwa, [&](auto KW, auto CWA) {
-        for_shape(name, kw, cwb, [&](auto KW2, auto CWB) {
-            if constexpr (decltype(KW2)::value == decltype(KW)::value) f(KW, CWA, CWB);
-        });
-    });
-}
-
 void launch_page_headers(const Launch& L, const uint8_t* pages, uint32_t n_pages, uint32_t rows_full,
                          uint32_t* page_rows, unsigned long long* flags) {
     if (!n_pages) return;
@@ -3876,90 +2728,6 @@ void launch_heavy_tasks(const Launch& L, const uint32_t* offR, const uint32_t* o
                n_heavy, max_tasks);
 }
 
-// tagged table (see k_join): one key word + two-word build carry, >= 14 radix bits
-static bool join_tagged(int key_words, int cw_build, const JoinParams& jp) {
-    return key_words == 1 && cw_build == 2 && jp.radix_bits >= 14 && jp.radix_bits <= 31;
-}
-
-template <int KW, int CWR, int CWS, int PK>
-static void join_pk(const Launch& L, const JoinParams& jp, uint32_t grid) {
-    const char* name = "join_build_probe";
-    // (the tagged table also serves a PACKED probe side — key + one carry word, PK bit 1: the shape of
-    // every join whose build side carries two words and whose probe side one; 1.45 -> 0.9 ms at 100 M rows)
-    if constexpr (KW == 1 && CWR == 2 && (PK & 1) == 0) {
-        const bool p366 = CWS == 2 && jp.key.mode == ST_PAGED32 && jp.bc.mode == ST_PAGED64 &&
-                          jp.pc.mode == ST_PAGED64;
-        if (join_tagged(KW, CWR, jp)) {
-            if constexpr (CWS == 2) {
-                if (p366) {
-                    RJ_KLAUNCH(L, name, (k_join<KW, CWR, CWS, OM_P32_64_64, PK, 1>), grid, jn_threads(2), jp);
-                    return;
-                }
-            }
-            RJ_KLAUNCH(L, name, (k_join<KW, CWR, CWS, OM_GENERIC, PK, 1>), grid, jn_threads(2), jp);
-            return;
-        }
-        if constexpr (CWS == 2) {
-            if (p366) {
-                RJ_KLAUNCH(L, name, (k_join<KW, CWR, CWS, OM_P32_64_64, PK, 0>), grid, jn_threads(KW + CWR), jp);
-                return;
-            }
-        }
-    }
-    // pick the straight-line emit variant when the stream layout allows it
-    int om = OM_GENERIC;
-    if (KW == 1 && CWR <= 1 && CWS <= 1) {
-        auto all = [&](int mode) {
-            return jp.key.mode == mode && (CWR == 0 || jp.bc.mode == mode) &&
-                   (CWS == 0 || jp.pc.mode == mode);
-        };
-        if (all(ST_PAGED32)) om = OM_PAGED32;
-        if (all(ST_DENSE32)) om = OM_DENSE32;
-    }
-    if constexpr (KW == 1 && CWR <= 1 && CWS <= 1) {
-        if (om == OM_PAGED32) {
-            RJ_KLAUNCH(L, name, (k_join<KW, CWR, CWS, OM_PAGED32, PK, 0>), grid, jn_threads(KW + CWR), jp);
-            return;
-        }
-        if (om == OM_DENSE32) {
-            RJ_KLAUNCH(L, name, (k_join<KW, CWR, CWS, OM_DENSE32, PK, 0>), grid, jn_threads(KW + CWR), jp);
-            return;
-        }
-    }
-    RJ_KLAUNCH(L, name, (k_join<KW, CWR, CWS, OM_GENERIC, PK, 0>), grid, jn_threads(KW + CWR), jp);
-}
-
-// the packed / 12-byte variants exist only for the shapes that can have them
-template <int KW, int CWR, int CWS>
-static void join_t(const Launch& L, const JoinParams& jp, uint32_t grid) {
-    constexpr int CAN = (KW == 1 && CWR == 1 ? 1 : 0) | (KW == 1 && CWS == 1 ? 2 : 0) |
-                        (KW == 1 && CWR == 2 ? 4 : 0) | (KW == 1 && CWS == 2 ? 8 : 0);
-    const int     pk = (jp.packR ? 1 : 0) | (jp.packS ? 2 : 0) | (jp.aosR ? 4 : 0) | (jp.aosS ? 8 : 0);
-    if (pk & ~CAN) launch_failed("join_build_probe", "tuple layout flags do not fit the key/carry widths", true);
-    auto packed = [&](auto... V) {  // the first layout V that is this join's: its kernel
-        auto one = [&](auto v) {
-            if constexpr ((CAN & v) == v)
-                if (pk == v) return join_pk<KW, CWR, CWS, v>(L, jp, grid), true;
-            return false;
-        };
-        return (... || one(V));
-    };
-    if (packed(int_c<1>{}, int_c<2>{}, int_c<3>{}, int_c<4>{}, int_c<8>{}, int_c<12>{}, int_c<6>{}, int_c<9>{})) return;
-    if (pk != 0) launch_failed("join_build_probe", "no kernel for this tuple layout", true);
-    join_pk<KW, CWR, CWS, 0>(L, jp, grid);
-}
-
-uint32_t join_partitions_per_workgroup(int key_words, int cw_build, const JoinParams& jp) {
-    return (uint32_t)jn_ppw(join_tagged(key_words, cw_build, jp) ? 2 : key_words + cw_build);
-}
-
-void launch_join(const Launch& L, int key_words, int cw_build, int cw_probe, const JoinParams& jp,
-                 uint32_t grid) {
-    if (!grid) return;
-    for_shape2("join_build_probe", key_words, cw_build, cw_probe,
-               [&](auto KW, auto CWR, auto CWS) { join_t<KW, CWR, CWS>(L, jp, grid); });
-}
-
 void launch_join_bcast(const Launch& L, int key_words, int cw_build, int cw_probe,
                        const BcastParams& bp, uint32_t grid) {
     if (!grid) return;
@@ -3987,61 +2755,6 @@ void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, co
     if (!grid) return;
     for_shape("filter_nullkeys", key_words, cw_preserved, [&](auto KW, auto CW) {
         RJ_KLAUNCH(L, "filter_nullkeys", (k_filter_nullkeys<KW, CW>), grid, JN_THREADS, fp);
-    });
-}
-
-// outer joins: the optional and the preserved side's carries
-void launch_outer_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
-                        uint32_t grid) {
-    if (!grid) return;
-    for_shape2("outer_broadcast", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
-        RJ_KLAUNCH(L, "outer_broadcast", (k_outer_bcast<KW, CWB, CWP>), grid, JN_THREADS, op);
-    });
-}
-
-void launch_outer_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const OuterParams& op,
-                       uint32_t grid) {
-    if (!grid) return;
-    for_shape2("outer_probe", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
-        RJ_KLAUNCH(L, "outer_probe", (k_outer_join<KW, CWB, CWP>), grid, JN_THREADS, op);
-    });
-}
-
-// full outer joins: the outer join's shapes, both carries optional
-void launch_full_bcast(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& op,
-                       uint32_t grid) {
-    if (!grid) return;
-    for_shape2("full_broadcast", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
-        RJ_KLAUNCH(L, "full_broadcast", (k_full_bcast<KW, CWB, CWP>), grid, JN_THREADS, op);
-    });
-}
-
-void launch_full_join(const Launch& L, int key_words, int cw_optional, int cw_preserved, const FullParams& op,
-                      uint32_t grid) {
-    if (!grid) return;
-    for_shape2("full_probe", key_words, cw_optional, cw_preserved, [&](auto KW, auto CWB, auto CWP) {
-        RJ_KLAUNCH(L, "full_probe", (k_full_join<KW, CWB, CWP>), grid, JN_THREADS, op);
-    });
-}
-
-void launch_full_unmatched(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid) {
-    if (!grid) return;
-    for_shape("full_unmatched", key_words, cw_built, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "full_unmatched", (k_full_unmatched<KW, CW>), grid, JN_THREADS, fp);
-    });
-}
-
-void launch_full_buildrows(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid) {
-    if (!grid) return;
-    for_shape("full_buildrows", key_words, cw_built, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "full_buildrows", (k_full_buildrows<KW, CW>), grid, JN_THREADS, fp);
-    });
-}
-
-void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, const OuterParams& op, uint32_t grid) {
-    if (!grid) return;
-    for_shape("outer_nullkeys", key_words, cw_preserved, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "outer_nullkeys", (k_outer_nullkeys<KW, CW>), grid, JN_THREADS, op);
     });
 }
 
@@ -4155,6 +2868,13 @@ void launch_select(const Launch& L, const SelectProg* prog, uint32_t n_ops, uint
                    unsigned long long* cursor, uint32_t grid) {
     if (!n_rows || !grid) return;
     RJ_KLAUNCH(L, "select", k_select, grid, SEL_THREADS, prog, n_ops, n_rows, out_ids, cursor);
+}
+
+// RJ_CTX_PREWARM: one harmless launch, so that HIP loads this translation unit's code object when the context is
+// built (as prewarm_varchar_dev does).  NP = 0: every thread of k_heavy_tasks leaves at `q >= NP`, its first check,
+// before any pointer is read.
+void prewarm_kernels(const Launch& L, uint32_t* zeroed) {
+    RJ_KLAUNCH(L, "prewarm", k_heavy_tasks, 1, 256, zeroed, zeroed, 0u, zeroed, zeroed, 0u);
 }
 
 }  // namespace rj

@@ -1,4 +1,5 @@
-// rj_kernels.hpp — host-callable launchers of the gfx950 kernels (rj_kernels.hip).
+// rj_kernels.hpp — host-callable launchers of the gfx950 kernels (rj_kernels.hip; k_join in rj_join.hip, the outer
+// and full outer joins in rj_outer.hip / rj_full.hip; the later families in the files named after them).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -282,6 +283,10 @@ void launch_vc_compact(const Launch& L, const uint8_t* keep, const uint32_t* bid
 // page_out == nullptr: pages_in_chunk[c] = pages of chunk c; else the pages are written to
 // page_out[page_base[c] ...]
 void prewarm_varchar_dev(const Launch& L, uint32_t* zeroed);  // (RJ_CTX_PREWARM: loads the code object)
+void prewarm_kernels(const Launch& L, uint32_t* zeroed);      // (... rj_kernels.hip's, rj_join.hip's, rj_outer.hip's and
+void prewarm_join(const Launch& L, uint32_t* zeroed);         //  rj_full.hip's: one launch each whose threads leave at
+void prewarm_outer(const Launch& L, uint32_t* zeroed);        //  the kernel's first bounds check)
+void prewarm_full(const Launch& L, uint32_t* zeroed);
 void launch_vc_walk(const Launch& L, const VcRow* rows, uint32_t n, uint32_t* pages_in_chunk,
                     const uint32_t* page_base, VcPage* page_out);
 void launch_vc_encode(const Launch& L, const uint8_t* pages, uint32_t n_pages, const VcRow* rows,

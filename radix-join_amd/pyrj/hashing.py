@@ -2,7 +2,7 @@
 
 INT32 keys use murmur3's fmix32, INT64/FP64 keys fmix64 (the reference hashes with fmix64,
 src/execute.cpp:21-27; the choice of hash is not observable in results).  Both are bijections,
-which is why partitions can store hashed keys and un-hash on emit (csrc/rj_kernels.hip).
+which is why partitions can store hashed keys and un-hash on emit (csrc/rj_tuple_util.hpp).
 Radix digits come from the LOW bits, LDS slot bits from the bits above them, and the sharding
 digit (which rank owns a key) from the TOP bits.
 """
@@ -45,7 +45,7 @@ M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def fmix64(k):
-    """murmur3 fmix64 over uint64 (INT64 keys, FP64 keys by bit pattern; csrc/rj_kernels.hip)."""
+    """murmur3 fmix64 over uint64 (INT64 keys, FP64 keys by bit pattern; csrc/rj_tuple_util.hpp)."""
     h = np.asarray(k).astype(np.uint64, copy=True)
     with np.errstate(over="ignore"):
         h ^= h >> np.uint64(33)

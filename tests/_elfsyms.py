@@ -2,7 +2,7 @@
 
 A `__global__` template instantiation leaves one host-side handle object per instantiation
 (`STT_OBJECT`, e.g. `_ZN2rj6k_joinILi1ELi2ELi2ELi3ELi12ELi1EEEvNS_10JoinParamsE`); the
-set of those named `rj::k_*` is what rj_kernels.hip / rj_varchar_dev.hip compiled.  The
+set of those named `rj::k_*` is what the kernel files (csrc/rj_*.hip) compiled.  The
 ingest kernels live in anonymous namespaces and are not listed."""
 import re
 import shutil
