@@ -407,6 +407,55 @@ typedef enum rj_status {
  *   2^32 - 16 child rows.  The node is checked before its child's rows are looked at.
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
+ *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * Set operations (UNION / INTERSECT / EXCEPT [ALL]; no reference counterpart).
+ * RJ_NODE_SETOP has TWO children, `left` and `right`; `build_left`, `base_table_id` and `right_attr` are
+ *   ignored.  rj_node cannot grow, so RJ_SETOP_OP(node) = `left_attr` is the operation (rj_setop).
+ *   Outputs: out_idx[k] = RJ_SETOP_OUT(l, r) pairs output column k with column l of the LEFT child's
+ *   outputs and column r of the RIGHT child's (SQL pairs by position; the plan carries the pairs so that
+ *   neither child needs a projection in front of it).  out_type[k] is the declared type, and BOTH columns
+ *   must have exactly that type: there is no implicit cast, an RJ_NODE_MAP below does that.  Pairs may
+ *   repeat and may come in any order.
+ *   Row and equality: a row is the tuple of the n_out output values.  Two rows are equal when they tie in
+ *   every column under rj_debug_sort_key's encoding — the grouping equalities of RJ_NODE_GROUP: NULL =
+ *   NULL per column, -0.0 = +0.0, NaN = NaN.
+ *   Multiplicities: for a row value with l copies on the left and r on the right the result holds
+ *     RJ_SET_UNION_ALL      l + r
+ *     RJ_SET_UNION          1 if l + r > 0
+ *     RJ_SET_INTERSECT      1 if l > 0 and r > 0
+ *     RJ_SET_INTERSECT_ALL  min(l, r)
+ *     RJ_SET_EXCEPT         1 if l > 0 and r == 0
+ *     RJ_SET_EXCEPT_ALL     max(l - r, 0)
+ *   copies.
+ *   Values: UNION ALL keeps every value's own bits, nothing is canonicalised.  The five other operations
+ *   output the run's CANONICAL value as RJ_NODE_GROUP does (rj_debug_sort_key_value): +0.0 for either
+ *   zero, 0x7ff8000000000000 for any NaN, NULL for NULL.  Their result is therefore one deterministic
+ *   multiset, whatever order the children's rows have and whichever side a copy came from.
+ *   Nullability: an output column is nullable when either paired column is (decided by the children's
+ *   columns, never by the data).
+ *   Order: the five sorting operations give their rows ordered by the output columns, the first most
+ *   significant, ascending, NULLs last, as RJ_NODE_SORT orders rows.  UNION ALL gives the left child's
+ *   rows followed by the right child's, each in the order that child has on the device: for SCAN
+ *   children the table order, otherwise unspecified.  As for RJ_NODE_SORT the order is promised ONLY
+ *   when the node is the plan's root; below another node the result is an ordinary relation, and a
+ *   parent of any kind may use every column of it, as a key too.  The node never passes an order promise
+ *   down to its children.
+ *   Empty inputs give the natural result: INTERSECT with an empty side 0 rows, EXCEPT ALL with an empty
+ *   right the left rows, canonicalised.  0 result rows come with the declared types and zero pages.
+ *   RJ_ERR_ARG: an operation code above RJ_SET_EXCEPT_ALL; n_out == 0; a column out of range on either
+ *   side; the two columns of a pair, or the declared type, disagreeing.
+ *   RJ_ERR_UNSUPPORTED: more than RJ_SORT_MAX_KEYS DISTINCT pairs in one of the five sorting operations
+ *   (UNION ALL takes any number); a VARCHAR pair in a sorting operation (a VARCHAR value travels as a row
+ *   id, its pages are not read here); a VARCHAR pair in UNION ALL whose two columns do not come from the
+ *   same base-table column (one row-id column cannot point into two tables); more than 2^32 - 16 rows in
+ *   the two children together.  A VARCHAR pair of UNION ALL from ONE base-table column is supported
+ *   (... FROM t WHERE a UNION ALL ... FROM t WHERE b): the row ids are concatenated.  (A child without rows
+ *   that is not a scan holds no row id and pairs with any VARCHAR column.)
+ *   The node is checked after its children ran but before their rows are looked at: empty children do
+ *   not hide an error.
+ *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
+ *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
  *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").                 */
 typedef enum rj_node_kind {
     RJ_NODE_SCAN = 0,
@@ -420,7 +469,8 @@ typedef enum rj_node_kind {
     RJ_NODE_SORT = 8,   /* ORDER BY / LIMIT / OFFSET over the one child `left` */
     RJ_NODE_GROUP = 9,  /* GROUP BY any keys, or none, over the one child `left` */
     RJ_NODE_WINDOW = 10, /* window functions OVER (PARTITION BY / ORDER BY) over the one child `left` */
-    RJ_NODE_MAP = 11     /* computed columns (scalar expressions) over the one child `left` */
+    RJ_NODE_MAP = 11,    /* computed columns (scalar expressions) over the one child `left` */
+    RJ_NODE_SETOP = 12   /* UNION / INTERSECT / EXCEPT [ALL] of the two children `left` and `right` */
 } rj_node_kind;
 
 /* Aggregate functions of RJ_NODE_AGG / RJ_NODE_GROUP and the encoding of their out_idx values. */
@@ -516,6 +566,15 @@ typedef enum rj_map_func {
 #define RJ_MAP_OUT(func, x) (((uint64_t)(func) << 56) | (uint64_t)(x))
 #define RJ_MAP_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
 #define RJ_MAP_ARG(x) ((uint64_t)(x) & 0x00ffffffffffffffull)
+
+/* The operation of an RJ_NODE_SETOP node (`node`: a const rj_node*) and the encoding of its out_idx
+ * values: the paired columns of the left and of the right child. */
+typedef enum rj_setop { RJ_SET_UNION_ALL = 0, RJ_SET_UNION = 1, RJ_SET_INTERSECT = 2,
+                        RJ_SET_INTERSECT_ALL = 3, RJ_SET_EXCEPT = 4, RJ_SET_EXCEPT_ALL = 5 } rj_setop;
+#define RJ_SETOP_OP(node)        ((node)->left_attr)
+#define RJ_SETOP_OUT(lcol, rcol) (((uint64_t)(rcol) << 32) | (uint64_t)(uint32_t)(lcol))
+#define RJ_SETOP_LCOL(x)         ((uint32_t)(x))
+#define RJ_SETOP_RCOL(x)         ((uint32_t)((uint64_t)(x) >> 32))
 
 /* One Column (include/plan.h:60-100): `pages[i]` points at an 8192-byte Page. */
 typedef struct rj_column {
@@ -757,15 +816,17 @@ void     rj_result_free(rj_result* r);
  * whose key hashes to that rank).  Collective: every process of the job must call it with the
  * same plan.  Shardable plans: every JoinNode carries at most one fixed-width non-key column per
  * side (the BASELINE shape), and no node is a semi, anti, outer or full outer join, an
- * aggregation, a selection, a sort, a grouping, a window or a map node; others return RJ_ERR_UNSUPPORTED.                                                                       */
+ * aggregation, a selection, a sort, a grouping, a window, a map or a set operation node; others return
+ * RJ_ERR_UNSUPPORTED.                                                                          */
 int rj_execute_sharded(rj_context* ctx, const rj_plan* plan, rj_table* const* tables,
                        uint64_t n_inputs, int32_t flags, rj_result** out /* [n local devices] */);
 /* 1 if rj_execute_sharded (and rj_execute on a multi-device context) can shard this plan, else 0
  * with the reason in `why` (optional, NUL-terminated, at most why_cap bytes).  Looks at the plan
  * only: needs neither a context nor a GPU.  A plan that holds a semi, anti, outer or full outer
- * join, an aggregation, a selection, a sort, a grouping, a window or a map node is not shardable; the
- * reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL / RJ_NODE_AGG /
- * RJ_NODE_SELECT / RJ_NODE_SORT / RJ_NODE_GROUP / RJ_NODE_WINDOW / RJ_NODE_MAP).                                                                                 */
+ * join, an aggregation, a selection, a sort, a grouping, a window, a map or a set operation node is not
+ * shardable; the reason names the kind (RJ_NODE_SEMI / RJ_NODE_ANTI / RJ_NODE_OUTER / RJ_NODE_FULL /
+ * RJ_NODE_AGG / RJ_NODE_SELECT / RJ_NODE_SORT / RJ_NODE_GROUP / RJ_NODE_WINDOW / RJ_NODE_MAP /
+ * RJ_NODE_SETOP).                                                                              */
 int rj_plan_shardable(const rj_plan* plan, char* why, size_t why_cap);
 
 /* The layout of the exchange step, as a pure function of the all-gathered count tensor (host

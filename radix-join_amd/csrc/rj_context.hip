@@ -41,6 +41,7 @@ void Tuning::from_env() {
     group_grid = env_int("RJ_TUNE_GROUP_GRID", group_grid);
     win_grid = env_int("RJ_TUNE_WIN_GRID", win_grid);
     map_grid = env_int("RJ_TUNE_MAP_GRID", map_grid);
+    setop_grid = env_int("RJ_TUNE_SETOP_GRID", setop_grid);
     exchange_timeout_ms = env_int("RJ_EXCHANGE_TIMEOUT_MS", exchange_timeout_ms);
     bringup_timeout_ms = env_int("RJ_BRINGUP_TIMEOUT_MS", bringup_timeout_ms);
     debug_shard_fail = env_int("RJ_DEBUG_SHARD_FAIL", debug_shard_fail);

@@ -522,4 +522,30 @@ struct WinScan {
     unsigned long long* mx;
 };
 
+// ---- Set operations (RJ_NODE_SETOP): the rows of both children in one relation (row id < n_left: a
+// left row), ordered and cut into runs by the sort's and the grouping's kernels; a run's rows and left
+// rows are differences of two prefix counts taken at its head and at the next run's, its multiplicity
+// follows from them (rj.h has the table), and an exclusive scan of the multiplicities says where its
+// copies go (rj_setop.hip).  Positions are walked in the grouping's geometry, runs in tiles of SETOP_TILE
+// and output rows in tiles of SETOP_EMIT_TILE.
+enum SetOp : int32_t {  // rj_setop
+    SETOP_UNION_ALL = 0,
+    SETOP_UNION = 1,
+    SETOP_INTERSECT = 2,
+    SETOP_INTERSECT_ALL = 3,
+    SETOP_EXCEPT = 4,
+    SETOP_EXCEPT_ALL = 5
+};
+constexpr int SETOP_THREADS = GROUP_THREADS;
+constexpr int SETOP_TILE = GROUP_TILE;                      // runs per tile of the multiplicity kernels
+constexpr int SETOP_ITEMS = SETOP_TILE / SETOP_THREADS;     // runs per thread
+constexpr int SETOP_EMIT_ITEMS = 4;                         // output rows per thread
+constexpr int SETOP_EMIT_TILE = SETOP_THREADS * SETOP_EMIT_ITEMS;
+// One entry per run and one behind the last (start[G] = rows, left[G] = left rows), so that run g has
+// start[g + 1] - start[g] rows, left[g + 1] - left[g] of them from the left child.
+struct SetopRuns {
+    uint32_t* start;  // position of the run's head
+    uint32_t* left;   // left rows in front of that position
+};
+
 }  // namespace rj

@@ -24,7 +24,8 @@ namespace rj {
 
 // What the plan walks know about a node kind: Exec::node, ShardedExec, first_unshardable and the
 // uploader's scan_order (rj_table.hip).  A new kind gets its line here, its driver in Exec and, if it has
-// one child, its case in Exec::node's switch (without one the walk reports "bad node kind").
+// one child, its case in Exec::node's switch (without one the walk reports "bad node kind"); a kind with
+// two children that is not a join is handed to its driver in front of join_kind().
 const NodeKind* node_kind(int kind) {
     static const NodeKind kinds[] = {
         {RJ_NODE_SCAN, "a scan", "RJ_NODE_SCAN", 0, true},
@@ -39,6 +40,7 @@ const NodeKind* node_kind(int kind) {
         {RJ_NODE_GROUP, "a grouping", "RJ_NODE_GROUP", 1, false},
         {RJ_NODE_WINDOW, "a window", "RJ_NODE_WINDOW", 1, false},
         {RJ_NODE_MAP, "a map", "RJ_NODE_MAP", 1, false},
+        {RJ_NODE_SETOP, "a set operation", "RJ_NODE_SETOP", 2, false},
     };
     for (const NodeKind& k : kinds)
         if (k.kind == kind) return &k;
@@ -460,6 +462,11 @@ class Exec {
             case RJ_NODE_WINDOW: return window(child, n, root_res);
             case RJ_NODE_MAP: return map(child, n, root_res);
             }
+        }
+        if (n.kind == RJ_NODE_SETOP) {  // (two children, no join; the order promise stops here)
+            Rel l = node(n.left, nullptr, depth + 1);
+            Rel r = node(n.right, nullptr, depth + 1);
+            return setop(l, r, n, root_res);
         }
         const JoinKind& K = join_kind(n.kind);
         Rel             l = node(n.left, nullptr, depth + 1);
@@ -2131,6 +2138,147 @@ class Exec {
             }());
         }
         return sink.out;
+    }
+
+    // ------------------------------------------------------------------ set operations
+    // RJ_NODE_SETOP (semantics in rj.h): UNION / INTERSECT / EXCEPT [ALL] of the two children.  UNION ALL
+    // puts every distinct pair of columns one behind the other (k_setop_concat) and is done.  The five
+    // other operations do that into a relation U of l.n + r.n rows (row id < l.n: a left row), order U by
+    // every column as a sort does and cut it into runs of equal rows as a grouping does; the k_setop_*
+    // kernels (rj_setop.hip) then count every run's rows and left rows, turn them into the run's
+    // multiplicity, scan the multiplicities and list, per output row, the run it is a copy of; the runs'
+    // canonical values (k_group_keys) are gathered through that list.  UNION takes every run once: the
+    // canonical values are the result.  Host syncs: one per column (its digit histograms), one for
+    // the run count and one for the output's row count.
+    static_assert((int)SETOP_UNION_ALL == (int)RJ_SET_UNION_ALL && (int)SETOP_UNION == (int)RJ_SET_UNION &&
+                      (int)SETOP_INTERSECT == (int)RJ_SET_INTERSECT && (int)SETOP_INTERSECT_ALL == (int)RJ_SET_INTERSECT_ALL &&
+                      (int)SETOP_EXCEPT == (int)RJ_SET_EXCEPT && (int)SETOP_EXCEPT_ALL == (int)RJ_SET_EXCEPT_ALL,
+                  "SetOp mirrors rj_setop");
+    Rel setop(Rel& l, Rel& r, const rj_node& n, Result* root_res) {
+        const uint64_t op = RJ_SETOP_OP(&n);
+        if (op > RJ_SET_EXCEPT_ALL) throw_fmt(RJ_ERR_ARG, "setop: unknown operation code %llu", (unsigned long long)op);
+        if (n.n_out == 0) throw_fmt(RJ_ERR_ARG, "setop: no output columns");
+        const bool sorting = op != RJ_SET_UNION_ALL;
+        std::vector<uint64_t> pairs;       // the distinct pairs, the first output's first
+        std::vector<uint64_t> out_cols;    // per output: its pair's index
+        for (uint64_t k = 0; k < n.n_out; ++k) {
+            const uint32_t lc = RJ_SETOP_LCOL(n.out_idx[k]), rc = RJ_SETOP_RCOL(n.out_idx[k]);
+            if (lc >= l.cols.size()) throw_fmt(RJ_ERR_ARG, "setop: left column %u out of range", lc);
+            if (rc >= r.cols.size()) throw_fmt(RJ_ERR_ARG, "setop: right column %u out of range", rc);
+            if (l.cols[lc].type != r.cols[rc].type)
+                throw_fmt(RJ_ERR_ARG, "setop: left column %u and right column %u differ in type (no implicit cast: map below)", lc, rc);
+            if (l.cols[lc].type != n.out_type[k]) throw_fmt(RJ_ERR_ARG, "setop: declared type differs from the paired columns' type");
+            const auto it = std::find(pairs.begin(), pairs.end(), n.out_idx[k]);
+            out_cols.push_back((uint64_t)(it - pairs.begin()));
+            if (it == pairs.end()) pairs.push_back(n.out_idx[k]);
+        }
+        if (sorting && pairs.size() > (size_t)SORT_MAX_KEYS)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "setop: more than %d distinct column pairs in a sorting operation", SORT_MAX_KEYS);
+        for (uint64_t p : pairs) {
+            const DCol &a = l.cols[RJ_SETOP_LCOL(p)], &b = r.cols[RJ_SETOP_RCOL(p)];
+            if (a.type != RJ_VARCHAR) continue;
+            if (sorting)
+                throw_fmt(RJ_ERR_UNSUPPORTED, "setop: VARCHAR pair (left column %u) in a sorting operation: a VARCHAR value travels as a "
+                                              "row id, its pages are not read here", RJ_SETOP_LCOL(p));
+            // (a relation without rows that no scan made — an empty selection's, say — has forgotten where its
+            // row ids would point: it holds none, so there is nothing to disagree about)
+            const bool known = !(l.n == 0 && a.vc_table < 0) && !(r.n == 0 && b.vc_table < 0);
+            if (known && (a.vc_table != b.vc_table || a.vc_col != b.vc_col))
+                throw_fmt(RJ_ERR_UNSUPPORTED, "setop: VARCHAR pair (left column %u, right column %u) from two base-table columns: one "
+                                              "row-id column cannot point into two tables", RJ_SETOP_LCOL(p), RJ_SETOP_RCOL(p));
+        }
+        const uint64_t rows64 = l.n + r.n;
+        if (l.n > 0xfffffff0ull || r.n > 0xfffffff0ull || rows64 > 0xfffffff0ull)
+            throw_fmt(RJ_ERR_UNSUPPORTED, "setop: more than 2^32 - 16 rows in the two children together");
+        if (rows64 == 0) return empty_rel(n, root_res);
+        const uint32_t rows = (uint32_t)rows64, n_left = (uint32_t)l.n;
+        if (ctx->tune.diag >= 2)
+            fprintf(stderr, "[rj diag] setop op=%llu left=%llu right=%llu pairs=%zu\n", (unsigned long long)op, (unsigned long long)l.n,
+                    (unsigned long long)r.n, pairs.size());
+
+        // one column of both children; to_pages: straight into Page images (a root column without NULLs)
+        auto concat = [&](uint64_t p, bool to_pages) {
+            const DCol &a = l.cols[RJ_SETOP_LCOL(p)], &b = r.cols[RJ_SETOP_RCOL(p)];
+            const bool nullable = a.valid != nullptr || b.valid != nullptr;
+            const int  mode = to_pages ? (a.width == 4 ? ST_PAGED32 : ST_PAGED64) : (a.width == 4 ? ST_DENSE32 : ST_DENSE64);
+            BufP       values = ctx->buf(stream_bytes(mode, rows));
+            DCol       d = dense_like(a, values, nullable ? ctx->buf(rows) : BufP());
+            if (to_pages) d.kind = COL_PAGED;
+            launch_setop_concat(L, a.ref(), b.ref(), n_left, rows, OutStream{values->as<uint8_t>(), mode, 0}, ptr<uint8_t>(d.hold_valid));
+            if (to_pages) launch_finish_pages(L, values->as<uint8_t>(), rows, a.width);
+            return d;
+        };
+
+        if (!sorting) {
+            Sink sink(this, root_res, rows);
+            for (uint64_t k = 0; k < n.n_out; ++k) {
+                const uint64_t p = n.out_idx[k];
+                sink.add(p, [&] {
+                    // one child without rows: the other child's column as it is
+                    if (r.n == 0) return l.cols[RJ_SETOP_LCOL(p)];
+                    if (l.n == 0) return r.cols[RJ_SETOP_RCOL(p)];
+                    const DCol &a = l.cols[RJ_SETOP_LCOL(p)], &b = r.cols[RJ_SETOP_RCOL(p)];
+                    return concat(p, root_res && a.type != RJ_VARCHAR && !a.valid && !b.valid);
+                });
+            }
+            return sink.out;
+        }
+
+        // ---- U, its order, the heads, the run count
+        Rel U;
+        U.n = rows;
+        std::vector<rj_sort_key> keys;
+        for (size_t c = 0; c < pairs.size(); ++c) {
+            U.cols.push_back(concat(pairs[c], false));
+            keys.push_back(rj_sort_key{(int32_t)c, 0});
+        }
+        const BufP     perm = order_by(U, keys);
+        const uint32_t n_tiles = rows / GROUP_TILE + (rows % GROUP_TILE != 0);
+        BufP           masks = ctx->buf(((uint64_t)rows + 63) / 64 * 8), tile_base = ctx->buf(((uint64_t)n_tiles + 1) * 4);
+        BufP           tile_heads = ctx->buf((uint64_t)n_tiles * 4), total = ctx->buf(4);
+        for (size_t c = 0; c < U.cols.size(); ++c) {
+            const DCol& col = U.cols[c];
+            launch_group_heads(L, col.ref(), ptr<uint32_t>(perm), rows, col.type == RJ_FP64, c == 0, c + 1 == U.cols.size(),
+                               masks->as<unsigned long long>(), tile_heads->as<uint32_t>());
+        }
+        launch_group_scan(L, tile_heads->as<uint32_t>(), rows, tile_base->as<uint32_t>(), total->as<uint32_t>());
+        uint32_t G = 0;
+        read_back(&G, total->p, 4);
+        if (G == 0 || G > rows) throw_fmt(RJ_ERR_DEVICE, "setop: %u runs out of %u rows", G, rows);
+
+        // ---- the runs' rows and left rows -> multiplicities -> where every run's copies go
+        const uint32_t max_grid = ctx->tune.setop_grid > 0 ? (uint32_t)ctx->tune.setop_grid : (uint32_t)ctx->compute_units() * 8u;
+        uint32_t       n_result = G;  // (UNION: every run once)
+        BufP           run_of;
+        if (op != RJ_SET_UNION) {
+            BufP            tile_left = ctx->buf((uint64_t)n_tiles * 4), tile_lbase = ctx->buf(((uint64_t)n_tiles + 1) * 4);
+            BufP            start = ctx->buf(((uint64_t)G + 1) * 4), left = ctx->buf(((uint64_t)G + 1) * 4);
+            const SetopRuns runs{start->as<uint32_t>(), left->as<uint32_t>()};
+            launch_setop_runs(L, ptr<uint32_t>(perm), rows, n_left, masks->as<unsigned long long>(), tile_base->as<uint32_t>(), G,
+                              tile_left->as<uint32_t>(), tile_lbase->as<uint32_t>(), runs, max_grid);
+            const uint32_t r_tiles = G / SETOP_TILE + (G % SETOP_TILE != 0);
+            BufP           tile_m = ctx->buf((uint64_t)r_tiles * 4), tile_mbase = ctx->buf(((uint64_t)r_tiles + 1) * 4);
+            BufP           off = ctx->buf(((uint64_t)G + 1) * 4), n_out_dev = ctx->buf(4);
+            launch_setop_offsets(L, runs, G, (int)op, tile_m->as<uint32_t>(), tile_mbase->as<uint32_t>(), off->as<uint32_t>(),
+                                 n_out_dev->as<uint32_t>(), max_grid);
+            read_back(&n_result, n_out_dev->p, 4);
+            if (n_result > rows) throw_fmt(RJ_ERR_DEVICE, "setop: %u result rows out of %u rows", n_result, rows);
+            if (n_result == 0) return empty_rel(n, root_res);
+            run_of = ctx->buf((uint64_t)n_result * 4);
+            launch_setop_emit(L, off->as<uint32_t>(), G, n_result, run_of->as<uint32_t>(), max_grid);
+        }
+        if (ctx->tune.diag >= 2) fprintf(stderr, "[rj diag] setop rows=%u runs=%u result=%u permuted=%d\n", rows, G, n_result, perm ? 1 : 0);
+
+        // ---- the runs' canonical values, gathered through the list (the run order is the result's order)
+        Rel K;
+        K.n = G;
+        for (const DCol& col : U.cols) {
+            const DCol d = new_col(col.type, G, col.valid != nullptr);
+            launch_group_keys(L, col.ref(), ptr<uint32_t>(perm), rows, col.type == RJ_FP64, masks->as<unsigned long long>(),
+                              tile_base->as<uint32_t>(), G, d.hold->as<uint8_t>(), ptr<uint8_t>(d.hold_valid));
+            K.cols.push_back(d);
+        }
+        return emit_rows(K, out_cols.data(), out_cols.size(), run_of, ptr<uint32_t>(run_of), n_result, root_res);
     }
 
     // ---------------------------------------------------------------------- window

@@ -233,6 +233,8 @@ struct Tuning {
     int map_grid = 0;     // RJ_TUNE_MAP_GRID: cap on the workgroups of k_map, so that a small input makes one workgroup walk several tiles (tests)
     int win_grid = 0;     // RJ_TUNE_WIN_GRID: cap on the quarter entries k_win_carry / k_win_tail_carry take per step, so that a
                           // small input takes several steps and carries from one to the next (0 = 1024, one per thread)
+    int setop_grid = 0;   // RJ_TUNE_SETOP_GRID: cap on the workgroups of the k_setop_* kernels that walk tiles, so that a small
+                          // input makes one workgroup walk several tiles (0 = 8 per compute unit)
     int exchange_timeout_ms = 120000;  // RJ_EXCHANGE_TIMEOUT_MS: bound on every wait of the exchange step of a
                                        // sharded join (communicator bring-up, count gathers, the all-to-all)
     int bringup_timeout_ms = 0;        // RJ_BRINGUP_TIMEOUT_MS: its own bound for the bring-up (0: the same) — in a

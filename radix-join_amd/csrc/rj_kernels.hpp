@@ -248,6 +248,25 @@ void launch_win_scan(const Launch& L, const ColRef& col, const uint32_t* perm, u
 void launch_win_column(const Launch& L, const unsigned long long* src, const uint32_t* nn, const uint32_t* peer_end, uint64_t n, int decode,
                        int width, uint8_t* dst, uint8_t* dst_valid);
 
+// ---- set operations (RJ_NODE_SETOP, rj_setop.hip): both children's rows in one relation of n_rows rows
+// (row id < n_left: a left row), ordered and cut into runs by the sort's and the grouping's kernels
+// (perm, masks, tile_base as above).  max_grid: cap on the workgroups of the kernels that walk tiles.
+// One column of both children, `r` behind `l` (n = rows of both): dst dense or Page images (the caller
+// finishes those), validity bytes where dst_valid is given (1 for a side without any)
+void launch_setop_concat(const Launch& L, const ColRef& l, const ColRef& r, uint32_t n_left, uint64_t n, const OutStream& dst,
+                         uint8_t* dst_valid);
+// k_setop_left, k_setop_scan, k_setop_runs: runs.start / runs.left [n_runs + 1]: where run g begins and the
+// left rows in front of it; entry n_runs = (n_rows, n_left).  tile_left [n_tiles], tile_lbase [n_tiles + 1]: scratch.
+void launch_setop_runs(const Launch& L, const uint32_t* perm, uint32_t n_rows, uint32_t n_left, const unsigned long long* masks,
+                       const uint32_t* tile_base, uint32_t n_runs, uint32_t* tile_left, uint32_t* tile_lbase, const SetopRuns& runs,
+                       uint32_t max_grid);
+// k_setop_mult, k_setop_scan, k_setop_offsets: off[n_runs + 1] = the exclusive scan of the runs' multiplicities
+// under `op` (SetOp), *total = off[n_runs] = the output rows.  tile_m [t], tile_mbase [t + 1], t = ceil(n_runs / SETOP_TILE): scratch.
+void launch_setop_offsets(const Launch& L, const SetopRuns& runs, uint32_t n_runs, int op, uint32_t* tile_m, uint32_t* tile_mbase,
+                          uint32_t* off, uint32_t* total, uint32_t max_grid);
+// run_of[j] = the run output row j is a copy of, j < n_out = off[n_runs]
+void launch_setop_emit(const Launch& L, const uint32_t* off, uint32_t n_runs, uint32_t n_out, uint32_t* run_of, uint32_t max_grid);
+
 // ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
 //      and Table::to_columnar, src/build_table.cpp:456-594)
 void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,

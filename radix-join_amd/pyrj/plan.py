@@ -54,6 +54,7 @@ NODE_SORT = 8
 NODE_GROUP = 9
 NODE_WINDOW = 10
 NODE_MAP = 11
+NODE_SETOP = 12
 # rj_sort_key::flags, RJ_SORT_NO_LIMIT
 SORT_DESC, SORT_NULLS_FIRST = 1, 2
 SORT_NO_LIMIT = 2**64 - 1
@@ -106,6 +107,22 @@ def map_func(x):
 
 def map_arg(x):
     return int(x) & ((1 << 56) - 1)
+
+
+# rj_setop and the RJ_SETOP_OUT / RJ_SETOP_LCOL / RJ_SETOP_RCOL encoding of a set operation's out_idx
+SET_UNION_ALL, SET_UNION, SET_INTERSECT, SET_INTERSECT_ALL, SET_EXCEPT, SET_EXCEPT_ALL = range(6)
+
+
+def setop_out(lcol, rcol):
+    return ((int(rcol) & 0xFFFFFFFF) << 32) | (int(lcol) & 0xFFFFFFFF)
+
+
+def setop_lcol(x):
+    return int(x) & 0xFFFFFFFF
+
+
+def setop_rcol(x):
+    return (int(x) >> 32) & 0xFFFFFFFF
 
 
 @dataclass
@@ -216,6 +233,18 @@ class MapNode:
 
 
 @dataclass
+class SetOpNode:
+    """Set operation (kind NODE_SETOP): `op` (SET_UNION_ALL ... SET_EXCEPT_ALL) of the children `left` and
+    `right`.  The PlanNode's output_attrs hold (RJ_SETOP_OUT(left column, right column), type) pairs: both
+    columns must have the declared type.  Rows are equal under the grouping equalities (NULL = NULL,
+    -0.0 = +0.0, NaN = NaN); every operation but UNION ALL gives canonical values, ordered by the output
+    columns, which is promised only at the plan's root (include/rj.h)."""
+    op: int
+    left: int
+    right: int
+
+
+@dataclass
 class PlanNode:
     data: object
     output_attrs: list  # [(index, DataType)]
@@ -294,6 +323,13 @@ class Plan:
         (or MAP_COL / MAP_EXPR for the names)."""
         oa = [(map_out(MAP_OUT_NAMES.get(f, f), x), t) for f, x, t in outputs]
         self.nodes.append(PlanNode(MapNode(child, [tuple(t) for t in (program or [])]), oa))
+        return len(self.nodes) - 1
+
+    def new_setop_node(self, op, left, right, outputs):
+        """UNION / INTERSECT / EXCEPT [ALL] of `left` and `right` (see SetOpNode).  outputs = [(left column,
+        right column, type)]."""
+        oa = [(setop_out(lc, rc), t) for lc, rc, t in outputs]
+        self.nodes.append(PlanNode(SetOpNode(int(op), left, right), oa))
         return len(self.nodes) - 1
 
     def _filter_node(self, kind, build_left, left, right, left_attr, right_attr, output_attrs):
@@ -567,6 +603,10 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.left = n.data.child
             nd.right = n_ops  # RJ_MAP_N_OPS / RJ_MAP_OPS: the struct cannot grow
             nd.right_attr = C.addressof(ops) if n_ops else 0
+        elif isinstance(n.data, SetOpNode):
+            nd.kind = NODE_SETOP
+            nd.left, nd.right = n.data.left, n.data.right
+            nd.left_attr = n.data.op  # RJ_SETOP_OP: the struct cannot grow
         else:
             nd.kind = 0
             nd.base_table_id = n.data.base_table_id
