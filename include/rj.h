@@ -157,7 +157,7 @@ typedef enum rj_status {
  *   nothing".  An empty child gives 0 rows with the declared column types and zero pages.
  *   RJ_ERR_ARG: a declared type other than the table above says, an unknown function code, a
  *   column out of range, RJ_AGG_KEY on another column than left_attr, RJ_AGG_COUNT_STAR with a
- *   column.  Key types are INT32 and INT64; FP64 and VARCHAR keys are RJ_ERR_UNSUPPORTED, and so are
+ *   column, RJ_AGG_FSUM (the exact FP64 sum is RJ_NODE_GROUP's).  Key types are INT32 and INT64; FP64 and VARCHAR keys are RJ_ERR_UNSUPPORTED, and so are
  *   FP64 and VARCHAR aggregated columns (a floating-point sum depends on the order of the rows,
  *   which no result of this library does).  The child may carry columns of any type that the node
  *   does not name.  Several functions over the same column cost one carried column.
@@ -265,6 +265,21 @@ typedef enum rj_status {
  *                       INT64; NULL if the group has no non-NULL value
  *     RJ_AGG_MIN / RJ_AGG_MAX  over the non-NULL values of an INT32 / INT64 / FP64 column; the
  *                       column's type; NULL if the group has no non-NULL value
+ *     RJ_AGG_FSUM       the exactly rounded sum of the non-NULL values of an FP64 column; FP64; NULL
+ *                       if the group has no non-NULL value (the count decides, never a sentinel);
+ *                       nullable when the child column is, or the child is empty, as RJ_AGG_SUM
+ *   RJ_AGG_FSUM, for every group and for the scalar aggregate: any NaN among the values, or +inf and
+ *   -inf together, give 0x7ff8000000000000.  Only +inf among the infinities gives +inf, only -inf
+ *   gives -inf, whatever the finite values are.  Otherwise the result is S, the exact real sum of the
+ *   finite values, rounded to nearest, ties to even, ONCE — what math.fsum returns.  |S| that rounds
+ *   to 2^1024 or more gives +-inf; there is no intermediate overflow (1e308 + 1e308 - 1e308 - 1e308
+ *   + 1.0 is 1.0); results in the subnormal range are exact, every double being a multiple of
+ *   2^-1074.  S = 0 gives +0.0, also when every value is -0.0: the canonical zero of this node's keys
+ *   and MIN / MAX.  The value depends only on the multiset of the child's rows: not on their order
+ *   on the device, not on how the inputs are cut into pages, not on RJ_TUNE_GROUP_GRID.  It may stand
+ *   next to KEY / COUNT(*) / COUNT / MIN / MAX over the same or other columns, in any order, repeated.
+ *   AVG is not a function of its own: an RJ_NODE_MAP above the node computes
+ *   FSUM(x) / TO_F64(COUNT(x)), which is NULL where the group has no value and rounds a second time.
  *   Grouping equality: two rows are in one group exactly when they tie on every key under
  *   rj_debug_sort_key's encoding.  So a NULL equals a NULL, per column — (NULL, 1), (1, NULL) and
  *   (NULL, NULL) are three groups —, -0.0 equals +0.0 and every NaN equals every other NaN.
@@ -283,10 +298,12 @@ typedef enum rj_status {
  *   any kind may use every column of it, as a key too.
  *   RJ_ERR_ARG: a key column or output column out of range; flag bits other than the two defined
  *   ones; n_keys != 0 with a NULL pointer; an unknown function code; RJ_AGG_KEY on a column that is
- *   not a key; RJ_AGG_COUNT_STAR with a column; a declared type other than the table above says.
+ *   not a key; RJ_AGG_COUNT_STAR with a column; a declared type other than the table above says;
+ *   RJ_AGG_FSUM on an INT32 / INT64 column (RJ_AGG_SUM is the integer sum).
  *   RJ_ERR_UNSUPPORTED: a VARCHAR key; a VARCHAR aggregated column (it travels as a row id, so
- *   MIN(title) is out of scope); SUM over an FP64 column (it depends on the order of the rows, which
- *   no result of this library does); more than RJ_SORT_MAX_KEYS keys; more than 2^32 - 16 child rows.
+ *   MIN(title) is out of scope); RJ_AGG_SUM over an FP64 column (a wrapping sum has no meaning there
+ *   and a sum of rounded additions depends on the order of the rows, which no result of this library
+ *   does: RJ_AGG_FSUM is the FP64 sum); more than RJ_SORT_MAX_KEYS keys; more than 2^32 - 16 child rows.
  *   The child may carry VARCHAR columns that the node does not name.  The node is checked before
  *   its child's rows are looked at: an empty child does not hide an error.
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
@@ -480,7 +497,9 @@ typedef enum rj_agg_func {
     RJ_AGG_COUNT      = 2,
     RJ_AGG_SUM        = 3,
     RJ_AGG_MIN        = 4,
-    RJ_AGG_MAX        = 5
+    RJ_AGG_MAX        = 5,
+    /* (6 and 7 are not assigned) */
+    RJ_AGG_FSUM       = 8 /* RJ_NODE_GROUP only: the exactly rounded sum of an FP64 column */
 } rj_agg_func;
 #define RJ_AGG_OUT(func, col) (((uint64_t)(func) << 56) | (uint64_t)(col))
 #define RJ_AGG_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
@@ -753,6 +772,13 @@ int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, u
  * context nor a GPU (an INT32 key is its low 32 bits).  RJ_ERR_ARG: another type, other flag bits, a
  * NULL pointer.                                                                                     */
 int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t* bits);
+/* RJ_AGG_FSUM of ONE group, run on the host through the add, merge and round functions the kernels
+ * call, in blocks of a few thousand values merged as the kernels merge their partial sums: bits[i] =
+ * the bits of value i, is_null[i] != 0 = NULL (is_null may be NULL: no NULLs).  *out_bits = the exactly
+ * rounded sum's bits, *out_is_null = 1 (and *out_bits = 0) when no value is left, as for n = 0.  Needs
+ * neither a context nor a GPU.  RJ_ERR_ARG: a NULL output pointer, or n != 0 without bits.          */
+int rj_debug_fsum(const uint64_t* bits, const uint8_t* is_null /* may be NULL */, uint64_t n,
+                  uint64_t* out_bits, int32_t* out_is_null);
 /* The program of an RJ_NODE_MAP node on ONE row, run on the host: it is validated by the code the
  * executor uses and evaluated through the op functions the kernel calls.  The row has n_cols columns:
  * col_type[c] (rj_dtype), col_bits[c] (the value's bits, an INT32's in the low word), col_null[c] != 0 =

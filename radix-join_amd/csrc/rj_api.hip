@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "rj_fsum.hpp"
 #include "rj_internal.hpp"
 #include "rj_sortkey.hpp"
 #include "rj_xplan.hpp"
@@ -194,6 +195,12 @@ int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t*
     if (!bits || (flags & ~(RJ_SORT_DESC | RJ_SORT_NULLS_FIRST))) return RJ_ERR_ARG;
     if (type != RJ_INT32 && type != RJ_INT64 && type != RJ_FP64) return RJ_ERR_ARG;
     *bits = rj::sort_key_value(key, type == RJ_INT32 ? 4 : 8, type == RJ_FP64, (flags & RJ_SORT_DESC) != 0);
+    return RJ_OK;
+}
+
+int rj_debug_fsum(const uint64_t* bits, const uint8_t* is_null, uint64_t n, uint64_t* out_bits, int32_t* out_is_null) {
+    if (!out_bits || !out_is_null || (n && !bits)) return RJ_ERR_ARG;
+    rj::fsum_host(bits, is_null, n, out_bits, out_is_null);
     return RJ_OK;
 }
 

@@ -1522,6 +1522,7 @@ class Exec {
             const uint32_t func = RJ_AGG_FUNC(n.out_idx[k]);
             const uint64_t col = RJ_AGG_COL(n.out_idx[k]);
             const int32_t  type = n.out_type[k];
+            if (func == RJ_AGG_FSUM) throw_fmt(RJ_ERR_ARG, "aggregation: RJ_AGG_FSUM is RJ_NODE_GROUP's, this kind has no FP64 sum");
             if (func > RJ_AGG_MAX) throw_fmt(RJ_ERR_ARG, "aggregation: unknown function code %u", func);
             int32_t expect = RJ_INT64;
             if (func == RJ_AGG_COUNT_STAR) {
@@ -2003,8 +2004,8 @@ class Exec {
     // (rj_group.hip).  Host syncs: one per key column (its digit histograms) and one for the group
     // count, which sizes the outputs.  Nothing is sized for a bound, nothing is attempted twice.
     struct GroupCol {
-        bool want_nn = false, want_sum = false, want_mn = false, want_mx = false;
-        BufP nn, sum, mn, mx;
+        bool want_nn = false, want_sum = false, want_mn = false, want_mx = false, want_fsum = false;
+        BufP nn, sum, mn, mx, fsum;
     };
     Rel group(Rel& child, const rj_node& n, Result* root_res) {
         const size_t                   cw = child.cols.size();
@@ -2023,7 +2024,7 @@ class Exec {
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint32_t func = RJ_AGG_FUNC(n.out_idx[k]);
             const uint64_t col = RJ_AGG_COL(n.out_idx[k]);
-            if (func > RJ_AGG_MAX) throw_fmt(RJ_ERR_ARG, "group: unknown function code %u", func);
+            if (func > RJ_AGG_MAX && func != RJ_AGG_FSUM) throw_fmt(RJ_ERR_ARG, "group: unknown function code %u", func);
             int32_t expect = RJ_INT64;
             if (func == RJ_AGG_COUNT_STAR) {
                 if (col != 0) throw_fmt(RJ_ERR_ARG, "group: COUNT(*) takes no column");
@@ -2041,13 +2042,19 @@ class Exec {
                                                       "travels as a row id, its pages are not read here", (unsigned long long)col);
                     if (func == RJ_AGG_SUM && c.type == RJ_FP64)
                         throw_fmt(RJ_ERR_UNSUPPORTED, "group: SUM over an FP64 column (child column %llu): a floating-point sum depends "
-                                                      "on the order of the rows", (unsigned long long)col);
+                                                      "on the order of the rows; RJ_AGG_FSUM is the exactly rounded FP64 sum",
+                                  (unsigned long long)col);
+                    if (func == RJ_AGG_FSUM && c.type != RJ_FP64)
+                        throw_fmt(RJ_ERR_ARG, "group: FSUM takes an FP64 column (child column %llu is not one): RJ_AGG_SUM is the "
+                                              "integer sum", (unsigned long long)col);
                     if (func == RJ_AGG_MIN || func == RJ_AGG_MAX) expect = c.type;
+                    if (func == RJ_AGG_FSUM) expect = RJ_FP64;
                     GroupCol& g = agg[(int)col];
                     g.want_nn = true;  // (COUNT itself, and what says whether SUM / MIN / MAX are NULL)
                     g.want_sum = g.want_sum || func == RJ_AGG_SUM;
                     g.want_mn = g.want_mn || func == RJ_AGG_MIN;
                     g.want_mx = g.want_mx || func == RJ_AGG_MAX;
+                    g.want_fsum = g.want_fsum || func == RJ_AGG_FSUM;
                 }
             }
             if (n.out_type[k] != expect) throw_fmt(RJ_ERR_ARG, "group: declared type differs from the function's result type");
@@ -2109,6 +2116,12 @@ class Exec {
             const ColRef   ref = c.ref();
             launch_group_reduce(L, &ref, dperm, rows, c.type == RJ_FP64, dmasks, dbase, G, acc, max_grid);
             rows_done = true;
+            if (g.want_fsum) {  // (the count above says which of its sums are NULL)
+                g.fsum = ctx->buf((uint64_t)G * 8);
+                BufP scratch = ctx->buf(fsum_scratch_bytes(rows, max_grid));
+                if (ctx->tune.diag >= 2) fprintf(stderr, "[rj diag] group fsum column=%d rows=%u groups=%u\n", kv.first, rows, G);
+                launch_fsum(L, ref, dperm, rows, dmasks, dbase, G, g.fsum->as<ull>(), max_grid, scratch->as<uint8_t>());
+            }
         }
         if (!rows_done) {
             const GroupAcc acc{ptr<ull>(rows_acc), nullptr, nullptr, nullptr, nullptr};
@@ -2126,10 +2139,10 @@ class Exec {
                 if (o.func == RJ_AGG_COUNT) return dense_col(type, agg.at(o.col).nn);
                 const GroupCol& g = agg.at(o.col);
                 const DCol&     c = child.cols[(size_t)o.col];
-                const BufP&     acc = o.func == RJ_AGG_SUM ? g.sum : (o.func == RJ_AGG_MIN ? g.mn : g.mx);
+                const BufP&     acc = o.func == RJ_AGG_FSUM ? g.fsum : (o.func == RJ_AGG_SUM ? g.sum : (o.func == RJ_AGG_MIN ? g.mn : g.mx));
                 // NULL where the group has no non-NULL value: a nullable column, or the one row over no rows
                 const bool nullable = c.valid != nullptr || rows == 0;
-                const int  decode = o.func == RJ_AGG_SUM ? GROUP_RAW : (c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64));
+                const int  decode = o.func == RJ_AGG_SUM || o.func == RJ_AGG_FSUM ? GROUP_RAW : (c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64));
                 if (decode == GROUP_RAW && !nullable) return dense_col(type, acc);
                 const DCol d = new_col(type, G, nullable);
                 launch_group_column(L, acc->as<ull>(), nullable ? g.nn->as<ull>() : nullptr, G, decode, d.width, d.hold->as<uint8_t>(),

@@ -230,6 +230,15 @@ void launch_group_reduce(const Launch& L, const ColRef* col, const uint32_t* per
 void launch_group_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int decode, int width,
                          uint8_t* dst, uint8_t* dst_valid);
 
+// ---- RJ_AGG_FSUM (rj_fsum.hip): out[g] = the bits of the exactly rounded sum of the non-NULL values of
+// the FP64 column `col` in group g (+0.0 where there is none: k_group_reduce's count says which are
+// NULL), every entry written whatever the memory held.  perm, masks, tile_base, max_grid and the scalar
+// aggregate as for launch_group_reduce; n_rows = 0 launches nothing.  scratch: fsum_scratch_bytes()
+// bytes, 8-byte aligned (the arena of the groups that runs of tiles share, and their slots).
+uint64_t fsum_scratch_bytes(uint32_t n_rows, uint32_t max_grid);
+void     launch_fsum(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, const unsigned long long* masks,
+                     const uint32_t* tile_base, uint32_t n_groups, unsigned long long* out, uint32_t max_grid, uint8_t* scratch);
+
 // ---- window functions (RJ_NODE_WINDOW): P / Q = the head masks of the partitions / the peer groups in
 // the grouping's layout, over the order the sort left; one entry per quarter of a tile in WinMarks / WinTails
 // (ceil(n_rows / WIN_QUARTER)); max_chunk: cap on the entries a carry kernel's workgroup takes per step

@@ -166,6 +166,7 @@ EXPORTS = [
     "rj_debug_parse_fp64",
     "rj_debug_sort_key",
     "rj_debug_sort_key_value",
+    "rj_debug_fsum",
     "rj_debug_map_eval",
     "rj_table_num_rows",
     "rj_table_col_pages",
@@ -679,6 +680,27 @@ def sort_key_value(dtype: int, flags: int, key: int) -> int:
     if rc != 0:
         raise RjError(rc, "rj_debug_sort_key_value: bad type or flags")
     return int(bits.value)
+
+
+def fsum(bits, is_null=None):
+    """rj_debug_fsum: RJ_AGG_FSUM of one group on the host, through the functions the kernels call.  bits: the
+    values' bits (uint64), is_null: optional flags (nonzero = NULL).  Returns the sum's bits, or None for
+    NULL (no value left)."""
+    L = load()
+    u64p = C.POINTER(C.c_uint64)
+    L.rj_debug_fsum.restype = C.c_int
+    L.rj_debug_fsum.argtypes = [u64p, C.POINTER(C.c_uint8), C.c_uint64, u64p, C.POINTER(C.c_int32)]
+    b = np.ascontiguousarray(bits, dtype=np.uint64)
+    nl = None if is_null is None else np.ascontiguousarray(is_null, dtype=np.uint8)
+    if nl is not None and nl.shape != b.shape:
+        raise ValueError("fsum: one NULL flag per value")
+    out, out_null = C.c_uint64(0), C.c_int32(0)
+    rc = L.rj_debug_fsum(b.ctypes.data_as(u64p) if b.size else None,
+                         nl.ctypes.data_as(C.POINTER(C.c_uint8)) if nl is not None and nl.size else None, b.size,
+                         C.byref(out), C.byref(out_null))
+    if rc != 0:
+        raise RjError(rc, "rj_debug_fsum: bad arguments")
+    return None if out_null.value else int(out.value)
 
 
 def map_eval(prog, row):

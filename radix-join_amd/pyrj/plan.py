@@ -60,6 +60,7 @@ SORT_DESC, SORT_NULLS_FIRST = 1, 2
 SORT_NO_LIMIT = 2**64 - 1
 # rj_agg_func and the RJ_AGG_OUT / RJ_AGG_FUNC / RJ_AGG_COL encoding of an aggregation's out_idx
 AGG_KEY, AGG_COUNT_STAR, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2, 3, 4, 5
+AGG_FSUM = 8  # RJ_NODE_GROUP only: the exactly rounded sum of an FP64 column (6 and 7 are not assigned)
 
 
 def agg_out(func, col):
