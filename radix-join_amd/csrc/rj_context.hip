@@ -306,13 +306,12 @@ void Context::prewarm() {
     RJ_HIP(hipMemcpyAsync(pinned, b->p, 256, hipMemcpyDeviceToHost, stream));
     RJ_HIP(hipMemcpyAsync(pinned_small, b->p, 64, hipMemcpyDeviceToHost, stream));
     RJ_HIP(hipMemsetAsync(b->p, 0, 256, stream));
-    // the code objects of the join path's four kernel files, then rj_varchar_dev.hip's
+    // the code objects of the join path's nine kernel files, then rj_varchar_dev.hip's
+    void (*const files[])(const Launch&, uint32_t*) = {prewarm_partition, prewarm_pages, prewarm_bcast, prewarm_filter,
+                                                       prewarm_agg,       prewarm_select, prewarm_join, prewarm_outer,
+                                                       prewarm_full,      prewarm_varchar_dev};
     uint32_t* const zeroed = b->as<uint32_t>();
-    prewarm_kernels(L, zeroed);
-    prewarm_join(L, zeroed);
-    prewarm_outer(L, zeroed);
-    prewarm_full(L, zeroed);
-    prewarm_varchar_dev(L, zeroed);
+    for (auto prewarm_file : files) prewarm_file(L, zeroed);
     sync();
 }
 

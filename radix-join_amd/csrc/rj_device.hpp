@@ -71,7 +71,7 @@ struct Words {
 
 // ---- Radix partition pass --------------------------------------------------
 // One workgroup sorts a tile of PT_TILE tuples by digit in LDS and writes each
-// digit's run contiguously (software write-combining), see rj_kernels.hip.
+// digit's run contiguously (software write-combining), see rj_partition.hip.
 // Geometry is overridable at build time (-DRJ_PT_THREADS=...) for tuning runs.
 #ifndef RJ_PT_THREADS
 #define RJ_PT_THREADS 1024

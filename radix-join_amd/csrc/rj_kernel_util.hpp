@@ -1,4 +1,4 @@
-// rj_kernel_util.hpp — what the kernel files (rj_kernels.hip, rj_join.hip, rj_outer.hip, rj_full.hip, rj_sort.hip, rj_group.hip, rj_window.hip, rj_setop.hip) share: wave / workgroup
+// rj_kernel_util.hpp — what every kernel file but rj_ingest.hip and rj_varchar_dev.hip shares: wave / workgroup
 // helpers, column loads and the launch macro.  Device code: include from a .hip file only.
 #pragma once
 #include <hip/hip_ext.h>

@@ -1,5 +1,22 @@
-// rj_kernels.hpp — host-callable launchers of the gfx950 kernels (rj_kernels.hip; k_join in rj_join.hip, the outer
-// and full outer joins in rj_outer.hip / rj_full.hip; the later families in the files named after them).
+// rj_kernels.hpp — host-callable launchers of every gfx950 (CDNA4, wave64) kernel, one block per kernel file.
+//
+// The radix join is integer / indexing work bound by HBM bandwidth (no MFMA):
+//   K0  page headers        rj_pages.hip      4 B read per 8 KiB page
+//   K1  page decode         rj_pages.hip      irregular (NULL-bearing) pages -> dense values + validity
+//   K2  pass histogram      rj_partition.hip  per-workgroup LDS histogram, flushed once per tile group
+//   K3  bin scan            rj_partition.hip  one workgroup per input segment, wave-shuffle scan
+//   K4  pass scatter        rj_partition.hip  tile of 16384 tuples sorted by digit in LDS (LDS atomics give the
+//                                             rank), runs written out contiguously = software write-combining
+//   K5/6 build + probe      rj_join.hip       per-partition bucketised hash table in LDS (one 16-byte read per
+//                                             probe), ballot/mbcnt output offsets, one global reservation per
+//                                             4096 probe tuples, streams written straight into Page images
+//                           rj_bcast.hip      (the broadcast form: a small build side, nothing partitioned)
+//   K7  gather              rj_pages.hip      row-id -> column value (generic late materialisation)
+//   K8  page finish/encode  rj_pages.hip      Page headers + validity bitmaps of the result
+// The other node kinds build on these: rj_filter.hip (semi / anti joins), rj_outer.hip, rj_full.hip (outer and full
+// outer joins), rj_agg.hip (hash aggregation), rj_select.hip, rj_map.hip, rj_sort.hip, rj_group.hip, rj_fsum.hip,
+// rj_window.hip, rj_setop.hip; rj_varchar_dev.hip holds the VARCHAR kernels.
+// Reference counterparts are cited at each kernel (paths relative to the reference).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +41,7 @@ struct Launch {
 // rj::Error (RJ_ERR_DEVICE / RJ_ERR_UNSUPPORTED).  Implemented in rj_context.hip.
 [[noreturn]] void launch_failed(const char* kernel, const char* what, bool unsupported);
 
+// ======================================================================================================== rj_pages.hip
 // ---- page metadata / decode (replaces Table::from_columnar, reference
 //      src/build_table.cpp:312-436, for fixed-width columns)
 // flags[0] = #pages breaking the "regular" shape, flags[1..2] = total rows (u64)
@@ -37,6 +55,29 @@ void launch_decode_pages(const Launch& L, const uint8_t* pages, uint32_t n_pages
                          const uint32_t* row_base, uint64_t num_rows, uint8_t* values,
                          uint8_t* valid);
 
+// ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
+//      and Table::to_columnar, src/build_table.cpp:456-594)
+void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,
+                   const OutStream& dst, uint8_t* dst_valid);
+// k_gather for an optional side's row-index stream: OUTER_NO_ROW gives a NULL (valid byte 0, value
+// 0) and is never dereferenced; dense values and validity bytes for every row
+void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
+                         uint8_t* dst_valid);
+void launch_finish_pages(const Launch& L, uint8_t* pages, uint64_t n_rows, int width);
+// headers + bitmaps of up to three probe-written streams, row count read on the device
+void launch_finish_streams(const Launch& L, uint8_t* const* pages, const int* widths, uint32_t n,
+                           const unsigned long long* n_rows_dev, uint64_t cap_rows);
+void launch_encode_nullable(const Launch& L, const uint8_t* values, const uint8_t* valid,
+                            uint64_t n_rows, int width, uint8_t* pages);
+// wide carries (several payload columns travelling with the key): validity bits of up to three
+// columns as one word per row; the emitted records -> one dense array (+ validity bytes) per column
+void launch_pack_validity(const Launch& L, const uint8_t* v0, const uint8_t* v1, const uint8_t* v2, uint32_t n,
+                          uint32_t* out);
+void launch_split_records(const Launch& L, const SplitParams& sp, uint64_t n);
+// test hook: keeps the stream busy for `ms` milliseconds (bounded; see RJ_DEBUG_SHARD_FAIL)
+void launch_debug_stall(const Launch& L, uint32_t ms);
+
+// ==================================================================================================== rj_partition.hip
 // ---- small single-workgroup scans
 // off[i] = sum_{j<i} in[j], off[n] = total; cursor (optional) = copy of off[0..n)
 void launch_scan_bins(const Launch& L, const uint32_t* in, uint32_t n, uint32_t* off,
@@ -104,19 +145,24 @@ void launch_pass_scatter_blocked(const Launch& L, const uint32_t* in_blocked, co
 void launch_pass_scatter_packed(const Launch& L, const uint32_t* in_pairs, const PassParams& pp,
                                 uint32_t n_groups, uint32_t* out_pairs);
 
-// ---- build + probe (replaces reference src/execute.cpp:196-249)
+// ---- the probe partitions above JN_HEAVY tuples, cut into tasks for the build + probe kernels
 void launch_heavy_tasks(const Launch& L, const uint32_t* offR, const uint32_t* offS, uint32_t NP,
                         uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks);
+
+// ========================================================================================================= rj_join.hip
+// ---- build + probe (replaces reference src/execute.cpp:196-249)
 // grid = jp.heavy_grid + ceil(jp.NP / join_partitions_per_workgroup(...))
 uint32_t join_partitions_per_workgroup(int key_words, int cw_build, const JoinParams& jp);
 void launch_join(const Launch& L, int key_words, int cw_build, int cw_probe, const JoinParams& jp,
                  uint32_t grid);
 
+// ======================================================================================================== rj_bcast.hip
 // Broadcast join: build side of at most JN_RMAX rows, no partitioning; `grid` workgroups stride
 // over the probe rows in chunks of JN_SUB.
 void launch_join_bcast(const Launch& L, int key_words, int cw_build, int cw_probe,
                        const BcastParams& bp, uint32_t grid);
 
+// ======================================================================================================= rj_filter.hip
 // ---- semi / anti joins (FilterParams): key_words 1 or 2, cw_preserved 0..MAX_WORDS - key_words
 // broadcast: filter side of at most JN_RMAX rows, `grid` workgroups stride over the preserved rows
 void launch_filter_bcast(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid);
@@ -126,6 +172,7 @@ void launch_filter_join(const Launch& L, int key_words, int cw_preserved, const 
 // FP64 NaN key) go out through the same cursor
 void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid);
 
+// ======================================================================================================== rj_outer.hip
 // ---- outer joins (OuterParams): key_words 1 or 2; cw_optional 0 (nothing), 1 (row index) or the
 // words of a wide carry; cw_preserved 0..MAX_WORDS - key_words
 // broadcast: optional side of at most JN_RMAX rows (or none / keys of another type)
@@ -137,11 +184,8 @@ void launch_outer_join(const Launch& L, int key_words, int cw_optional, int cw_p
 // after the partitioned probe: the preserved rows the first radix pass drops (NULL key, FP64 NaN
 // key) go out padded through the same cursor
 void launch_outer_nullkeys(const Launch& L, int key_words, int cw_preserved, const OuterParams& op, uint32_t grid);
-// k_gather for an optional side's row-index stream: OUTER_NO_ROW gives a NULL (valid byte 0, value
-// 0) and is never dereferenced; dense values and validity bytes for every row
-void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
-                         uint8_t* dst_valid);
 
+// ========================================================================================================= rj_full.hip
 // ---- full outer joins (FullParams): the outer join's shapes, both carries under the optional rules
 // (0 = nothing, 1 = row index, 2 / 3 = a wide record that ends in a validity word)
 // broadcast probe: built side of at most JN_RMAX rows (or none / keys of another type); ORs the
@@ -158,6 +202,7 @@ void launch_full_unmatched(const Launch& L, int key_words, int cw_built, const F
 // fp.use_flags, broadcast — the rows whose flag stayed clear, probed side padded
 void launch_full_buildrows(const Launch& L, int key_words, int cw_built, const FullParams& fp, uint32_t grid);
 
+// ========================================================================================================== rj_agg.hip
 // ---- aggregation (AggParams): key_words 1 or 2, carry_words 0..MAX_WORDS - key_words
 // the merge table's entries (ap.m_slots + 2) before anybody adds to them
 void launch_agg_merge_init(const Launch& L, const AggParams& ap, uint32_t grid);
@@ -172,6 +217,7 @@ void launch_agg_emit(const Launch& L, int key_words, const AggParams& ap, uint32
 void launch_agg_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int width,
                        uint8_t* dst, uint8_t* dst_valid);
 
+// ======================================================================================================= rj_select.hip
 // ---- selection (RJ_NODE_SELECT): the rows of [0, n_rows) for which the program (a device copy of
 // SelectProg, n_ops of its ops) leaves 1 -> their row ids in out_ids (room for n_rows), ascending
 // within every tile of SEL_TILE rows; *cursor (zeroed) += their number.  `grid` workgroups stride
@@ -179,12 +225,14 @@ void launch_agg_column(const Launch& L, const unsigned long long* src, const uns
 void launch_select(const Launch& L, const SelectProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t* out_ids,
                    unsigned long long* cursor, uint32_t grid);
 
+// ========================================================================================================== rj_map.hip
 // ---- computed columns (RJ_NODE_MAP, rj_map.hip): the n_ops ops of the program (a device copy of MapProg,
 // rj_expr.hpp) over every row of [0, n_rows); every X_OUT op names the dense arrays it writes.  `grid`
 // workgroups stride over the tiles of MAP_TILE rows.
 struct MapProg;
 void launch_map(const Launch& L, const MapProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t grid);
 
+// ========================================================================================================= rj_sort.hip
 // ---- sort (RJ_NODE_SORT): a stable LSD radix sort of {key, row id}, SORT_RADIX bins per pass, tiles of
 // SORT_TILE rows (rj_device.hpp).  n_tiles = ceil(n_rows / SORT_TILE) everywhere.
 // One key column read through `perm` (row i of the current order = row perm[i]; nullptr = i) -> keys_out
@@ -205,6 +253,7 @@ void launch_sort_scatter(const Launch& L, int mode, const uint8_t* keys_in, cons
 // out[i] = base + i, i < n
 void launch_sort_iota(const Launch& L, uint32_t* out, uint32_t base, uint32_t n);
 
+// ======================================================================================================== rj_group.hip
 // ---- grouping (RJ_NODE_GROUP): runs of equal keys in the order the sort left, tiles of GROUP_TILE
 // positions (rj_device.hpp).  perm: row i of that order = row perm[i] (nullptr = i); masks: one 64-bit
 // head mask per 64 positions (ceil(n_rows / 64)); n_tiles = ceil(n_rows / GROUP_TILE) everywhere.
@@ -230,6 +279,7 @@ void launch_group_reduce(const Launch& L, const ColRef* col, const uint32_t* per
 void launch_group_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int decode, int width,
                          uint8_t* dst, uint8_t* dst_valid);
 
+// ========================================================================================================= rj_fsum.hip
 // ---- RJ_AGG_FSUM (rj_fsum.hip): out[g] = the bits of the exactly rounded sum of the non-NULL values of
 // the FP64 column `col` in group g (+0.0 where there is none: k_group_reduce's count says which are
 // NULL), every entry written whatever the memory held.  perm, masks, tile_base, max_grid and the scalar
@@ -239,6 +289,7 @@ uint64_t fsum_scratch_bytes(uint32_t n_rows, uint32_t max_grid);
 void     launch_fsum(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, const unsigned long long* masks,
                      const uint32_t* tile_base, uint32_t n_groups, unsigned long long* out, uint32_t max_grid, uint8_t* scratch);
 
+// ======================================================================================================= rj_window.hip
 // ---- window functions (RJ_NODE_WINDOW): P / Q = the head masks of the partitions / the peer groups in
 // the grouping's layout, over the order the sort left; one entry per quarter of a tile in WinMarks / WinTails
 // (ceil(n_rows / WIN_QUARTER)); max_chunk: cap on the entries a carry kernel's workgroup takes per step
@@ -257,6 +308,7 @@ void launch_win_scan(const Launch& L, const ColRef& col, const uint32_t* perm, u
 void launch_win_column(const Launch& L, const unsigned long long* src, const uint32_t* nn, const uint32_t* peer_end, uint64_t n, int decode,
                        int width, uint8_t* dst, uint8_t* dst_valid);
 
+// ======================================================================================================== rj_setop.hip
 // ---- set operations (RJ_NODE_SETOP, rj_setop.hip): both children's rows in one relation of n_rows rows
 // (row id < n_left: a left row), ordered and cut into runs by the sort's and the grouping's kernels
 // (perm, masks, tile_base as above).  max_grid: cap on the workgroups of the kernels that walk tiles.
@@ -276,24 +328,7 @@ void launch_setop_offsets(const Launch& L, const SetopRuns& runs, uint32_t n_run
 // run_of[j] = the run output row j is a copy of, j < n_out = off[n_runs]
 void launch_setop_emit(const Launch& L, const uint32_t* off, uint32_t n_runs, uint32_t n_out, uint32_t* run_of, uint32_t max_grid);
 
-// ---- materialise (replaces the per-row output copy, reference src/execute.cpp:236-242,
-//      and Table::to_columnar, src/build_table.cpp:456-594)
-void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,
-                   const OutStream& dst, uint8_t* dst_valid);
-// test hook: keeps the stream busy for `ms` milliseconds (bounded; see RJ_DEBUG_SHARD_FAIL)
-void launch_debug_stall(const Launch& L, uint32_t ms);
-// wide carries (several payload columns travelling with the key): validity bits of up to three
-// columns as one word per row; the emitted records -> one dense array (+ validity bytes) per column
-void launch_pack_validity(const Launch& L, const uint8_t* v0, const uint8_t* v1, const uint8_t* v2, uint32_t n,
-                          uint32_t* out);
-void launch_split_records(const Launch& L, const SplitParams& sp, uint64_t n);
-void launch_finish_pages(const Launch& L, uint8_t* pages, uint64_t n_rows, int width);
-// headers + bitmaps of up to three probe-written streams, row count read on the device
-void launch_finish_streams(const Launch& L, uint8_t* const* pages, const int* widths, uint32_t n,
-                           const unsigned long long* n_rows_dev, uint64_t cap_rows);
-void launch_encode_nullable(const Launch& L, const uint8_t* values, const uint8_t* valid,
-                            uint64_t n_rows, int width, uint8_t* pages);
-
+// ================================================================================================== rj_varchar_dev.hip
 // ---- VARCHAR gather + page encode on the device (replaces, for large results, the string half
 //      of Table::to_columnar, reference src/build_table.cpp:595-677)
 void launch_vc_resolve(const Launch& L, const uint8_t* pages, uint32_t n_pages, const uint32_t* row_base,
@@ -310,14 +345,23 @@ void launch_vc_compact(const Launch& L, const uint8_t* keep, const uint32_t* bid
                        uint32_t* out_b, uint32_t* out_p, unsigned long long* cursor);
 // page_out == nullptr: pages_in_chunk[c] = pages of chunk c; else the pages are written to
 // page_out[page_base[c] ...]
-void prewarm_varchar_dev(const Launch& L, uint32_t* zeroed);  // (RJ_CTX_PREWARM: loads the code object)
-void prewarm_kernels(const Launch& L, uint32_t* zeroed);      // (... rj_kernels.hip's, rj_join.hip's, rj_outer.hip's and
-void prewarm_join(const Launch& L, uint32_t* zeroed);         //  rj_full.hip's: one launch each whose threads leave at
-void prewarm_outer(const Launch& L, uint32_t* zeroed);        //  the kernel's first bounds check)
-void prewarm_full(const Launch& L, uint32_t* zeroed);
 void launch_vc_walk(const Launch& L, const VcRow* rows, uint32_t n, uint32_t* pages_in_chunk,
                     const uint32_t* page_base, VcPage* page_out);
 void launch_vc_encode(const Launch& L, const uint8_t* pages, uint32_t n_pages, const VcRow* rows,
                       const VcPage* plist, uint32_t n_out_pages, uint8_t* out);
+
+// ---- RJ_CTX_PREWARM: one launch per kernel file of the join path and of rj_varchar_dev.hip, whose threads leave at
+// the kernel's first bounds check: HIP loads a file's code object on the first use of one of its kernels.  One
+// signature for all (Context::prewarm walks an array of them); zeroed: 256 zero bytes on the device.
+void prewarm_pages(const Launch& L, uint32_t* zeroed);
+void prewarm_partition(const Launch& L, uint32_t* zeroed);
+void prewarm_join(const Launch& L, uint32_t* zeroed);
+void prewarm_bcast(const Launch& L, uint32_t* zeroed);
+void prewarm_filter(const Launch& L, uint32_t* zeroed);
+void prewarm_outer(const Launch& L, uint32_t* zeroed);
+void prewarm_full(const Launch& L, uint32_t* zeroed);
+void prewarm_agg(const Launch& L, uint32_t* zeroed);
+void prewarm_select(const Launch& L, uint32_t* zeroed);
+void prewarm_varchar_dev(const Launch& L, uint32_t* zeroed);
 
 }  // namespace rj

@@ -1,20 +1,6 @@
-// rj_kernels.hip — hand-written gfx950 (CDNA4, wave64) kernels of the radix join.
-//
-// Everything here is integer / indexing work bound by HBM bandwidth (no MFMA):
-//   K0  page headers        4 B read per 8 KiB page
-//   K1  page decode         irregular (NULL-bearing) pages -> dense values + validity
-//   K2  pass histogram      per-workgroup LDS histogram, flushed once per tile group
-//   K3  bin scan            one workgroup per input segment, wave-shuffle scan
-//   K4  pass scatter        tile of 16384 tuples sorted by digit in LDS (LDS atomics give the
-//                           rank), runs written out contiguously = software write-combining
-//   K5/6 build + probe      per-partition bucketised hash table in LDS (one 16-byte read per
-//                           probe), ballot/mbcnt output offsets, one global reservation per
-//                           4096 probe tuples, streams written straight into Page images
-//                           (partitioned: rj_join.hip; the broadcast form is here)
-//   K7  gather              row-id -> column value (generic late materialisation)
-//   K8  page finish/encode  Page headers + validity bitmaps of the result
-//
-// Reference counterparts are cited at each kernel (paths relative to the reference).
+// rj_partition.hip — gfx950 (wave64) kernels of the radix partition: K3 the bin scans, the tuple loaders, K2 the pass
+// histograms, K4 the pass scatters, and the heavy task list.  Every node kind that partitions its input uses them:
+// the five join node kinds (INNER, SEMI, ANTI, OUTER, FULL) and RJ_NODE_AGG.
 #include <hip/hip_ext.h>
 
 #include "rj_kernels.hpp"
@@ -25,134 +11,6 @@
 #include <type_traits>
 
 namespace rj {
-
-// ================================================================= K0 headers
-// One wave per page: reads `u16 n_rows @0` and the validity bitmap in the last
-// (n_rows+7)/8 bytes (layout: reference src/build_table.cpp:326-331).  A column is
-// "regular" when every page but the last holds exactly rows_full rows and every bitmap bit
-// of every page is set; regular columns are addressed in place by every later kernel, the
-// others go through K1 once.  The reference decodes fixed-width pages from the bitmap alone
-// and never reads the header's non-null count (:332-343), so neither does this.
-__global__ __launch_bounds__(256) void k_page_headers(const uint8_t* pages, uint32_t n_pages,
-                                                      uint32_t rows_full, uint32_t* page_rows,
-                                                      unsigned long long* flags) {
-    // every workgroup walks a strip of pages (one wave per page at a time) and adds its two
-    // sums with ONE pair of global atomics: a million pages must not queue on two words
-    __shared__ unsigned long long s_irr[4], s_rows[4];
-    const uint32_t     lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    unsigned long long irr = 0, rows = 0;
-    for (uint32_t p = blockIdx.x * 4u + wid; p < n_pages; p += gridDim.x * 4u) {
-        const uint8_t* page = pages + (size_t)p * PAGE_BYTES;
-        const uint32_t nr = *reinterpret_cast<const uint16_t*>(page);
-        const uint32_t nb = (nr + 7) / 8;
-        const uint8_t* bm = page + PAGE_BYTES - nb;
-        bool           ones = true;
-        // full pages: 248 bitmap bytes at a dword boundary (INT32) or 126 at a halfword boundary
-        // (INT64/FP64) — one load per lane; anything else byte by byte
-        const uint32_t boff = PAGE_BYTES - nb;
-        if ((nr & 31u) == 0 && (boff & 3u) == 0) {
-            for (uint32_t k = lane; k < nb / 4; k += 64)
-                ones = ones && reinterpret_cast<const uint32_t*>(bm)[k] == 0xffffffffu;
-        } else if ((boff & 1u) == 0 && (nb & 1u) == 0) {
-            for (uint32_t k = lane; k < nb / 2; k += 64) {
-                const uint32_t rem = nr - k * 16u;
-                const uint32_t want = rem >= 16 ? 0xffffu : ((1u << rem) - 1u);
-                ones = ones && ((uint32_t)reinterpret_cast<const uint16_t*>(bm)[k] & want) == want;
-            }
-        } else {
-            for (uint32_t k = lane; k < nb; k += 64) {
-                const uint32_t rem = nr - k * 8u;
-                const uint32_t want = rem >= 8 ? 0xffu : ((1u << rem) - 1u);
-                ones = ones && ((bm[k] & want) == want);
-            }
-        }
-        const bool all_ones = __ballot(!ones) == 0;
-        if (lane == 0) {
-            page_rows[p] = nr;
-            irr += !all_ones || (p + 1 < n_pages ? nr != rows_full : (nr > rows_full || nr == 0));
-            rows += nr;
-        }
-    }
-    if (lane == 0) {
-        s_irr[wid] = irr;
-        s_rows[wid] = rows;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long i = s_irr[0] + s_irr[1] + s_irr[2] + s_irr[3];
-        const unsigned long long r = s_rows[0] + s_rows[1] + s_rows[2] + s_rows[3];
-        if (i) atomicAdd(&flags[0], i);
-        if (r) atomicAdd(&flags[1], r);
-    }
-}
-
-// "row_idx" rule of Table::from_columnar (reference src/build_table.cpp:334-336): the
-// reference throws only when a NON-NULL value lands at a row index >= num_rows; NULL rows
-// past the end are tolerated.  One wave per page; flag[0] counts offending pages.
-__global__ __launch_bounds__(256) void k_rows_beyond(const uint8_t* pages, uint32_t n_pages,
-                                                     const uint32_t* row_base, uint64_t num_rows,
-                                                     unsigned long long* flag) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t p = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (p >= n_pages) return;
-    const uint8_t* page = pages + (size_t)p * PAGE_BYTES;
-    const uint32_t nr = *reinterpret_cast<const uint16_t*>(page);
-    const uint64_t rb = row_base[p];
-    if (rb + nr <= num_rows) return;
-    const uint8_t* bm = page + PAGE_BYTES - (nr + 7) / 8;
-    bool           bad = false;
-    for (uint32_t i = lane; i < nr; i += 64)
-        if (rb + i >= num_rows && ((bm[i >> 3] >> (i & 7u)) & 1u)) bad = true;
-    if (__ballot(bad) != 0 && lane == 0) atomicAdd(flag, 1ull);
-}
-
-// ================================================================== K1 decode
-// One workgroup per page: rows -> dense values + validity bytes.  The value
-// index of row i is the number of set validity bits below i (values are stored
-// densely, the bitmap sits in the last (n_rows+7)/8 bytes: reference
-// src/build_table.cpp:325-381).  Per 64 rows one ballot + mbcnt.
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_decode_pages(const uint8_t* pages, const uint32_t* row_base,
-                                                      uint64_t num_rows, uint8_t* values,
-                                                      uint8_t* valid) {
-    __shared__ uint32_t s_w[4];
-    const uint8_t*      page = pages + (size_t)blockIdx.x * PAGE_BYTES;
-    const uint32_t      nr = *reinterpret_cast<const uint16_t*>(page);
-    const uint32_t      rb = row_base[blockIdx.x];
-    const uint8_t*      bitmap = page + PAGE_BYTES - (nr + 7) / 8;
-    const uint8_t*      vals = page + (WIDTH == 4 ? HDR32 : HDR64);
-    const uint32_t      lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t            running = 0;
-    for (uint32_t base = 0; base < nr; base += 256) {
-        uint32_t i = base + threadIdx.x;
-        bool     bit = i < nr ? ((bitmap[i >> 3] >> (i & 7u)) & 1u) : false;
-        uint64_t mask = __ballot(bit);
-        uint32_t pre = lane_prefix(mask);
-        if (lane == 0) s_w[wid] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        uint32_t wpre = 0, tot = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {
-            uint32_t c = s_w[k];
-            if (k < wid) wpre += c;
-            tot += c;
-        }
-        uint64_t row = (uint64_t)rb + i;
-        if (i < nr && row < num_rows) {
-            valid[row] = bit ? 1 : 0;
-            uint32_t vi = running + wpre + pre;
-            if (WIDTH == 4) {
-                reinterpret_cast<uint32_t*>(values)[row] =
-                    bit ? reinterpret_cast<const uint32_t*>(vals)[vi] : 0u;
-            } else {
-                reinterpret_cast<uint64_t*>(values)[row] =
-                    bit ? reinterpret_cast<const uint64_t*>(vals)[vi] : 0ull;
-            }
-        }
-        running += tot;
-        __syncthreads();
-    }
-}
 
 // ==================================================================== K3 scan
 // Single workgroup of 1024 threads; thread t owns a contiguous chunk.
@@ -1371,1144 +1229,7 @@ __global__ void k_heavy_tasks(const uint32_t* offR, const uint32_t* offS, uint32
     }
 }
 
-// ============================================================ broadcast join
-// A build side of at most JN_RMAX rows (the filtered dimension tables of the JOB plans: a
-// handful of rows against millions) needs no partitioning: every workgroup builds the SAME
-// LDS table straight from the build child's columns and streams a slice of the probe
-// child's columns past it — page decode, NULL-key drop and hashing happen on the way, the
-// probe side is read exactly once and nothing is scattered.  (The reference counterpart is
-// still hash_join_omp, src/execute.cpp:44-262, with num_buckets = 1.)
-// The table keeps key words + the build ROW; build carries are fetched from the build
-// columns on emit (a few KB: cache resident).  With no radix digit to derive an EMPTY
-// sentinel from, a slot is valid when its index is below its bucket's insert counter.
-template <int KW, int CWR, int CWS>
-__global__ __launch_bounds__(JN_THREADS) void k_join_bcast(BcastParams bp) {
-    constexpr int RW = KW + 1;  // key words + build row
-    __shared__ __attribute__((aligned(16))) uint32_t t_w[RW][JN_CAP];
-    __shared__ __attribute__((aligned(16))) uint32_t t_cnt[JN_CAP / 4];
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const uint32_t     lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    constexpr uint32_t BMASK = JN_CAP / 4 - 1;
-
-    // ---- build (identical in every workgroup)
-    for (uint32_t i = threadIdx.x; i < JN_CAP / 4; i += JN_THREADS) t_cnt[i] = 0;
-    lds_barrier();
-    for (uint32_t r = threadIdx.x; r < bp.R.n_rows; r += JN_THREADS) {
-        uint32_t lo, hi;
-        if (!src_key<KW>(bp.R, r, lo, hi)) continue;
-        uint32_t b = lo & BMASK;
-        while (true) {
-            uint32_t pos = atomicAdd(&t_cnt[b], 1u);
-            if (pos < 4) {
-                const uint32_t slot = b * 4 + pos;
-                t_w[0][slot] = lo;
-                if constexpr (KW == 2) t_w[1][slot] = hi;
-                t_w[KW][slot] = r;
-                break;
-            }
-            b = (b + 1) & BMASK;
-        }
-    }
-    lds_barrier();
-
-    // matches of one probe key in bucket b: bit mask over its (valid) slots; `more` = the
-    // bucket overflowed, the walk goes on in the next one
-    auto match = [&](uint32_t b, uint32_t lo, uint32_t hi, bool& more) -> uint32_t {
-        const uint32_t cnt = t_cnt[b];
-        const uint4    kv = *reinterpret_cast<const uint4*>(&t_w[0][b * 4]);
-        uint32_t       eq = (uint32_t)(kv.x == lo) | ((uint32_t)(kv.y == lo) << 1) |
-                      ((uint32_t)(kv.z == lo) << 2) | ((uint32_t)(kv.w == lo) << 3);
-        if constexpr (KW == 2) {
-            const uint4 hv = *reinterpret_cast<const uint4*>(&t_w[1][b * 4]);
-            eq &= (uint32_t)(hv.x == hi) | ((uint32_t)(hv.y == hi) << 1) |
-                  ((uint32_t)(hv.z == hi) << 2) | ((uint32_t)(hv.w == hi) << 3);
-        }
-        more = cnt > 4;
-        return eq & ((1u << min(cnt, 4u)) - 1u);
-    };
-
-    // ---- probe: chunks of JN_SUB rows, strided over the grid
-    const uint32_t n = bp.S.n_rows;
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t klo[JN_SPT], khi[JN_SPT], m[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            m[j] = 0;
-            klo[j] = khi[j] = 0;
-            if (row < n && src_key<KW>(bp.S, (uint32_t)row, klo[j], khi[j])) {
-                uint32_t b = klo[j] & BMASK;
-                bool     more;
-                do {
-                    m[j] += (uint32_t)__popc(match(b, klo[j], khi[j], more));
-                    b = (b + 1) & BMASK;
-                } while (more);
-            }
-        }
-        // output offsets: wave prefix (ballot when every lane has <= 1 match), one global
-        // reservation per chunk
-        uint32_t pre[JN_SPT], wave_total = 0;
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            uint32_t tot;
-            if (__ballot(m[j] > 1) == 0) {
-                uint64_t mk = __ballot(m[j] == 1);
-                pre[j] = lane_prefix(mk);
-                tot = (uint32_t)__popcll(mk);
-            } else {
-                uint32_t incl = m[j];
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    uint32_t t = __shfl_up(incl, off);
-                    if (lane >= (uint32_t)off) incl += t;
-                }
-                pre[j] = incl - m[j];
-                tot = __shfl(incl, 63);
-            }
-            pre[j] += wave_total;
-            wave_total += tot;
-        }
-        if (lane == 0) s_wtot[wid] = wave_total;
-        lds_barrier();
-        if (threadIdx.x == 0) {
-            uint32_t tot = 0;
-            for (int w = 0; w < JN_THREADS / 64; ++w) tot += s_wtot[w];
-            s_obase = tot ? atomicAdd(bp.out_cursor, (unsigned long long)tot) : 0ull;
-        }
-        lds_barrier();
-        const uint64_t gbase = s_obase;
-        uint64_t       obase = gbase;
-        uint32_t       block_total = 0;
-        for (uint32_t w = 0; w < JN_THREADS / 64; ++w) {
-            uint32_t t = s_wtot[w];
-            if (w < wid) obase += t;
-            block_total += t;
-        }
-        // rows beyond the stream capacity are counted but not written (the host re-runs the
-        // join with exact-size buffers)
-        if (gbase + block_total <= bp.out_cap) {
-#pragma unroll
-            for (int j = 0; j < JN_SPT; ++j) {
-                if (m[j] == 0) continue;
-                const uint32_t srow = (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x);
-                uint64_t       row = obase + pre[j];
-                uint32_t       k0, k1 = 0;
-                unhash_key<KW>(klo[j], khi[j], k0, k1);
-                uint32_t p0, p1, p2;
-                src_carry<CWS>(bp.S, srow, p0, p1, p2);
-                uint32_t b = klo[j] & BMASK;
-                bool     more;
-                do {
-                    uint32_t eq = match(b, klo[j], khi[j], more);
-                    while (eq) {
-                        const uint32_t slot = b * 4 + (uint32_t)__builtin_ctz(eq);
-                        eq &= eq - 1;
-                        uint32_t b0, b1, b2;
-                        src_carry<CWR>(bp.R, t_w[KW][slot], b0, b1, b2);
-                        stream_store(bp.key, row, k0, k1);
-                        if constexpr (CWR >= 1) stream_store(bp.bc, row, b0, b1, b2);
-                        if constexpr (CWS >= 1) stream_store(bp.pc, row, p0, p1, p2);
-                        ++row;
-                    }
-                    b = (b + 1) & BMASK;
-                } while (more);
-            }
-        }
-        lds_barrier();  // s_wtot / s_obase are reused by the next chunk
-    }
-}
-
-// ====================================================== semi / anti joins
-// RJ_NODE_SEMI / RJ_NODE_ANTI ask "has this preserved row a partner on the filter side?".  The
-// filter side's DISTINCT hashed keys go into an LDS set; the preserved tuples are looked up and
-// each one that hits (SEMI) or misses (ANTI) is emitted ONCE — the un-hashed key and its carry,
-// ballot/mbcnt offsets inside the wave, one global reservation per JN_SUB tuples (as k_join_bcast).
-// Nothing travels with a filter key, so a slot is the hashed key alone: 32 KiB (KW = 1) or 64 KiB
-// (KW = 2) for JN_CAP slots, of which at most JN_RMAX are used (load <= 50 %).
-//   insert  open addressing, linear probing, one LDS compare-and-swap per step: a key that is
-//           already there is not stored again (duplicates collapse on insert);
-//   lookup  walk from the home slot until the key or an EMPTY slot.
-// EMPTY is the all-ones word; a filter key whose hash is all ones sets a flag instead of a slot.
-// The home slot is the multiplicative hash of the key words: their low radix bits are the same for
-// a whole partition, the product's high bits are not.
-static_assert((JN_CAP & (JN_CAP - 1)) == 0, "set slots: a power of two");
-
-template <int KW>
-struct FilterSet {
-    using Slot = std::conditional_t<KW == 1, uint32_t, unsigned long long>;
-    static constexpr Slot     EMPTY = ~Slot(0);
-    static constexpr uint32_t LOG2 = ilog2_u32(JN_CAP), MASK = JN_CAP - 1;
-    Slot*     t;         // [JN_CAP]
-    uint32_t* count;     // distinct keys in the slots
-    uint32_t* sentinel;  // 1: the EMPTY key itself is in the set
-
-    __device__ __forceinline__ static Slot make(uint32_t lo, uint32_t hi) {
-        if constexpr (KW == 1)
-            return lo;
-        else
-            return (Slot)lo | ((Slot)hi << 32);
-    }
-    __device__ __forceinline__ static uint32_t home(uint32_t lo, uint32_t hi) {
-        return ((lo ^ hi) * 0x9e3779b1u) >> (32 - LOG2);
-    }
-    // every thread of the workgroup; the caller puts a barrier behind it
-    __device__ __forceinline__ void clear() const {
-        uint4* t4 = reinterpret_cast<uint4*>(t);
-        for (uint32_t i = threadIdx.x; i < JN_CAP * sizeof(Slot) / 16; i += blockDim.x)
-            t4[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
-        if (threadIdx.x == 0) {
-            *count = 0;
-            *sentinel = 0;
-        }
-    }
-    // true: the key was not in the set before
-    __device__ __forceinline__ bool insert(uint32_t lo, uint32_t hi) const {
-        const Slot k = make(lo, hi);
-        if (k == EMPTY) {
-            *sentinel = 1u;
-            return false;
-        }
-        uint32_t s = home(lo, hi);
-        while (true) {
-            const Slot prev = atomicCAS(&t[s], EMPTY, k);
-            if (prev == EMPTY) return true;
-            if (prev == k) return false;
-            s = (s + 1) & MASK;
-        }
-    }
-    __device__ __forceinline__ bool has(uint32_t lo, uint32_t hi) const {
-        const Slot k = make(lo, hi);
-        if (k == EMPTY) return *sentinel != 0;
-        uint32_t s = home(lo, hi);
-        while (true) {
-            const Slot v = t[s];
-            if (v == k) return true;
-            if (v == EMPTY) return false;
-            s = (s + 1) & MASK;
-        }
-    }
-};
-
-// Emit the items with e[j] set: offsets from the wave ballots, ONE global reservation for the
-// workgroup, then the un-hashed key (key stream) and carry(j, p0, p1, p2) (preserved carry stream).
-// Contains barriers: every thread of the workgroup calls it.
-template <int KW, int SPT, class Carry>
-__device__ __forceinline__ void filter_emit(const FilterParams& fp, const bool (&e)[SPT], const uint32_t (&klo)[SPT],
-                                            const uint32_t (&khi)[SPT], uint32_t* s_wtot,
-                                            unsigned long long* s_obase, Carry carry) {
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t       pre[SPT], wave_total = 0;
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-        const uint64_t mk = __ballot(e[j]);
-        pre[j] = wave_total + lane_prefix(mk);
-        wave_total += (uint32_t)__popcll(mk);
-    }
-    if (lane == 0) s_wtot[wid] = wave_total;
-    lds_barrier();
-    if (threadIdx.x == 0) {
-        uint32_t tot = 0;
-        for (uint32_t w = 0; w < nw; ++w) tot += s_wtot[w];
-        *s_obase = tot ? atomicAdd(fp.out_cursor, (unsigned long long)tot) : 0ull;
-    }
-    lds_barrier();
-    uint64_t obase = *s_obase;
-    for (uint32_t w = 0; w < wid; ++w) obase += s_wtot[w];
-#pragma unroll
-    for (int j = 0; j < SPT; ++j) {
-        const uint64_t row = obase + pre[j];
-        // (the output never holds more rows than the preserved side: the bound is a guard only)
-        if (!e[j] || row >= fp.out_cap) continue;
-        if (fp.key.mode != ST_NONE) {
-            uint32_t k0, k1 = 0;
-            unhash_key<KW>(klo[j], khi[j], k0, k1);
-            stream_store(fp.key, row, k0, k1);
-        }
-        if (fp.pc.mode != ST_NONE) {
-            uint32_t p0, p1, p2;
-            carry(j, p0, p1, p2);
-            stream_store(fp.pc, row, p0, p1, p2);
-        }
-    }
-    lds_barrier();  // s_wtot / s_obase are reused by the next chunk
-}
-
-// Broadcast form: a filter side of at most JN_RMAX rows.  Every workgroup builds the SAME set
-// straight from the filter child's key column (page decode, NULL / NaN drop, hashing on the way)
-// and streams a grid-strided slice of the preserved child past it.  A preserved row whose key is
-// NULL or NaN has no partner: ANTI emits it.  keyless (the key types differ): no key is read,
-// every row misses.
-template <int KW, int CWS>
-__global__ __launch_bounds__(JN_THREADS) void k_filter_bcast(FilterParams fp) {
-    using Set = FilterSet<KW>;
-    __shared__ __attribute__((aligned(16))) typename Set::Slot t_set[JN_CAP];
-    __shared__ uint32_t s_cnt[2];
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const Set set{t_set, &s_cnt[0], &s_cnt[1]};
-    set.clear();
-    lds_barrier();
-    if (!fp.keyless) {
-        for (uint32_t r = threadIdx.x; r < fp.F.n_rows; r += JN_THREADS) {
-            uint32_t lo, hi;
-            if (src_key<KW>(fp.F, r, lo, hi)) (void)set.insert(lo, hi);
-        }
-    }
-    lds_barrier();
-    const uint32_t n = fp.P.n_rows;
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t klo[JN_SPT], khi[JN_SPT];
-        bool     e[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            klo[j] = khi[j] = 0;
-            e[j] = false;
-            if (row < n) {
-                bool hit = false;
-                if (!fp.keyless && src_key<KW>(fp.P, (uint32_t)row, klo[j], khi[j])) hit = set.has(klo[j], khi[j]);
-                e[j] = fp.anti ? !hit : hit;
-            }
-        }
-        filter_emit<KW, JN_SPT>(fp, e, klo, khi, s_wtot, &s_obase, [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-            src_carry<CWS>(fp.P, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), p0, p1, p2);
-        });
-    }
-}
-
-// ANTI on the partitioned path: the preserved rows the first radix pass drops (NULL key; FP64 NaN
-// key) have no partner, so they belong to the result.  Grid-strided over the preserved child, the
-// same tuple formation (src_key / src_carry over the TupleSrc) and output cursor as the filter.
-template <int KW, int CWS>
-__global__ __launch_bounds__(JN_THREADS) void k_filter_nullkeys(FilterParams fp) {
-    __shared__ uint32_t s_wtot[JN_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const uint32_t n = fp.P.n_rows;
-    for (uint64_t base = (uint64_t)blockIdx.x * JN_SUB; base < n; base += (uint64_t)gridDim.x * JN_SUB) {
-        uint32_t klo[JN_SPT], khi[JN_SPT];
-        bool     e[JN_SPT];
-#pragma unroll
-        for (int j = 0; j < JN_SPT; ++j) {
-            const uint64_t row = base + (uint64_t)j * JN_THREADS + threadIdx.x;
-            klo[j] = khi[j] = 0;
-            e[j] = row < n && !src_key<KW>(fp.P, (uint32_t)row, klo[j], khi[j]);
-        }
-        filter_emit<KW, JN_SPT>(fp, e, klo, khi, s_wtot, &s_obase, [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-            src_carry<CWS>(fp.P, (uint32_t)(base + (uint64_t)j * JN_THREADS + threadIdx.x), p0, p1, p2);
-        });
-    }
-}
-
-// Partitioned form: one workgroup per co-partition, or per heavy task of a preserved partition
-// above JN_HEAVY tuples (k_heavy_tasks; it leaves partitions WITHOUT filter tuples to the main
-// workgroups, which is where ANTI emits them whole).  The set is built from the partition's filter
-// keys in blocks of JN_RMAX / 2 tuples for as long as it holds at most JN_RMAX / 2 distinct keys,
-// so a round ends with at most JN_RMAX of them.  A partition that needs more than one round (more
-// distinct filter keys than one set holds: a forced radix_bits, or adversarial hashes) is exact
-// all the same: every JN_SUB-tuple chunk of preserved tuples stays in registers while the rounds
-// are rebuilt one after the other, its per-tuple hit flags OR-ed over them, and is emitted after
-// the last one.  No memory outside the LDS holds a flag.
-template <int KW, int CWS>
-__global__ __launch_bounds__(JN_THREADS) void k_filter_join(FilterParams fp) {
-    using Set = FilterSet<KW>;
-    constexpr int      TH = JN_THREADS, SPT = JN_SPT, SUB = JN_SUB, SW = KW + CWS;
-    constexpr uint32_t RB = JN_RMAX / 2;  // filter tuples per insert block
-    static_assert(SPT * TH == SUB, "sub-chunk geometry");
-    __shared__ __attribute__((aligned(16))) typename Set::Slot t_set[JN_CAP];
-    __shared__ uint32_t s_cnt[2];
-    __shared__ uint32_t s_wtot[TH / 64];
-    __shared__ unsigned long long s_obase;
-    const Set set{t_set, &s_cnt[0], &s_cnt[1]};
-
-    uint32_t q, sbeg, send;
-    if (blockIdx.x < fp.heavy_grid) {
-        if (blockIdx.x >= *fp.n_heavy) return;
-        q = fp.heavy_tasks[3 * blockIdx.x + 0];
-        sbeg = fp.heavy_tasks[3 * blockIdx.x + 1];
-        send = fp.heavy_tasks[3 * blockIdx.x + 2];
-    } else {
-        q = blockIdx.x - fp.heavy_grid;
-        if (q >= fp.NP) return;
-        sbeg = fp.offP[q];
-        send = fp.offP[q + 1];
-        if (send - sbeg > JN_HEAVY && fp.offF[q + 1] != fp.offF[q]) return;  // split into heavy tasks
-    }
-    const uint32_t rbeg = fp.offF[q], rend = fp.offF[q + 1];
-    if (sbeg >= send || (!fp.anti && rbeg == rend)) return;
-
-    // one round of the set: filter tuples from `from` on; returns where the round ended
-    auto build_round = [&](uint32_t from) -> uint32_t {
-        lds_barrier();  // nobody still looks up the previous round
-        set.clear();
-        lds_barrier();
-        uint32_t cur = from;
-        while (cur < rend) {
-            const uint32_t nb = min(RB, rend - cur);
-            uint32_t       added = 0;
-            for (uint32_t i = threadIdx.x; i < nb; i += TH) {
-                const uint32_t lo = fp.Fw.w[0][cur + i], hi = KW == 2 ? fp.Fw.w[KW - 1][cur + i] : 0u;
-                added += set.insert(lo, hi) ? 1u : 0u;
-            }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) added += __shfl_xor(added, off);
-            if ((threadIdx.x & 63u) == 0 && added) atomicAdd(set.count, added);
-            lds_barrier();
-            cur += nb;
-            const uint32_t distinct = *set.count;
-            lds_barrier();  // every thread has read the count before the next block adds to it
-            if (distinct > (uint32_t)JN_RMAX - RB) break;
-        }
-        return cur;
-    };
-
-    uint32_t sw[SPT][SW];
-    auto load_chunk = [&](uint32_t sc, uint32_t sn) {
-#pragma unroll
-        for (int j = 0; j < SPT; ++j) {
-            // (items past the chunk re-read its last tuple; they are masked off)
-            const uint32_t idx = sc + min((uint32_t)(j * TH + threadIdx.x), sn - 1u);
-            part_tuple<KW, CWS>(fp.Pw, fp.packP, fp.aosP, idx, sw[j]);
-        }
-    };
-
-    const uint32_t first_end = build_round(rbeg);
-    const bool     one_round = first_end == rend;
-    for (uint32_t sc = sbeg; sc < send; sc += SUB) {
-        const uint32_t sn = min((uint32_t)SUB, send - sc);
-        load_chunk(sc, sn);
-        bool hit[SPT];
-#pragma unroll
-        for (int j = 0; j < SPT; ++j) hit[j] = false;
-        uint32_t end = (one_round || sc == sbeg) ? first_end : build_round(rbeg);
-        while (true) {
-#pragma unroll
-            for (int j = 0; j < SPT; ++j)
-                if ((uint32_t)(j * TH + threadIdx.x) < sn && !hit[j]) hit[j] = set.has(sw[j][0], KW == 2 ? sw[j][KW - 1] : 0u);
-            if (end == rend) break;
-            end = build_round(end);
-        }
-        uint32_t klo[SPT], khi[SPT];
-        bool     e[SPT];
-#pragma unroll
-        for (int j = 0; j < SPT; ++j) {
-            klo[j] = sw[j][0];
-            khi[j] = KW == 2 ? sw[j][KW - 1] : 0u;
-            e[j] = (uint32_t)(j * TH + threadIdx.x) < sn && (fp.anti ? !hit[j] : hit[j]);
-        }
-        filter_emit<KW, SPT>(fp, e, klo, khi, s_wtot, &s_obase, [&](int j, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-            tuple_carry<KW, CWS>(sw[j], p0, p1, p2);
-        });
-    }
-}
-
-// k_gather for the row-index stream of an outer join's optional side: OUTER_NO_ROW (a padded row)
-// is never dereferenced and gives a NULL; every row gets a validity byte.
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_outer_gather(ColRef src, const uint32_t* idx, uint64_t n, uint8_t* dst,
-                                                      uint8_t* dst_valid) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t r = idx[i];
-    const bool     there = r != OUTER_NO_ROW;
-    if (WIDTH == 4)
-        reinterpret_cast<uint32_t*>(dst)[i] = there ? col_load32(src, r) : 0u;
-    else
-        reinterpret_cast<uint64_t*>(dst)[i] = there ? col_load64(src, r) : 0ull;
-    dst_valid[i] = there ? (src.valid ? src.valid[r] : (uint8_t)1) : (uint8_t)0;
-}
-
-// ================================================================== K7 gather
-// Late materialisation: out[i] = column[idx[i]] (reference counterpart: the
-// per-row `out.push_back(lrow[ci])`, src/execute.cpp:236-242).
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_gather(ColRef src, const uint32_t* idx, uint64_t n,
-                                                OutStream dst, uint8_t* dst_valid) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t r = idx ? idx[i] : (uint32_t)i;
-    if (WIDTH == 4) {
-        stream_store(dst, i, col_load32(src, r), 0u);
-    } else {
-        uint64_t v = col_load64(src, r);
-        stream_store(dst, i, (uint32_t)v, (uint32_t)(v >> 32));
-    }
-    if (dst_valid) dst_valid[i] = src.valid ? src.valid[r] : (uint8_t)1;
-}
-
-// =========================================================== K8 page finishing
-// Headers + all-ones validity bitmaps of result pages whose values were written
-// in place by the probe / gather kernels (page layout: reference
-// src/build_table.cpp:472-481).
-__global__ __launch_bounds__(256) void k_finish_pages(uint8_t* pages, uint64_t n_rows,
-                                                      uint32_t rows_full) {
-    uint8_t*       page = pages + (size_t)blockIdx.x * PAGE_BYTES;
-    const uint64_t first = (uint64_t)blockIdx.x * rows_full;
-    const uint32_t nr = (uint32_t)min((uint64_t)rows_full, n_rows - first);
-    const uint32_t nb = (nr + 7) / 8;
-    if (threadIdx.x == 0) {
-        reinterpret_cast<uint16_t*>(page)[0] = (uint16_t)nr;
-        reinterpret_cast<uint16_t*>(page)[1] = (uint16_t)nr;
-    }
-    uint8_t* bm = page + PAGE_BYTES - nb;
-    for (uint32_t k = threadIdx.x; k < nb; k += blockDim.x) {
-        uint32_t bits = nr - k * 8u;
-        bm[k] = bits >= 8 ? 0xff : (uint8_t)((1u << bits) - 1u);
-    }
-}
-
-// Same, for the (up to three) streams the probe kernel wrote, with the row count still on
-// the device: launched right behind the probe, before the host reads the count back.
-struct FinishStreams {
-    uint8_t* pages[3];
-    uint32_t rows_full[3];
-    uint32_t n;
-};
-__global__ __launch_bounds__(256) void k_finish_streams(FinishStreams fs,
-                                                        const unsigned long long* n_rows_dev,
-                                                        uint64_t cap_rows) {
-    const uint64_t n_rows = *n_rows_dev;
-    if (n_rows > cap_rows) return;  // overflow: the host re-runs the probe with larger buffers
-    // one wave per page: the header and a bitmap of at most 248 bytes
-    const uint32_t b = blockIdx.y, lane = threadIdx.x & 63u;
-    const uint32_t rf = fs.rows_full[b];
-    const uint64_t pg = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const uint64_t first = pg * rf;
-    if (first >= n_rows) return;
-    uint8_t*       page = fs.pages[b] + (size_t)pg * PAGE_BYTES;
-    const uint32_t nr = (uint32_t)min((uint64_t)rf, n_rows - first);
-    const uint32_t nb = (nr + 7) / 8;
-    if (lane == 0) *reinterpret_cast<uint32_t*>(page) = nr | (nr << 16);  // n_rows, n_nonnull
-    uint8_t* bm = page + PAGE_BYTES - nb;
-    if (nr == rf && (nr & 31u) == 0 && ((PAGE_BYTES - nb) & 3u) == 0) {
-        // full INT32 page: 248 bytes of ones, dword aligned
-        for (uint32_t k = lane; k < nb / 4; k += 64) reinterpret_cast<uint32_t*>(bm)[k] = 0xffffffffu;
-        return;
-    }
-    if (nr == rf && rf == ROWS64) {
-        // full INT64 / FP64 page: 1007 bits = 126 bytes from offset 8066 — one halfword, then 31
-        // dwords (the last byte holds 7 bits)
-        static_assert(ROWS64 == 1007 && ((PAGE_BYTES - 126 + 2) & 3u) == 0, "bitmap layout of a full 8-byte page");
-        if (lane == 0) *reinterpret_cast<uint16_t*>(bm) = 0xffffu;
-        if (lane < 31) reinterpret_cast<uint32_t*>(bm + 2)[lane] = lane == 30 ? 0x7fffffffu : 0xffffffffu;
-        return;
-    }
-    for (uint32_t k = lane; k < nb; k += 64) {
-        uint32_t bits = nr - k * 8u;
-        bm[k] = bits >= 8 ? 0xff : (uint8_t)((1u << bits) - 1u);
-    }
-}
-
-// Result pages of a column that carries NULLs: a fixed rows_full rows per page
-// (any fill that satisfies the layout decodes to the same rows), values packed
-// densely in row order, bitmap at the tail.
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_encode_nullable(const uint8_t* values, const uint8_t* valid,
-                                                         uint64_t n_rows, uint8_t* pages) {
-    __shared__ uint32_t s_w[4];
-    constexpr uint32_t  RF = WIDTH == 4 ? ROWS32 : ROWS64;
-    uint8_t*            page = pages + (size_t)blockIdx.x * PAGE_BYTES;
-    const uint64_t      first = (uint64_t)blockIdx.x * RF;
-    const uint32_t      nr = (uint32_t)min((uint64_t)RF, n_rows - first);
-    const uint32_t      nb = (nr + 7) / 8;
-    uint8_t*            out_vals = page + (WIDTH == 4 ? HDR32 : HDR64);
-    uint8_t*            bm = page + PAGE_BYTES - nb;
-    const uint32_t      lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t            running = 0;
-    for (uint32_t base = 0; base < nr; base += 256) {
-        uint32_t i = base + threadIdx.x;
-        bool     bit = i < nr ? valid[first + i] != 0 : false;
-        uint64_t mask = __ballot(bit);
-        uint32_t pre = lane_prefix(mask);
-        if (lane == 0) s_w[wid] = (uint32_t)__popcll(mask);
-        __syncthreads();
-        uint32_t wpre = 0, tot = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {
-            uint32_t c = s_w[k];
-            if (k < wid) wpre += c;
-            tot += c;
-        }
-        if (bit) {
-            uint32_t vi = running + wpre + pre;
-            if (WIDTH == 4)
-                reinterpret_cast<uint32_t*>(out_vals)[vi] =
-                    reinterpret_cast<const uint32_t*>(values)[first + i];
-            else
-                reinterpret_cast<uint64_t*>(out_vals)[vi] =
-                    reinterpret_cast<const uint64_t*>(values)[first + i];
-        }
-        // bitmap bytes of this 256-row slab: the wave's ballot holds 8 of them
-        if (lane < 8) {
-            uint32_t byte_idx = (base >> 3) + wid * 8u + lane;
-            if (byte_idx < nb) bm[byte_idx] = (uint8_t)(mask >> (lane * 8u));
-        }
-        running += tot;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        reinterpret_cast<uint16_t*>(page)[0] = (uint16_t)nr;
-        reinterpret_cast<uint16_t*>(page)[1] = (uint16_t)running;
-    }
-}
-
-// ============================================================ wide carries
-// Validity of up to three carried columns as ONE 32-bit word per row (bit c = column c is
-// non-NULL): the word then travels like a 32-bit column of the wide carry.
-__global__ __launch_bounds__(256) void k_pack_validity(const uint8_t* v0, const uint8_t* v1, const uint8_t* v2,
-                                                       uint32_t n, uint32_t* out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = (uint32_t)(!v0 || v0[i]) | ((uint32_t)(!v1 || v1[i]) << 1) | ((uint32_t)(!v2 || v2[i]) << 2);
-}
-
-// The records a join emitted for a wide carry (cw words per output row) -> one dense array per
-// carried column, plus validity bytes for the columns that have them.  Sequential reads and
-// writes: this replaces k_gather's random reads through a row-index stream.
-__global__ __launch_bounds__(256) void k_split_records(SplitParams sp, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t* r = sp.rec + i * sp.cw;
-    const uint32_t  vw = sp.valid_word >= 0 ? r[sp.valid_word] : 0xffffffffu;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (c >= sp.n_cols) break;
-        const uint32_t lo = r[sp.col[c].word];
-        if (sp.col[c].paged)
-            stream_store(OutStream{sp.col[c].out, sp.col[c].width == 8 ? ST_PAGED64 : ST_PAGED32, 0}, i, lo,
-                         sp.col[c].width == 8 ? r[sp.col[c].word + 1] : 0u);
-        else if (sp.col[c].width == 8)
-            reinterpret_cast<uint64_t*>(sp.col[c].out)[i] = (uint64_t)lo | ((uint64_t)r[sp.col[c].word + 1] << 32);
-        else
-            reinterpret_cast<uint32_t*>(sp.col[c].out)[i] = lo;
-        if (sp.col[c].valid) sp.col[c].valid[i] = (uint8_t)((vw >> sp.col[c].valid_bit) & 1u);
-    }
-}
-
-// Test hook (RJ_DEBUG_SHARD_FAIL=4): holds a stream for `ticks` of the constant-rate wall clock
-// (hipDeviceAttributeWallClockRate) — a rank whose stage A "never finishes", so that its peers'
-// bounded waits can be seen to expire.  Every wave leaves on its own when the time is up.
-__global__ void k_debug_stall(unsigned long long ticks) {
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(127);
-}
-
-// ============================================================ aggregation
-// RJ_NODE_AGG: GROUP BY the key of ONE partitioned relation (rj_device.hpp, AggParams).
-// part_tuple's inverse: a tuple goes back into the partition layout (the tuples k_agg_parts defers).
-template <int KW, int CW>
-__device__ __forceinline__ void part_tuple_store(const Words& W, int pack, int aos, uint32_t idx, const uint32_t (&t)[KW + CW]) {
-    constexpr int NW = KW + CW;
-    if constexpr (KW == 1 && CW == 2) {
-        if (aos) {
-            uint32_t* p = W.w[0] + (size_t)idx * 3u;
-            p[0] = t[0];
-            p[1] = t[1];
-            p[2] = t[2];
-            return;
-        }
-    }
-    if constexpr (KW == 1 && CW == 1) {
-        if (pack) {
-            reinterpret_cast<uint2*>(W.w[0])[idx] = make_uint2(t[0], t[1]);
-            return;
-        }
-    }
-    constexpr int NA = CW >= 2 ? NW - 2 : NW;
-#pragma unroll
-    for (int a = 0; a < NA; ++a) W.w[a][idx] = t[a];
-    if constexpr (CW >= 2) reinterpret_cast<uint2*>(W.w[NA])[idx] = make_uint2(t[NA], t[NA + 1]);
-}
-
-constexpr long long AGG_MIN_INIT = 0x7fffffffffffffffll, AGG_MAX_INIT = -0x7fffffffffffffffll - 1;
-
-// value of carried column `a` in the carry words c0..c2 (selects, no indexed registers); false = NULL
-__device__ __forceinline__ bool agg_value(const AggCol& a, int valid_word, uint32_t c0, uint32_t c1, uint32_t c2, long long& v) {
-    const uint32_t vw = valid_word == 0 ? c0 : (valid_word == 1 ? c1 : c2);
-    if (a.valid_bit >= 0 && !((vw >> a.valid_bit) & 1u)) return false;
-    const uint32_t lo = a.word == 0 ? c0 : (a.word == 1 ? c1 : c2), hi = a.word == 0 ? c1 : c2;
-    v = a.width == 4 ? (long long)(int32_t)lo : (long long)((uint64_t)lo | ((uint64_t)hi << 32));
-    return true;
-}
-
-// The merge table's entry of a hashed key (open addressing over m_slots entries; the key that
-// equals the "nobody's" pattern owns entry m_slots); 0xffffffff and *m_overflow set when the walk
-// finds neither the key nor a free entry within AGG_MERGE_WALK steps.
-constexpr uint32_t AGG_MERGE_WALK = 4096, AGG_NO_ENTRY = 0xffffffffu;
-__device__ __forceinline__ uint32_t agg_merge_entry(const AggParams& ap, unsigned long long k64) {
-    if (k64 == AGG_NO_KEY) return ap.m_slots;
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ap.m.key);
-    const uint32_t      mask = ap.m_slots - 1u;
-    uint32_t            slot = (uint32_t)((k64 * 0x9e3779b97f4a7c15ull) >> 32) & mask;
-    if (ap.m_slots)
-        for (uint32_t pr = 0; pr < AGG_MERGE_WALK && pr < ap.m_slots; ++pr) {
-            unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == AGG_NO_KEY) {
-                cur = atomicCAS(&keys[slot], AGG_NO_KEY, k64);
-                if (cur == AGG_NO_KEY) cur = k64;
-            }
-            if (cur == k64) return slot;
-            slot = (slot + 1u) & mask;
-        }
-    atomicOr(ap.m_overflow, 1u);
-    return AGG_NO_ENTRY;
-}
-// one partial group -> the merge table (ordinary vector atomics in HBM)
-template <int NC>
-__device__ __forceinline__ void agg_merge(const AggParams& ap, uint32_t entry, unsigned long long rows,
-                                          const unsigned long long (&nn)[NC], const unsigned long long (&sum)[NC],
-                                          const long long (&mn)[NC], const long long (&mx)[NC]) {
-    if (entry == AGG_NO_ENTRY) return;
-    atomicAdd(&ap.m.rows[entry], rows);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        if (c >= ap.n_cols || nn[c] == 0) continue;
-        atomicAdd(&ap.m.nn[c][entry], nn[c]);
-        if (ap.col[c].need & AGG_NEED_SUM) atomicAdd(&ap.m.sum[c][entry], sum[c]);
-        if (ap.col[c].need & AGG_NEED_MIN) atomicMin(&ap.m.mn[c][entry], mn[c]);
-        if (ap.col[c].need & AGG_NEED_MAX) atomicMax(&ap.m.mx[c][entry], mx[c]);
-    }
-}
-// one finished group -> row `row` of the node's output arrays; the key is un-hashed, as the join does
-template <int KW, int NC>
-__device__ __forceinline__ void agg_write(const AggParams& ap, uint64_t row, unsigned long long k64, bool null_key,
-                                          unsigned long long rows, const unsigned long long (&nn)[NC],
-                                          const unsigned long long (&sum)[NC], const long long (&mn)[NC],
-                                          const long long (&mx)[NC]) {
-    if (row >= ap.out_cap) return;
-    if (ap.out.key) {
-        if constexpr (KW == 1)
-            reinterpret_cast<uint32_t*>(ap.out.key)[row] = null_key ? 0u : unfmix32((uint32_t)k64);
-        else
-            reinterpret_cast<unsigned long long*>(ap.out.key)[row] = null_key ? 0ull : unfmix64(k64);
-    }
-    if (null_key && ap.out_keyvalid) ap.out_keyvalid[row] = 0;
-    if (ap.out.rows) ap.out.rows[row] = rows;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        if (c >= ap.n_cols) continue;
-        if (ap.out.nn[c]) ap.out.nn[c][row] = nn[c];
-        if (ap.out.sum[c]) ap.out.sum[c][row] = sum[c];
-        if (ap.out.mn[c]) ap.out.mn[c][row] = mn[c];
-        if (ap.out.mx[c]) ap.out.mx[c][row] = mx[c];
-    }
-}
-
-template <int NC>
-struct AggTable {
-    unsigned long long key[AGG_CAP];
-    uint32_t           rows[AGG_CAP];
-    uint32_t           nn[NC][AGG_CAP];
-    unsigned long long sum[NC][AGG_CAP];
-    long long          mn[NC][AGG_CAP], mx[NC][AGG_CAP];
-};
-
-// One workgroup per partition, or per heavy task of a partition above JN_HEAVY tuples.  The LDS
-// table is open addressing over AGG_CAP entries, keyed by the hashed key words (64-bit compare and
-// swap; the "free" pattern is a key word 0 whose lowest radix bit differs from the partition's, so
-// no key of the partition equals it); the accumulators are LDS atomics: 32-bit counts, 64-bit add
-// and signed min / max.  The tuples go by in steps of AGG_STEP; between two steps every thread
-// reads the table's fill, and from AGG_FREEZE keys on the round is FROZEN: a tuple whose key is
-// not in the table (or — before that — that found the AGG_WALK entries from its home taken) is put back into the
-// partition's own memory from its start, always behind the read position, and is aggregated in the
-// next round with a fresh table.  A key that is in the table catches every later tuple of its
-// own, and a key that was turned away once never enters the same round (free entries only
-// vanish, and the frozen state only begins at a barrier), so every key is emitted in exactly one
-// round.  A partition's main workgroup reserves the rows of all groups of a round at once and
-// writes them; a heavy task adds its groups to the merge table in HBM instead (k_agg_emit).
-template <int KW, int CW>
-__global__ __launch_bounds__(AGG_THREADS) void k_agg_parts(AggParams ap) {
-    constexpr int NW = KW + CW, NC = CW ? CW : 1;
-    __shared__ AggTable<NC>       T;
-    __shared__ uint32_t           s_used, s_ndefer, s_wsum[AGG_THREADS / 64];
-    __shared__ unsigned long long s_obase;
-    const bool heavy = blockIdx.x < ap.heavy_grid;
-    uint32_t   b, e;
-    if (heavy) {
-        if (blockIdx.x >= *ap.n_heavy) return;
-        b = ap.heavy_tasks[3 * blockIdx.x + 1];
-        e = ap.heavy_tasks[3 * blockIdx.x + 2];
-    } else {
-        const uint32_t q = blockIdx.x - ap.heavy_grid;
-        if (q >= ap.NP) return;
-        b = ap.off[q];
-        e = ap.off[q + 1];
-        if (e - b > JN_HEAVY) return;  // (its tasks do it)
-    }
-    if (b >= e) return;
-    unsigned long long EMPTY;
-    {
-        uint32_t t0[NW];
-        part_tuple<KW, CW>(ap.W, ap.pack, ap.aos, b, t0);
-        EMPTY = (unsigned long long)(t0[0] ^ 1u);
-    }
-    uint32_t rd_e = e;
-    while (true) {
-        for (uint32_t i = threadIdx.x; i < AGG_CAP; i += AGG_THREADS) {
-            T.key[i] = EMPTY;
-            T.rows[i] = 0;
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                T.nn[c][i] = 0;
-                T.sum[c][i] = 0;
-                T.mn[c][i] = AGG_MIN_INIT;
-                T.mx[c][i] = AGG_MAX_INIT;
-            }
-        }
-        if (threadIdx.x == 0) {
-            s_used = 0;
-            s_ndefer = 0;
-        }
-        __syncthreads();
-        for (uint64_t base = b; base < rd_e; base += AGG_STEP) {
-            // (nobody changes s_used between the barrier that ended the last step and the next one)
-            const bool frozen = *(volatile uint32_t*)&s_used >= (uint32_t)AGG_FREEZE;
-            uint32_t   t[AGG_SPT][NW];
-            bool       live[AGG_SPT];
-#pragma unroll
-            for (int j = 0; j < AGG_SPT; ++j) {
-                const uint64_t idx = base + (uint64_t)j * AGG_THREADS + threadIdx.x;
-                live[j] = idx < rd_e;
-                if (live[j]) part_tuple<KW, CW>(ap.W, ap.pack, ap.aos, (uint32_t)idx, t[j]);
-            }
-            __syncthreads();  // every tuple of the step is in registers before a deferred one lands on it
-#pragma unroll
-            for (int j = 0; j < AGG_SPT; ++j) {
-                if (!live[j]) continue;
-                const uint32_t           lo = t[j][0], hi = KW == 2 ? t[j][KW - 1] : 0u;
-                const unsigned long long k64 = (unsigned long long)lo | ((unsigned long long)hi << 32);
-                uint32_t                 slot = ((lo ^ hi) * 0x9e3779b1u) >> (32 - ilog2_u32(AGG_CAP));
-                bool                     found = false;
-                for (uint32_t pr = 0; pr < (uint32_t)AGG_WALK; ++pr) {
-                    unsigned long long cur = __hip_atomic_load(&T.key[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (cur == EMPTY && !frozen) {
-                        cur = atomicCAS(&T.key[slot], EMPTY, k64);
-                        if (cur == EMPTY) {
-                            atomicAdd(&s_used, 1u);
-                            cur = k64;
-                        }
-                    }
-                    if (cur == k64) {
-                        found = true;
-                        break;
-                    }
-                    if (cur == EMPTY) break;  // frozen, and the key is not in the table
-                    slot = (slot + 1u) & (uint32_t)(AGG_CAP - 1);
-                }
-                if (!found) {
-                    const uint32_t pos = atomicAdd(&s_ndefer, 1u);
-                    part_tuple_store<KW, CW>(ap.W, ap.pack, ap.aos, b + pos, t[j]);
-                    continue;
-                }
-                atomicAdd(&T.rows[slot], 1u);
-                if constexpr (CW >= 1) {
-                    const uint32_t c0 = t[j][KW], c1 = CW >= 2 ? t[j][KW + (CW >= 2 ? 1 : 0)] : 0u,
-                                   c2 = CW >= 3 ? t[j][KW + (CW >= 3 ? 2 : 0)] : 0u;
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        long long v;
-                        if (c >= ap.n_cols || !agg_value(ap.col[c], ap.valid_word, c0, c1, c2, v)) continue;
-                        atomicAdd(&T.nn[c][slot], 1u);
-                        if (ap.col[c].need & AGG_NEED_SUM) atomicAdd(&T.sum[c][slot], (unsigned long long)v);
-                        if (ap.col[c].need & AGG_NEED_MIN) atomicMin(&T.mn[c][slot], v);
-                        if (ap.col[c].need & AGG_NEED_MAX) atomicMax(&T.mx[c][slot], v);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        // ---- the round's groups
-        constexpr int      EPT = AGG_CAP / AGG_THREADS;
-        uint32_t           cnt = 0;
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) cnt += T.key[threadIdx.x + k * AGG_THREADS] != EMPTY;
-        uint64_t row = 0;
-        if (!heavy) {
-            uint32_t       total;
-            const uint32_t pre = block_excl_scan(cnt, s_wsum, total);
-            if (threadIdx.x == 0) s_obase = total ? atomicAdd(ap.out_cursor, (unsigned long long)total) : 0ull;
-            __syncthreads();
-            row = s_obase + pre;
-        }
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            const uint32_t           i = threadIdx.x + k * AGG_THREADS;
-            const unsigned long long k64 = T.key[i];
-            if (k64 == EMPTY) continue;
-            unsigned long long nn[NC], sum[NC];
-            long long          mn[NC], mx[NC];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                nn[c] = T.nn[c][i];
-                sum[c] = T.sum[c][i];
-                mn[c] = T.mn[c][i];
-                mx[c] = T.mx[c][i];
-            }
-            if (heavy)
-                agg_merge<NC>(ap, agg_merge_entry(ap, k64), T.rows[i], nn, sum, mn, mx);
-            else
-                agg_write<KW, NC>(ap, row++, k64, false, T.rows[i], nn, sum, mn, mx);
-        }
-        const uint32_t nd = *(volatile uint32_t*)&s_ndefer;
-        if (nd == 0) break;
-        // the deferred tuples, written by any thread of the workgroup, are read by any other next round
-        __threadfence();
-        __syncthreads();
-        __threadfence();
-        rd_e = b + nd;
-    }
-}
-
-// The rows whose key is NULL: the first radix pass drops them; they form one group (SQL's GROUP BY),
-// entry m_slots + 1 of the merge table.  Grid-strided over the child's columns, per-thread
-// accumulators, a wave reduction, one set of atomics per wave that saw such a row.
-template <int CW>
-__global__ __launch_bounds__(JN_THREADS) void k_agg_nullkey(AggParams ap) {
-    constexpr int      NC = CW ? CW : 1;
-    unsigned long long rows = 0, nn[NC], sum[NC];
-    long long          mn[NC], mx[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        nn[c] = sum[c] = 0;
-        mn[c] = AGG_MIN_INIT;
-        mx[c] = AGG_MAX_INIT;
-    }
-    const uint32_t n = ap.src.n_rows;
-    for (uint64_t r = (uint64_t)blockIdx.x * JN_THREADS + threadIdx.x; r < n; r += (uint64_t)gridDim.x * JN_THREADS) {
-        if (ap.src.key.valid[r]) continue;
-        ++rows;
-        if constexpr (CW >= 1) {
-            uint32_t c0, c1, c2;
-            src_carry<CW>(ap.src, (uint32_t)r, c0, c1, c2);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                long long v;
-                if (c >= ap.n_cols || !agg_value(ap.col[c], ap.valid_word, c0, c1, c2, v)) continue;
-                ++nn[c];
-                sum[c] += (unsigned long long)v;
-                mn[c] = min(mn[c], v);
-                mx[c] = max(mx[c], v);
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        rows += __shfl_xor(rows, off);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            nn[c] += __shfl_xor(nn[c], off);
-            sum[c] += __shfl_xor(sum[c], off);
-            mn[c] = min(mn[c], __shfl_xor(mn[c], off));
-            mx[c] = max(mx[c], __shfl_xor(mx[c], off));
-        }
-    }
-    if ((threadIdx.x & 63u) == 0 && rows) agg_merge<NC>(ap, ap.m_slots + 1u, rows, nn, sum, mn, mx);
-}
-
-// the merge table before anybody adds to it
-__global__ __launch_bounds__(256) void k_agg_merge_init(AggParams ap) {
-    const uint64_t n = (uint64_t)ap.m_slots + 2;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        reinterpret_cast<unsigned long long*>(ap.m.key)[i] = AGG_NO_KEY;
-        ap.m.rows[i] = 0;
-        for (int c = 0; c < ap.n_cols; ++c) {
-            ap.m.nn[c][i] = 0;
-            ap.m.sum[c][i] = 0;
-            ap.m.mn[c][i] = AGG_MIN_INIT;
-            ap.m.mx[c][i] = AGG_MAX_INIT;
-        }
-    }
-}
-
-// The live entries of the merge table -> rows of the output, through the same cursor as
-// k_agg_parts: one reservation per 256 entries.  The NULL-key group's key comes out NULL.
-template <int KW>
-__global__ __launch_bounds__(256) void k_agg_emit(AggParams ap) {
-    __shared__ uint32_t           s_wsum[256 / 64];
-    __shared__ unsigned long long s_obase;
-    const uint64_t n = (uint64_t)ap.m_slots + 2;
-    for (uint64_t base = (uint64_t)blockIdx.x * 256; base < n; base += (uint64_t)gridDim.x * 256) {
-        const uint64_t i = base + threadIdx.x;
-        const bool     live = i < n && ap.m.rows[i] != 0;
-        uint32_t       total;
-        const uint32_t pre = block_excl_scan(live ? 1u : 0u, s_wsum, total);
-        if (threadIdx.x == 0) s_obase = total ? atomicAdd(ap.out_cursor, (unsigned long long)total) : 0ull;
-        __syncthreads();
-        if (live) {
-            unsigned long long nn[AGG_MAX_COLS], sum[AGG_MAX_COLS];
-            long long          mn[AGG_MAX_COLS], mx[AGG_MAX_COLS];
-#pragma unroll
-            for (int c = 0; c < AGG_MAX_COLS; ++c) {
-                const bool has = c < ap.n_cols;
-                nn[c] = has ? ap.m.nn[c][i] : 0;
-                sum[c] = has ? ap.m.sum[c][i] : 0;
-                mn[c] = has ? ap.m.mn[c][i] : 0;
-                mx[c] = has ? ap.m.mx[c][i] : 0;
-            }
-            const unsigned long long k64 = i < ap.m_slots ? reinterpret_cast<const unsigned long long*>(ap.m.key)[i] : AGG_NO_KEY;
-            agg_write<KW, AGG_MAX_COLS>(ap, s_obase + pre, k64, i == (uint64_t)ap.m_slots + 1, ap.m.rows[i], nn, sum, mn, mx);
-        }
-        __syncthreads();
-    }
-}
-
-// An accumulator array as a result column: narrowed to 32 bits for an INT32 MIN / MAX (dst,
-// optional), and NULL where the group had no value (dst_valid, optional; nn = nullptr: never).
-template <int WIDTH>
-__global__ __launch_bounds__(256) void k_agg_column(const unsigned long long* src, const unsigned long long* nn, uint64_t n,
-                                                    uint8_t* dst, uint8_t* dst_valid) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (dst) {
-        if (WIDTH == 4)
-            reinterpret_cast<uint32_t*>(dst)[i] = (uint32_t)src[i];
-        else
-            reinterpret_cast<unsigned long long*>(dst)[i] = src[i];
-    }
-    if (dst_valid) dst_valid[i] = nn ? (nn[i] != 0) : 1;
-}
-
-// ================================================================== selection
-// RJ_NODE_SELECT: the predicate program of rj_device.hpp (SelectProg) over a relation's columns, the
-// row ids of the rows it keeps compacted into out_ids.  The program is the same for every row, so the
-// op loop, the stack pointer and every branch on an op are uniform and ops[k] is read with scalar
-// loads; a row's stack is one 64-bit register of bits, as in k_ing_filter (the host checked the
-// depth: at most 60).  A thread evaluates SEL_BATCH rows op by op, so that the loads of one leaf are
-// in flight together, and keeps one bit per row it owns in the tile (SEL_ITEMS of them).  Wave w owns
-// the w-th quarter of the tile, 64 consecutive rows per item: ranks come from a ballot per item and a
-// prefix over the four wave totals in LDS, the tile reserves its range of out_ids with ONE atomic on
-// the cursor and writes its ids in ascending order.  The tile is large because that atomic is the
-// scarce resource: every workgroup of the grid adds to the same address.
-template <class T>
-__device__ __forceinline__ bool sel_cmp(int cmp, T x, T y) {
-    switch (cmp) {
-    case 0: return x == y;
-    case 1: return x != y;
-    case 2: return x < y;
-    case 3: return x > y;
-    case 4: return x <= y;
-    default: return x >= y;
-    }
-}
-// a leaf on one row: a comparison is false when an operand is NULL; doubles compare IEEE-wise
-__device__ __forceinline__ bool sel_leaf(const SelectOp& o, uint32_t row) {
-    bool nn = o.a.valid ? o.a.valid[row] != 0 : true;
-    if (o.kind == SEL_IS_NULL) return !nn;
-    if (o.kind == SEL_NOT_NULL) return nn;
-    const bool col = o.kind == SEL_COL;
-    if (col && o.b.valid) nn = nn && o.b.valid[row] != 0;
-    if (o.a.width == 4) {
-        const int64_t x = (int32_t)col_load32(o.a, row);
-        const int64_t y = col ? (int64_t)(int32_t)col_load32(o.b, row) : o.literal;
-        return nn && sel_cmp(o.cmp, x, y);
-    }
-    const uint64_t xb = col_load64(o.a, row);
-    const uint64_t yb = col ? col_load64(o.b, row) : (uint64_t)o.literal;
-    if (o.f64) return nn && sel_cmp(o.cmp, __longlong_as_double((long long)xb), __longlong_as_double((long long)yb));
-    return nn && sel_cmp(o.cmp, (int64_t)xb, (int64_t)yb);
-}
-
-__global__ __launch_bounds__(SEL_THREADS) void k_select(const SelectProg* __restrict__ prog, uint32_t n_ops, uint32_t n_rows,
-                                                        uint32_t* __restrict__ out_ids, unsigned long long* cursor) {
-    constexpr uint32_t NWAVES = SEL_THREADS / 64, WAVE_ROWS = SEL_TILE / NWAVES;
-    __shared__ uint32_t s_wtot[NWAVES];
-    __shared__ uint32_t s_base;
-    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    const uint32_t n_tiles = n_rows / SEL_TILE + (n_rows % SEL_TILE != 0);  // (n_rows + SEL_TILE - 1 may not fit 32 bits)
-    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint32_t tile_base = tile * SEL_TILE;  // (< n_rows)
-        const uint32_t in_tile = min((uint32_t)SEL_TILE, n_rows - tile_base);
-        const uint32_t local0 = wid * WAVE_ROWS + lane;  // item i: row tile_base + local0 + 64 i
-        uint32_t       keep = 0, wtot = 0;               // bit i: item i passed; the wave's rows that passed
-#pragma unroll 1
-        for (uint32_t b = 0; b < SEL_ITEMS; b += SEL_BATCH) {
-            if (wid * WAVE_ROWS + 64u * b >= in_tile) break;  // (the same for the whole wave)
-            uint64_t st[SEL_BATCH];
-#pragma unroll
-            for (int j = 0; j < SEL_BATCH; ++j) st[j] = 0;
-            uint32_t sp = 0;
-            for (uint32_t k = 0; k < n_ops; ++k) {
-                const SelectOp& o = prog->ops[k];
-                if (o.kind == SEL_AND || o.kind == SEL_OR) {
-                    sp -= 2;
-#pragma unroll
-                    for (int j = 0; j < SEL_BATCH; ++j) {
-                        const uint64_t x = (st[j] >> sp) & 1u, y = (st[j] >> (sp + 1)) & 1u;
-                        st[j] = (st[j] & ((1ull << sp) - 1ull)) | ((o.kind == SEL_AND ? (x & y) : (x | y)) << sp);
-                    }
-                    ++sp;
-                } else if (o.kind == SEL_NOT) {
-#pragma unroll
-                    for (int j = 0; j < SEL_BATCH; ++j) st[j] ^= 1ull << (sp - 1);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < SEL_BATCH; ++j) {
-                        const uint32_t local = local0 + 64u * (b + j);
-                        const uint64_t v = local < in_tile && sel_leaf(o, tile_base + local);
-                        st[j] |= v << sp;
-                    }
-                    ++sp;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < SEL_BATCH; ++j) {
-                const bool pass = local0 + 64u * (b + j) < in_tile && (st[j] & 1u);
-                keep |= (uint32_t)pass << (b + j);
-                wtot += (uint32_t)__popcll(__ballot(pass));
-            }
-        }
-        // ranks: item by item inside the wave (below), over the waves here; ONE reservation per tile
-        if (lane == 0) s_wtot[wid] = wtot;
-        __syncthreads();
-        uint32_t wbase = 0, total = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < NWAVES; ++w) {
-            const uint32_t t = s_wtot[w];
-            if (w < wid) wbase += t;
-            total += t;
-        }
-        if (threadIdx.x == 0 && total) s_base = (uint32_t)atomicAdd(cursor, (unsigned long long)total);
-        __syncthreads();
-        if (wtot) {  // (the same for the whole wave)
-            uint32_t pos = s_base + wbase;
-#pragma unroll 4
-            for (uint32_t i = 0; i < SEL_ITEMS; ++i) {
-                const bool     pass = (keep >> i) & 1u;
-                const uint64_t mask = __ballot(pass);
-                if (pass) out_ids[pos + lane_prefix(mask)] = tile_base + local0 + 64u * i;
-                pos += (uint32_t)__popcll(mask);
-            }
-        }
-    }
-}
-
 // ================================================================== launchers
-void launch_page_headers(const Launch& L, const uint8_t* pages, uint32_t n_pages, uint32_t rows_full,
-                         uint32_t* page_rows, unsigned long long* flags) {
-    if (!n_pages) return;
-    RJ_KLAUNCH(L, "page_headers", k_page_headers, std::min<uint32_t>((n_pages + 3) / 4, 8192u), 256, pages, n_pages,
-               rows_full, page_rows, flags);
-}
-
-void launch_rows_beyond(const Launch& L, const uint8_t* pages, uint32_t n_pages,
-                        const uint32_t* row_base, uint64_t num_rows, unsigned long long* flag) {
-    if (!n_pages) return;
-    RJ_KLAUNCH(L, "rows_beyond", k_rows_beyond, (n_pages + 3) / 4, 256, pages, n_pages, row_base,
-               num_rows, flag);
-}
-
-void launch_decode_pages(const Launch& L, const uint8_t* pages, uint32_t n_pages, int width,
-                         const uint32_t* row_base, uint64_t num_rows, uint8_t* values,
-                         uint8_t* valid) {
-    if (!n_pages) return;
-    if (width == 4)
-        RJ_KLAUNCH(L, "decode_pages", (k_decode_pages<4>), n_pages, 256, pages, row_base, num_rows,
-                   values, valid);
-    else
-        RJ_KLAUNCH(L, "decode_pages", (k_decode_pages<8>), n_pages, 256, pages, row_base, num_rows,
-                   values, valid);
-}
-
 void launch_scan_bins(const Launch& L, const uint32_t* in, uint32_t n, uint32_t* off,
                       uint32_t* cursor) {
     RJ_KLAUNCH(L, "scan_bins", (k_scan_bins<0>), 1, 1024, in, (const uint32_t*)nullptr, n, 1u, off, cursor);
@@ -2728,152 +1449,10 @@ void launch_heavy_tasks(const Launch& L, const uint32_t* offR, const uint32_t* o
                n_heavy, max_tasks);
 }
 
-void launch_join_bcast(const Launch& L, int key_words, int cw_build, int cw_probe,
-                       const BcastParams& bp, uint32_t grid) {
-    if (!grid) return;
-    for_shape2("join_broadcast", key_words, cw_build, cw_probe, [&](auto KW, auto CWR, auto CWS) {
-        RJ_KLAUNCH(L, "join_broadcast", (k_join_bcast<KW, CWR, CWS>), grid, JN_THREADS, bp);
-    });
-}
-
-// semi / anti joins: the preserved side's carry
-void launch_filter_bcast(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid) {
-    if (!grid) return;
-    for_shape("filter_broadcast", key_words, cw_preserved, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "filter_broadcast", (k_filter_bcast<KW, CW>), grid, JN_THREADS, fp);
-    });
-}
-
-void launch_filter_join(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid) {
-    if (!grid) return;
-    for_shape("filter_probe", key_words, cw_preserved, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "filter_probe", (k_filter_join<KW, CW>), grid, JN_THREADS, fp);
-    });
-}
-
-void launch_filter_nullkeys(const Launch& L, int key_words, int cw_preserved, const FilterParams& fp, uint32_t grid) {
-    if (!grid) return;
-    for_shape("filter_nullkeys", key_words, cw_preserved, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "filter_nullkeys", (k_filter_nullkeys<KW, CW>), grid, JN_THREADS, fp);
-    });
-}
-
-void launch_outer_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n, uint8_t* dst,
-                         uint8_t* dst_valid) {
-    if (!n) return;
-    const uint32_t grid = (uint32_t)((n + 255) / 256);
-    if (src.width == 4)
-        RJ_KLAUNCH(L, "outer_gather", (k_outer_gather<4>), grid, 256, src, idx, n, dst, dst_valid);
-    else
-        RJ_KLAUNCH(L, "outer_gather", (k_outer_gather<8>), grid, 256, src, idx, n, dst, dst_valid);
-}
-
-void launch_debug_stall(const Launch& L, uint32_t ms) {
-    int dev = 0, khz = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
-    RJ_KLAUNCH(L, "debug_stall", k_debug_stall, 1, 64, (unsigned long long)ms * (unsigned long long)khz);
-}
-
-void launch_pack_validity(const Launch& L, const uint8_t* v0, const uint8_t* v1, const uint8_t* v2, uint32_t n,
-                          uint32_t* out) {
-    if (!n) return;
-    RJ_KLAUNCH(L, "pack_validity", k_pack_validity, (n + 255) / 256, 256, v0, v1, v2, n, out);
-}
-
-void launch_split_records(const Launch& L, const SplitParams& sp, uint64_t n) {
-    if (!n) return;
-    RJ_KLAUNCH(L, "split_records", k_split_records, (uint32_t)((n + 255) / 256), 256, sp, n);
-}
-
-void launch_gather(const Launch& L, const ColRef& src, const uint32_t* idx, uint64_t n,
-                   const OutStream& dst, uint8_t* dst_valid) {
-    if (!n) return;
-    uint32_t grid = (uint32_t)((n + 255) / 256);
-    if (src.width == 4)
-        RJ_KLAUNCH(L, "gather", (k_gather<4>), grid, 256, src, idx, n, dst, dst_valid);
-    else
-        RJ_KLAUNCH(L, "gather", (k_gather<8>), grid, 256, src, idx, n, dst, dst_valid);
-}
-
-void launch_finish_pages(const Launch& L, uint8_t* pages, uint64_t n_rows, int width) {
-    if (!n_rows) return;
-    uint32_t rf = width == 4 ? ROWS32 : ROWS64;
-    uint32_t np = (uint32_t)((n_rows + rf - 1) / rf);
-    RJ_KLAUNCH(L, "finish_pages", k_finish_pages, np, 256, pages, n_rows, rf);
-}
-
-void launch_finish_streams(const Launch& L, uint8_t* const* pages, const int* widths, uint32_t n,
-                           const unsigned long long* n_rows_dev, uint64_t cap_rows) {
-    if (!n || !cap_rows) return;
-    FinishStreams fs{};
-    fs.n = n;
-    uint64_t max_pages = 0;
-    for (uint32_t i = 0; i < n && i < 3; ++i) {
-        fs.pages[i] = pages[i];
-        fs.rows_full[i] = widths[i] == 4 ? ROWS32 : ROWS64;
-        max_pages = std::max<uint64_t>(max_pages, (cap_rows + fs.rows_full[i] - 1) / fs.rows_full[i]);
-    }
-    RJ_KLAUNCH(L, "finish_pages", k_finish_streams, dim3((uint32_t)((max_pages + 3) / 4), n), 256, fs,
-               n_rows_dev, cap_rows);
-}
-
-void launch_encode_nullable(const Launch& L, const uint8_t* values, const uint8_t* valid,
-                            uint64_t n_rows, int width, uint8_t* pages) {
-    if (!n_rows) return;
-    uint32_t rf = width == 4 ? ROWS32 : ROWS64;
-    uint32_t np = (uint32_t)((n_rows + rf - 1) / rf);
-    if (width == 4)
-        RJ_KLAUNCH(L, "encode_nullable", (k_encode_nullable<4>), np, 256, values, valid, n_rows,
-                   pages);
-    else
-        RJ_KLAUNCH(L, "encode_nullable", (k_encode_nullable<8>), np, 256, values, valid, n_rows,
-                   pages);
-}
-
-// ---- aggregation
-void launch_agg_merge_init(const Launch& L, const AggParams& ap, uint32_t grid) {
-    RJ_KLAUNCH(L, "agg_merge_init", k_agg_merge_init, grid, 256, ap);
-}
-void launch_agg_parts(const Launch& L, int key_words, int carry_words, const AggParams& ap, uint32_t grid) {
-    if (!grid) return;
-    for_shape("agg_parts", key_words, carry_words, [&](auto KW, auto CW) {
-        RJ_KLAUNCH(L, "agg_parts", (k_agg_parts<KW, CW>), grid, AGG_THREADS, ap);
-    });
-}
-void launch_agg_nullkey(const Launch& L, int carry_words, const AggParams& ap, uint32_t grid) {
-    if (!grid) return;
-    for_shape("agg_nullkey", 1, carry_words, [&](auto, auto CW) {  // (no key: the carries of a one-word key)
-        RJ_KLAUNCH(L, "agg_nullkey", (k_agg_nullkey<CW>), grid, JN_THREADS, ap);
-    });
-}
-void launch_agg_emit(const Launch& L, int key_words, const AggParams& ap, uint32_t grid) {
-    if (key_words == 1)
-        RJ_KLAUNCH(L, "agg_emit", (k_agg_emit<1>), grid, 256, ap);
-    else
-        RJ_KLAUNCH(L, "agg_emit", (k_agg_emit<2>), grid, 256, ap);
-}
-void launch_agg_column(const Launch& L, const unsigned long long* src, const unsigned long long* nn, uint64_t n, int width,
-                       uint8_t* dst, uint8_t* dst_valid) {
-    if (!n) return;
-    const uint32_t grid = (uint32_t)((n + 255) / 256);
-    if (width == 4)
-        RJ_KLAUNCH(L, "agg_column", (k_agg_column<4>), grid, 256, src, nn, n, dst, dst_valid);
-    else
-        RJ_KLAUNCH(L, "agg_column", (k_agg_column<8>), grid, 256, src, nn, n, dst, dst_valid);
-}
-
-// ---- selection
-void launch_select(const Launch& L, const SelectProg* prog, uint32_t n_ops, uint32_t n_rows, uint32_t* out_ids,
-                   unsigned long long* cursor, uint32_t grid) {
-    if (!n_rows || !grid) return;
-    RJ_KLAUNCH(L, "select", k_select, grid, SEL_THREADS, prog, n_ops, n_rows, out_ids, cursor);
-}
-
 // RJ_CTX_PREWARM: one harmless launch, so that HIP loads this translation unit's code object when the context is
 // built (as prewarm_varchar_dev does).  NP = 0: every thread of k_heavy_tasks leaves at `q >= NP`, its first check,
 // before any pointer is read.
-void prewarm_kernels(const Launch& L, uint32_t* zeroed) {
+void prewarm_partition(const Launch& L, uint32_t* zeroed) {
     RJ_KLAUNCH(L, "prewarm", k_heavy_tasks, 1, 256, zeroed, zeroed, 0u, zeroed, zeroed, 0u);
 }
 

@@ -1,6 +1,6 @@
-// rj_tuple_util.hpp — what the kernel files of the join path (rj_kernels.hip, rj_join.hip, rj_outer.hip, rj_full.hip)
-// share: the hash mixers, stream stores, one tuple of a partitioned relation or of a child's columns, and the host
-// side of the one shape rule.  Device code: include from a .hip file only.
+// rj_tuple_util.hpp — what the kernel files of the join path (rj_pages, rj_partition, rj_join, rj_bcast, rj_filter,
+// rj_outer, rj_full, rj_agg .hip; rj_setop.hip) share: the hash mixers, stream stores, one tuple of a partitioned relation
+// or of a child's columns, and the host side of the one shape rule.  Device code: include from a .hip file only.
 #pragma once
 #include "rj_kernel_util.hpp"
 

@@ -383,7 +383,7 @@ SINGLE_NULL_SHAPES = ((INT32, 1984, "dword"), (INT64, 1007, "halfword"), (INT32,
 
 
 def bitmap_branch(nr):
-    """the branch of k_page_headers (csrc/rj_kernels.hip) a page of nr rows takes"""
+    """the branch of k_page_headers (csrc/rj_pages.hip) a page of nr rows takes"""
     nb = (nr + 7) // 8
     boff = PS - nb
     if nr % 32 == 0 and boff % 4 == 0:

@@ -6,7 +6,7 @@ hash-adversarial tests construct.  Here the join is a sort + searchsorted over t
   * NULL keys drop out on both sides;
   * duplicates on either side multiply;
   * FP64 keys compare by bit pattern and a NaN matches nothing (the device's documented rule,
-    csrc/rj_kernels.hip hash_keys).  Not for inputs holding both -0.0 and +0.0 keys: the
+    csrc/rj_partition.hip hash_keys).  Not for inputs holding both -0.0 and +0.0 keys: the
     reference lets those meet by accident of probing.
 The plan is Scan(0) JOIN Scan(1) in either order, with scans selecting columns of the inputs and
 the join's output list indexing left outputs ++ right outputs, as in the reference (plan.h)."""

@@ -1,6 +1,6 @@
 """Hash-adversarial joins: keys chosen against the device hash, not drawn from a random domain.
 
-The kernels lay out their work by the HASHED key (csrc/rj_kernels.hip, rj_join.hip): the low radix_bits bits pick
+The kernels lay out their work by the HASHED key (csrc/rj_partition.hip, rj_join.hip, rj_bcast.hip): the low radix_bits bits pick
 the partition, the next 11 bits the home bucket of the LDS table (a full bucket spills into the next,
 bucket 2047 wraps to 0), the broadcast table takes its home bucket from the lowest 11 bits, the
 tagged table stores h >> radix_bits as tag, a 64-bit key's high hash word separates keys whose low

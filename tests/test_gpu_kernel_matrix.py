@@ -1,6 +1,6 @@
 """Every compiled join / radix-pass kernel instantiation, driven against the oracle.
 
-The join path is a family of templated kernels (csrc/rj_kernels.hip, rj_join.hip): launch_join picks
+The join path is a family of templated kernels (csrc/rj_partition.hip, rj_join.hip, rj_bcast.hip): launch_join picks
 k_join<KW, CWR, CWS, OM, PK, TG> from the key width, the carry words per side, the output stream
 modes, the tuple layout between the passes and the tagged table; launch_join_bcast picks
 k_join_bcast<KW, CWR, CWS>; the pass launchers pick k_pass_hist / k_fine_hist / k_pass_scatter /

@@ -1,5 +1,6 @@
 """A context built with prewarm=True (RJ_CTX_PREWARM, what bench.py and Contest::build_context() use) loads
-the code object of every kernel file of the join path, and rj_varchar_dev.hip's, before its first execute.
+the code object of every kernel file of the join path (csrc/rj_pages.hip, rj_partition.hip, rj_join.hip, rj_bcast.hip,
+rj_filter.hip, rj_outer.hip, rj_full.hip, rj_agg.hip, rj_select.hip), and rj_varchar_dev.hip's, before its first execute.
 What is checked here is narrow: after those loads everything still computes correctly.  One plan per
 kernel family on ONE such context, 12 000 probe rows with NULL keys on both sides against 5 000 build rows
 — more than one LDS table holds (JN_RMAX), so the joins take the partition passes and the partitioned
@@ -91,7 +92,8 @@ def _check(ctx, plan, want, family):
     ("inner", NB, "k_join"), ("semi", NB, "k_filter_join"), ("anti", NB, "k_filter_join"), ("left outer", NB, "k_outer_join"),
     ("full outer", NB, "k_full_join"), ("agg", NB, "k_agg_parts"), ("select over join", NB, "k_select"),
     ("inner", NB_BCAST, "k_join_bcast"), ("semi", NB_BCAST, "k_filter_bcast"), ("anti", NB_BCAST, "k_filter_bcast"),
-    ("left outer", NB_BCAST, "k_outer_bcast"), ("full outer", NB_BCAST, "k_full_bcast")])
+    ("left outer", NB_BCAST, "k_outer_bcast"), ("full outer", NB_BCAST, "k_full_bcast"),
+    ("inner", NB, "k_pass_scatter"), ("inner", NB, "k_finish_streams")])
 def test_prewarmed_context_computes_every_family(contexts, kind, nb, family):
     plan = _plan(kind, nb)
     want = _oracle.execute(plan) if kind == "inner" else _selectref.execute(plan)

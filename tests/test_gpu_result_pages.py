@@ -17,7 +17,7 @@ through the inverse of the order in which the broadcast probe kernels write thei
 result has to show the pattern where it was meant (the validity of the column row by row; the row ids of
 a VARCHAR case in ascending order).  That order: a workgroup takes a chunk of JN_THREADS * JN_SPT probe
 rows, thread t holding the rows j * JN_THREADS + t, and writes them wave by wave, inside a wave by j,
-inside a j by lane (k_join_bcast in rj_kernels.hip, outer_emit in rj_outer_util.hpp).  It is probe order up to JN_THREADS
+inside a j by lane (k_join_bcast in rj_bcast.hip, outer_emit in rj_outer_util.hpp).  It is probe order up to JN_THREADS
 rows only, and it is fixed as long as the probe side is one chunk, which every placed case is.  Not
 placed, and said so where they are run:
   - RJ_NODE_AGG outputs: the groups come out in the order of the aggregation's hash table;

@@ -3,7 +3,7 @@
 The first pass of a key + two-word-carry plan (k_pass_scatter<3,SrcLoader<1,2,*>,1,*>) ranks a tile
 with one LDS atomic per item and no branch: an item that holds no tuple (past the end of a partial
 tile, NULL key) adds to one of PT_DUMMY dummy counters behind the real ones, and ranks and LDS
-positions travel two per register (14 bits of rank) (csrc/rj_kernels.hip: rank_tile, place_tile).
+positions travel two per register (14 bits of rank) (csrc/rj_partition.hip: rank_tile, place_tile).
 The other shapes here keep a branch per item; they share the kernel template, the loaders and the
 counter array with it, so the same data goes through them.  What can break, per plan shape:
 
