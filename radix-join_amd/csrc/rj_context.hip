@@ -1,6 +1,7 @@
 // rj_context.hip — context, HBM block cache, HIP-event profiler.
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 
@@ -31,6 +32,10 @@ void Tuning::from_env() {
     tpg2 = env_int("RJ_TUNE_TPG2", tpg2);
     packed_side = env_int("RJ_TUNE_PACKED_SIDE", packed_side);
     xcd_min_rows = env_int("RJ_TUNE_XCD_MIN_ROWS", xcd_min_rows);
+    spec_p1 = env_int("RJ_TUNE_SPEC_P1", spec_p1);
+    spec_min_rows = env_int("RJ_TUNE_SPEC_MIN_ROWS", spec_min_rows);
+    spec_sample = std::min(5, std::max(1, env_int("RJ_TUNE_SPEC_SAMPLE", spec_sample)));
+    spec_z = std::max(0, env_int("RJ_TUNE_SPEC_Z", spec_z));
     bcast = env_int("RJ_TUNE_BCAST", bcast);
     diag = env_int("RJ_DIAG", diag);
     varchar_dev_rows = env_int("RJ_TUNE_VARCHAR_DEV", varchar_dev_rows);

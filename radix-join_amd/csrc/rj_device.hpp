@@ -156,6 +156,26 @@ __host__ __device__ inline uint32_t pass_digit(const PassParams& pp, uint32_t w,
     return (w >> pp.shift) & mask;
 }
 
+// ---- Speculative first pass (no histogram: DESIGN.md §4) ---------------------------------------
+// The first pass of a big two-pass plan sizes the 2^fanout_log2 * 8 output sub-ranges from a SAMPLE
+// of the keys instead of counting them all: sub-range i gets cap[i] tuples of room (k_spec_caps), the
+// scatter checks the room in the reservation itself, and a sub-range that turns out too small sends
+// the whole partition() call back to the exact histogram path.  The speculative kernels take these
+// parameters as an argument of their own: PassParams, and with it every kernel of the exact path,
+// stays as it is.
+constexpr uint32_t SPEC_BINS = (1u << PT_MAXBITS) * 8u;  // sub-ranges of a 9-bit first pass: 4096
+struct SpecParams {
+    // one 64-bit word per sub-range: {next free position : low 32, tuples of room left : high 32}.
+    // A tile reserves c tuples with ONE atomic add of c | (0 - c) << 32; what comes back holds where
+    // the run starts and whether it fits (room >= c, compared as signed numbers: the room of a
+    // sub-range that overflowed goes negative and stays so)
+    unsigned long long* cursor;
+    uint32_t*           flag;        // OR 1: some reservation did not fit, the output is to be thrown away
+    uint32_t            sink;        // first tuple of the PT_TILE spare tuples behind the sub-ranges: where
+                                     // a run that did not fit is written (sink + its offset inside the tile)
+    uint32_t            sample_log2; // k_pass_sample: PT_TILE >> sample_log2 rows of every tile are counted
+};
+
 // ---- Build/probe -------------------------------------------------------------
 #ifndef RJ_JN_THREADS
 #define RJ_JN_THREADS 512

@@ -12,6 +12,7 @@
 //   * At the root the streams are written straight into Page images.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <functional>
 #include <set>
@@ -82,6 +83,8 @@ struct Parted {
     bool     packed = false;      // w[0] = {hashed key, carry} pairs, no w[1]
     bool     aos3 = false;        // w[0] = 12-byte {hashed key, carry lo, carry hi} tuples, no w[1..2]
     uint64_t n_tuples = 0;        // tuples that went in (NULL keys are dropped on the way: an upper bound)
+    bool     spec = false;        // the first pass ran without its histogram (partition(): spec_flag); the caller's flag word tells
+                                  // whether everything found room — if not, what is in here is in bounds but not the partition
 };
 
 // Tuples that already sit in the partition layout (hashed word arrays, a pair array for a
@@ -488,13 +491,15 @@ class Exec {
     // Source = columns (`src`: page decode, NULL drop and hashing ride on the first pass) or
     // tuples already in the partition layout (`ws`, sharded stage B).
     // `external`: caller-owned arrays that receive the output of a single-pass partition
+    // spec_flag (optional, device, zeroed by the caller): the call may run its first pass speculatively (see `spec`
+    // below); the word is then set on the device if the result has to be thrown away, Parted::spec says it was tried
     // after_offsets (optional): called once the FIRST pass' partition offsets are enqueued to be
     // computed, before its scatter is enqueued — a caller that needs the counts on the host
     // (the sharded join's stage A) copies them out ahead of the scatter.
     Parted partition(const TupleSrc* srcp, const WordSrc* ws, int KW, int CW, uint32_t bits,
                      uint32_t shift0 = 0, bool single_pass = false, const Words* external = nullptr,
                      const std::function<void(const uint32_t*)>* after_offsets = nullptr,
-                     const PassShape* shape = nullptr) {
+                     const PassShape* shape = nullptr, uint32_t* spec_flag = nullptr) {
         Parted P;
         const bool preseg = shape && shape->nseg > 0;
         P.NW = KW + CW;
@@ -562,6 +567,31 @@ class Exec {
         // the last two words of a carry of two or three words are ONE array of 8-byte pairs (at word
         // pair_word); key + one carry word one array of pairs altogether (packed)
         const int pair_word = CW >= 2 ? KW + CW - 2 : -1;
+        // The speculative first pass (SpecParams; only for a caller that handed in a flag word and
+        // repeats the call without it when the flag comes back set): no histogram over the source, the 8 << pbits[0]
+        // sub-ranges of its output are sized from a 2^-s sample of the keys plus a margin of z standard deviations,
+        // and the second pass reads them as input segments with gaps between them.
+        // The arrays of that output are made before any count exists.  With C sampled row positions (at most a
+        // slice per tile), B sub-ranges and sample counts c_i, sum c_i <= C, the capacities k_spec_caps hands out sum to
+        //   sum 2^s (c_i + z sqrt(c_i + 1) + z^2 / 2) + 32 B  <=  2^s C + 2^s z sqrt(B (C + B)) + 2^s z^2 / 2 B + 32 B
+        // (Cauchy–Schwarz on the square roots; 32 B: each is rounded up to a multiple of 32) — 1.071 n at 1 B rows,
+        // s = 5, z = 6.  One more tile behind them takes the runs that found no room.  Positions stay 32-bit even
+        // if every tuple were reserved behind a full sub-range: cap_max and n are both below 2^31.
+        const uint32_t spec_s = (uint32_t)ctx->tune.spec_sample;
+        const double   spec_z = ctx->tune.spec_z / 10.0;
+        uint64_t       spec_cap_max = 0;
+        {
+            const double Bn = (double)((uint64_t)8 << pbits[0]);
+            const double C = (double)((n + PT_TILE - 1) / PT_TILE) * (double)(PT_TILE >> spec_s);
+            const double bound = std::ldexp(C + spec_z * std::sqrt(Bn * (C + Bn)) + 0.5 * spec_z * spec_z * Bn, (int)spec_s) + 32.0 * Bn;
+            spec_cap_max = bound < 4.0e9 ? (((uint64_t)std::ceil(bound) + 255u) & ~(uint64_t)255u) : ~(uint64_t)0 >> 1;
+        }
+        const bool spec = spec_flag && ctx->tune.spec_p1 != 0 && passes == 2 && !fine && !ws && !external && !shape &&
+                          !after_offsets && !aos_mid && !packed_side && ctx->tune.mall_chunk <= 0 && ctx->tune.xcd_split &&
+                          n >= (uint64_t)ctx->tune.xcd_min_rows && n >= (uint64_t)ctx->tune.spec_min_rows &&
+                          spec_cap_max < (uint64_t(1) << 31) && n < (uint64_t(1) << 31);  // (... and the room left, which goes down by at most n, stays a signed 32-bit number)
+        P.spec = spec;
+        const uint64_t n_first_out = spec ? spec_cap_max + PT_TILE : n;  // tuples the first pass' output arrays hold
         for (int a = 0; a < (P.packed ? 1 : P.NW); ++a) {
             if (pair_word >= 0 && a == pair_word + 1) continue;
             const uint64_t wbytes = (P.packed || a == pair_word) ? 8 : 4;
@@ -571,7 +601,7 @@ class Exec {
             }
             if ((P.aos3 && passes == 1) || aos_mid) continue;  // every pass writes 12-byte tuples
             // (+2048: a blocked array ends with a whole block, see BlockedLoader)
-            A[a] = ctx->buf(n * wbytes + 2048);
+            A[a] = ctx->buf(n_first_out * wbytes + 2048);
             wa.w[a] = A[a]->as<uint32_t>();
             if (passes > (P.aos3 ? 2u : 1u)) {
                 B[a] = ctx->buf(n * wbytes + 2048);
@@ -583,6 +613,7 @@ class Exec {
         Words    cur = ws ? ws->w : Words{}, nxt = (P.aos3 && passes == 1) ? waos : wa;
         bool     cur_is_a = false;
         BufP       fine_off, fine_cursor, coarse_off, coarse_cursor;
+        BufP       spec_start, spec_limit, spec_end;  // per sub-range of a speculative first pass' output: [start, end) holds tuples, limit = start + capacity
         // tiles per group of the first pass (the fine histogram must know it: see fine_xcd)
         uint32_t tpg_first = tiles_per_group(n, 4096);
         if (ctx->tune.tpg1 > 0) tpg_first = (uint32_t)ctx->tune.tpg1;
@@ -642,10 +673,12 @@ class Exec {
             BufP     grp_start;
             // segments this pass reads / output segments it fills (the same unless the input is a
             // set of exchanged runs, several of which feed one output segment)
-            const bool      first_preseg = p == 0 && preseg;
-            const uint32_t  nseg_in = first_preseg ? shape->nseg : nseg;
+            // (... or the sub-ranges a speculative first pass left behind, eight per output segment)
+            const bool      first_preseg = p == 0 && preseg, spec_in = p == 1 && spec;
+            const uint32_t  nseg_in = first_preseg ? shape->nseg : (spec_in ? nseg << 3 : nseg);
             const uint32_t  n_oseg = first_preseg ? shape->n_oseg : nseg;
             const uint64_t  bins = (uint64_t)n_oseg * F;
+            const uint32_t* in_end = first_preseg ? shape->seg_end : (spec_in ? spec_end->as<uint32_t>() : nullptr);
             if (p == 0 && shape && shape->hi_shift) {
                 pp.hi_shift = shape->hi_shift;
                 pp.lo_bits = shape->lo_bits;
@@ -655,7 +688,7 @@ class Exec {
                 uint64_t gt = (uint64_t)pp.tiles_per_group * PT_TILE;
                 n_groups = (uint32_t)((n + gt - 1) / gt);
             } else {
-                pp.tiles_per_group = tiles_per_group(n / nseg_in + 1, 16);
+                pp.tiles_per_group = tiles_per_group(n / (spec_in ? n_oseg : nseg_in) + 1, 16);  // (spec_in: as for whole segments)
                 // the last pass of 12-byte-tuple plans (one 384-byte-run output stream) does
                 // better with short groups — 2 tiles per workgroup: 9.3-10.3 -> 8.9-9.1 ms per step
                 // at 1 B rows; packed 8-byte tuples lose with them
@@ -671,18 +704,38 @@ class Exec {
                     pp.xcd_remap = 1;
                     n_groups += 8;  // 8 * ceil(G / 8) workgroups
                 }
-                const uint32_t* in_off = first_preseg ? shape->seg_begin : seg_off->as<uint32_t>();
+                const uint32_t* in_off = first_preseg ? shape->seg_begin : (spec_in ? spec_start->as<uint32_t>() : seg_off->as<uint32_t>());
                 grp_start = ctx->buf(((uint64_t)nseg_in + 1) * 4);
-                launch_group_table(L, in_off, nseg_in, (uint32_t)gt, grp_start->as<uint32_t>(),
-                                   first_preseg ? shape->seg_end : nullptr);
+                launch_group_table(L, in_off, nseg_in, (uint32_t)gt, grp_start->as<uint32_t>(), in_end);
                 pp.nseg = nseg_in;
                 pp.seg_off = in_off;
-                pp.seg_end = first_preseg ? shape->seg_end : nullptr;
-                pp.oseg_shift = first_preseg ? shape->oseg_shift : 0u;
+                pp.seg_end = in_end;
+                pp.oseg_shift = first_preseg ? shape->oseg_shift : (spec_in ? 3u : 0u);
                 pp.grp_start = grp_start->as<uint32_t>();
             }
             BufP off, hist, cursor;  // this pass' partition offsets, bin totals, write cursors
-            if (fine) {  // offsets and cursors of both passes came out of the fine histogram
+            SpecParams sp{};
+            if (p == 0 && spec) {
+                // sample -> capacities, {position, room} cursors; the partition offsets come from where the cursors
+                // stand once the scatter is through (launch_spec_close below)
+                pp.xcd_log2 = 3u;
+                const uint32_t nb = (uint32_t)bins << 3;
+                hist = ctx->buf((uint64_t)nb * 4);
+                off = ctx->buf((bins + 1) * 4);
+                cursor = ctx->buf((uint64_t)nb * 8);
+                spec_start = ctx->buf((uint64_t)nb * 4);
+                spec_limit = ctx->buf((uint64_t)nb * 4);
+                spec_end = ctx->buf((uint64_t)nb * 4);
+                RJ_HIP(hipMemsetAsync(hist->p, 0, (uint64_t)nb * 4, ctx->stream));
+                pp.hist = hist->as<uint32_t>();
+                sp.cursor = cursor->as<unsigned long long>();
+                sp.flag = spec_flag;
+                sp.sink = (uint32_t)spec_cap_max;
+                sp.sample_log2 = spec_s;
+                launch_pass_sample_src(L, src, KW, pp, sp, n_groups);
+                launch_spec_caps(L, pp.hist, nb, spec_s, (float)spec_z, (uint32_t)spec_cap_max, spec_start->as<uint32_t>(),
+                                 spec_limit->as<uint32_t>(), sp.cursor);
+            } else if (fine) {  // offsets and cursors of both passes came out of the fine histogram
                 off = p == 0 ? coarse_off : fine_off;
                 cursor = p == 0 ? coarse_cursor : fine_cursor;
                 pp.cursor = cursor->as<uint32_t>();
@@ -757,7 +810,8 @@ class Exec {
                 else
                     launch_pass_hist_dense(L, cur, pp, n_groups);
                 // (one workgroup per OUTPUT segment; its base = where that segment starts)
-                launch_scan_segments(L, pp.hist, first_preseg ? shape->oseg_off : (p == 0 ? nullptr : pp.seg_off),
+                launch_scan_segments(L, pp.hist,
+                                     first_preseg ? shape->oseg_off : (p == 0 ? nullptr : (spec_in ? seg_off->as<uint32_t>() : pp.seg_off)),
                                      n_oseg, F, pp.xcd_log2, off->as<uint32_t>(), pp.cursor);
             }
             if (p == 0 && after_offsets) (*after_offsets)(off->as<uint32_t>());
@@ -793,16 +847,21 @@ class Exec {
                 }
                 const bool blk_out = blocked_mid && p + 1 < passes;
                 if (p == 0 && !ws)
-                    launch_pass_scatter_src_packed(L, src, pp, n_groups, nxt.w[0], blk_out);
+                    launch_pass_scatter_src_packed(L, src, pp, n_groups, nxt.w[0], blk_out, p == 0 && spec ? &sp : nullptr);
                 else if (blocked_mid)
                     launch_pass_scatter_blocked(L, cur.w[0], pp, n_groups, nxt.w[0], blk_out);
                 else
                     launch_pass_scatter_packed(L, cur.w[0], pp, n_groups, nxt.w[0]);
             } else if (p == 0 && !ws) {
-                launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, nxt, P.aos3 && p + 1 == passes);
+                launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, nxt, P.aos3 && p + 1 == passes, p == 0 && spec ? &sp : nullptr);
             } else {
                 launch_pass_scatter_dense(L, cur, P.NW, pair_word, pp, n_groups, nxt,
                                           P.aos3 && p + 1 == passes);
+            }
+            if (p == 0 && spec) {
+                launch_spec_close(L, sp.cursor, spec_start->as<uint32_t>(), spec_limit->as<uint32_t>(), F, spec_end->as<uint32_t>(),
+                                  off->as<uint32_t>());
+                if (ctx->tune.diag >= 1) spec_report(cursor, spec_limit, spec_start, (uint32_t)bins << 3, n, n_first_out);
             }
             seg_off = off;
             nseg = (uint32_t)bins;
@@ -825,6 +884,24 @@ class Exec {
         if (shape && !shape->prior_bits.empty()) P.pbits.insert(P.pbits.begin(), shape->prior_bits.begin(), shape->prior_bits.end());
         P.n_tuples = n;
         return P;
+    }
+
+    // RJ_DIAG >= 1: how full the sub-ranges of a speculative first pass came out (waits for the stream)
+    void spec_report(const BufP& cursor, const BufP& limit, const BufP& start, uint32_t nb, uint64_t n, uint64_t n_alloc) {
+        std::vector<unsigned long long> c(nb);
+        std::vector<uint32_t>           lim(nb), st(nb);
+        read_back(c.data(), cursor->p, (size_t)nb * 8);
+        read_back(lim.data(), limit->p, (size_t)nb * 4);
+        read_back(st.data(), start->p, (size_t)nb * 4);
+        double   worst = 0;
+        uint32_t over = 0;
+        for (uint32_t i = 0; i < nb; ++i) {
+            const double used = (double)((uint32_t)c[i] - st[i]), room = (double)(lim[i] - st[i]);
+            if (used > room) ++over;
+            if (room > 0) worst = std::max(worst, used / room);
+        }
+        fprintf(stderr, "[rj diag] speculative pass 1: rows=%llu sub-ranges=%u fullest=%.4f of its capacity, over=%u, room for %llu tuples (+%.3f)\n",
+                (unsigned long long)n, nb, worst, over, (unsigned long long)n_alloc, (double)n_alloc / (double)std::max<uint64_t>(n, 1) - 1.0);
     }
 
     // ---------------------------------------------------------------- join
@@ -1109,12 +1186,41 @@ class Exec {
         BufP     tasks;  // [max_tasks][3]
         uint32_t max_tasks = 0;
     };
-    CoParts partition_sides(JoinState& st, const JoinSpec& js, uint32_t bits) {
+    // counters (optional, from zeroed_counters()): either side's first pass may run speculatively (partition():
+    // spec_flag), with the node's two flag words; emit_with_retry then sees them with the row count, and
+    // repartition_exact() is what its caller does about a flag that is set
+    CoParts partition_sides(JoinState& st, const JoinSpec& js, uint32_t bits, const BufP* counters = nullptr) {
         CoParts        cp;
         const TupleSrc sb = make_src(st, st.bs(), js), sp = make_src(st, st.ps(), js);
-        cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits);
-        cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits);
+        uint32_t*      fl = counters ? (*counters)->as<uint32_t>() + 4 : nullptr;
+        cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits, 0, false, nullptr, nullptr, nullptr, fl);
+        cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits, 0, false, nullptr, nullptr, nullptr, fl ? fl + 1 : nullptr);
         return cp;
+    }
+    // A speculative first pass found a sub-range too small (flag_b / flag_p: on which side).  What the node has
+    // produced since is thrown away: that side is partitioned again, with its histogram, the heavy tasks are listed
+    // again (which zeroes the row cursor) and the flags are cleared.  The caller then points its kernel parameters
+    // at the new partitions and runs the probe again.
+    int  spec_fallbacks = 0;
+    void repartition_exact(JoinState& st, const JoinSpec& js, uint32_t bits, CoParts& cp, const BufP& counters, bool flag_b,
+                           bool flag_p) {
+        ++spec_fallbacks;
+        if (ctx->tune.diag >= 1)
+            fprintf(stderr, "[rj diag] %s: speculative pass 1 overflowed (build side %d, probe side %d): exact partition again (fallback %d of this plan)\n",
+                    st.kind->name, (int)flag_b, (int)flag_p, spec_fallbacks);
+        if (flag_b) {
+            const TupleSrc sb = make_src(st, st.bs(), js);
+            cp.B = Parted();  // (its arrays go back to the block cache first)
+            cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits);
+        }
+        if (flag_p) {
+            const TupleSrc sp = make_src(st, st.ps(), js);
+            cp.P = Parted();
+            cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits);
+        }
+        RJ_HIP(hipMemsetAsync(counters->as<uint32_t>() + 4, 0, 8, ctx->stream));
+        cp.tasks = BufP();
+        heavy_tasks(cp, counters);
     }
     // heavy probe partitions -> task list; zeroes all 16 bytes of `counters` on the way
     void heavy_tasks(CoParts& cp, const BufP& counters) {
@@ -1123,14 +1229,16 @@ class Exec {
         launch_heavy_tasks_zeroed(cp.B, cp.P, cp.tasks, counters, cp.max_tasks);
     }
     CoParts co_partition(JoinState& st, const JoinSpec& js, uint32_t bits, const BufP& counters) {
-        CoParts cp = partition_sides(st, js, bits);
+        CoParts cp = partition_sides(st, js, bits, &counters);
         heavy_tasks(cp, counters);
         return cp;
     }
-    // [0..7] out cursor (u64), [8..11] n_heavy
+    // [0..7] out cursor (u64), [8..11] n_heavy, [12..15] the aggregation's overflow flag, [16..19] / [20..23] a join's
+    // build / probe side: its speculative first pass did not fit (SpecParams::flag)
+    static constexpr size_t COUNTER_BYTES = 32;
     BufP zeroed_counters() {
-        BufP counters = ctx->buf(16);
-        RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
+        BufP counters = ctx->buf(COUNTER_BYTES);
+        RJ_HIP(hipMemsetAsync(counters->p, 0, COUNTER_BYTES, ctx->stream));
         return counters;
     }
     // the fields every partitioned probe kernel's parameters hold under the same names
@@ -1174,10 +1282,16 @@ class Exec {
     // waits for the read-back.  (FULL has no such stream: both of its sides are optional, so both
     // carries are dense records or row ids and no key stream exists; finish_paged_streams then
     // finds nothing and no k_finish_streams is launched.)
+    // `respec(flag_b, flag_p)` (optional; `counters` then come from zeroed_counters()): the sides were partitioned
+    // with partition_sides(.., &counters).  The flag words travel with the row count; when one is set the attempt
+    // counted rows of truncated partitions, so it is looked at before the count: respec() partitions again
+    // (repartition_exact) and the node starts over at its first capacity.
     template <class LaunchFn>
-    Emitted emit_with_retry(JoinState& st, const BufP& counters, uint64_t cap, LaunchFn&& launch) {
+    Emitted emit_with_retry(JoinState& st, const BufP& counters, uint64_t cap, LaunchFn&& launch,
+                            const std::function<void(bool, bool)>& respec = nullptr) {
         const JoinKind& K = *st.kind;
         Emitted         e;
+        const uint64_t  cap0 = cap;
         e.key_mode = st.need_key_stream ? stream_mode_of(st.is_root, st.KW * 4, true) : ST_NONE;
         for (int attempt = 1;; ++attempt) {
             e.key_stream = e.key_mode != ST_NONE ? ctx->buf(stream_bytes(e.key_mode, cap)) : BufP();
@@ -1189,7 +1303,19 @@ class Exec {
             e.finished.clear();
             finish_paged_streams(st, e, counters, cap);
             unsigned long long h = 0;
-            read_back(&h, counters->p, 8);
+            if (respec) {
+                uint32_t hw[6] = {};
+                read_back(hw, counters->p, sizeof hw);
+                if (hw[4] | hw[5]) {
+                    respec(hw[4] != 0, hw[5] != 0);
+                    cap = cap0;
+                    attempt = 0;
+                    continue;
+                }
+                h = (unsigned long long)hw[0] | ((unsigned long long)hw[1] << 32);
+            } else {
+                read_back(&h, counters->p, 8);
+            }
             e.nrows = h;
             if (e.nrows <= cap) return e;
             if (K.attempts == 1)
@@ -1217,19 +1343,25 @@ class Exec {
             fprintf(stderr, "[rj diag] join build=%llu probe=%llu bits=%u cw=%d/%d\n",
                     (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bits, bs.CW, ps.CW);
         if (broadcast_form(st, js)) return join_finish(st, js, nullptr, bits, root_res);
-        CoParts cp = partition_sides(st, js, bits);
-        return join_finish(st, js, &cp, bits, root_res);
+        BufP    counters = zeroed_counters();
+        CoParts cp = partition_sides(st, js, bits, &counters);
+        return join_finish(st, js, &cp, bits, root_res, counters);
     }
 
     // Build + probe of an inner join over co-partitioned tuples (cp->B / cp->P; nullptr = broadcast
     // join straight from the children's columns), output streams, late materialisation, result pages.
-    Rel join_finish(JoinState& st, const JoinSpec& js, CoParts* cp, uint32_t bits, Result* root_res) {
+    // (spec_counters: the zeroed counters the sides were partitioned with, if their first passes may have been speculative)
+    Rel join_finish(JoinState& st, const JoinSpec& js, CoParts* cp, uint32_t bits, Result* root_res,
+                    const BufP& spec_counters = BufP()) {
         Side &    bs = st.bs(), &ps = st.ps();
         const int KW = st.KW;
         // (not zeroed here: heavy_tasks() zeroes all of it, and the broadcast form uses the cursor
         // alone, which every attempt resets)
-        BufP counters = ctx->buf(16);  // [0..7] out cursor (u64), [8..11] n_heavy
+        BufP counters = spec_counters ? spec_counters : ctx->buf(COUNTER_BYTES);  // (see zeroed_counters)
         if (cp) heavy_tasks(*cp, counters);
+        std::function<void(bool, bool)> respec;
+        if (cp && spec_counters && (cp->B.spec || cp->P.spec))
+            respec = [&](bool fb, bool fpr) { repartition_exact(st, js, bits, *cp, counters, fb, fpr); };
         plan_carry_streams(st);
         Emitted e = emit_with_retry(st, counters, first_cap(st.cap_hint), [&](const OutStream& key, uint64_t cap) {
             if (!cp) {
@@ -1283,7 +1415,7 @@ class Exec {
                     fprintf(stderr, "[rj diag]   %-16s %6.1f %%  %8.0f cyc/wg\n", names[i],
                             100.0 * hd[i] / tot, (double)hd[i] / PB.NP);
             }
-        });
+        }, respec);
         if (st.vkey && e.nrows) e.nrows = verify_varchar_pairs(st, e.nrows);
         return join_assemble(st, js, e, root_res);
     }
@@ -1327,9 +1459,7 @@ class Exec {
         BufP counters = zeroed_counters();
         fp.out_cursor = counters->as<unsigned long long>();
         CoParts cp;
-        if (!bcast) {
-            // both sides partitioned as an inner join's would be; the filter side carries nothing
-            cp = co_partition(st, js, bits, counters);
+        auto    bind_parts = [&]() {
             set_heavy(fp, cp, counters, bits);
             fp.Fw = cp.B.w;
             fp.Pw = cp.P.w;
@@ -1337,7 +1467,18 @@ class Exec {
             fp.offP = cp.P.off->as<uint32_t>();
             fp.packP = cp.P.packed ? 1 : 0;
             fp.aosP = cp.P.aos3 ? 1 : 0;
+        };
+        if (!bcast) {
+            // both sides partitioned as an inner join's would be; the filter side carries nothing
+            cp = co_partition(st, js, bits, counters);
+            bind_parts();
         }
+        std::function<void(bool, bool)> respec;
+        if (cp.B.spec || cp.P.spec)
+            respec = [&](bool fb, bool fpr) {
+                repartition_exact(st, js, bits, cp, counters, fb, fpr);
+                bind_parts();
+            };
         // the output never holds more rows than the preserved side: streams of that size, no retry
         Emitted e = emit_with_retry(st, counters, ps.rel->n, [&](const OutStream& key, uint64_t cap) {
             fp.key = key;
@@ -1351,7 +1492,7 @@ class Exec {
                 if (anti && (fp.P.key.valid || fp.P.key_f64))
                     launch_filter_nullkeys(L, KW, ps.CW, fp, stride_grid(ps.rel->n));
             }
-        });
+        }, respec);
         return join_assemble(st, js, e, root_res);
     }
 
@@ -1459,6 +1600,14 @@ class Exec {
             fp.flags = flags->as<uint32_t>();
             fp.use_flags = bcast ? 1 : 0;
         }
+        std::function<void(bool, bool)> respec;
+        if (cp.B.spec || cp.P.spec)
+            respec = [&](bool fb, bool fpr) {
+                repartition_exact(st, js, bits, cp, counters, fb, fpr);
+                set_parts(op, cp, counters, bits);
+                // (FULL: the matched bits of the attempt that is thrown away)
+                if (flags) RJ_HIP(hipMemsetAsync(flags->p, 0, ((cp.B.n_tuples) / 32 + 2) * 4, ctx->stream));
+            };
         const uint32_t probe_grid = stride_grid(ps.rel->n), build_grid = stride_grid(bs.rel->n);
         // OUTER holds at least the preserved rows, FULL may hold every row of both sides, and
         // dup x dup may exceed either
@@ -1486,7 +1635,7 @@ class Exec {
                 if (probe_dropped) launch_outer_nullkeys(L, KW, ps.CW, op, probe_grid);
                 if (op.B.key.valid || op.B.key_f64) launch_full_buildrows(L, KW, bs.CW, fp, build_grid);
             }
-        });
+        }, respec);
         return join_assemble(st, js, e, root_res);
     }
 

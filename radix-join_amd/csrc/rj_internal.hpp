@@ -216,6 +216,12 @@ struct Tuning {
     int tpg2 = 0;         // RJ_TUNE_TPG2: tiles per group of the later passes (0 = auto)
     int xcd_min_rows = 40 << 20;  // RJ_TUNE_XCD_MIN_ROWS: ... for passes over at least this many tuples
     int xcd_split = 1;    // RJ_TUNE_XCD_SPLIT: XCD-aware output placement of the big passes (PassParams::xcd_log2, xcd_remap)
+    // The first pass of a join's big two-pass plans without its histogram: output sub-ranges sized from a
+    // sample of the keys, the exact histogram path again when one of them turns out too small
+    int spec_p1 = 1;      // RJ_TUNE_SPEC_P1: 0 = never
+    int spec_min_rows = 40 << 20;  // RJ_TUNE_SPEC_MIN_ROWS: ... for passes over at least this many tuples (XCD placement must be on for them too)
+    int spec_sample = 5;  // RJ_TUNE_SPEC_SAMPLE: log2 of the sampling rate's inverse (1 .. 5: of every tile of 16384 rows, 16384 >> it)
+    int spec_z = 60;      // RJ_TUNE_SPEC_Z: the safety margin's normal quantile z, in tenths (0: no margin at all — tests)
     int bcast = 1;        // RJ_TUNE_BCAST: broadcast join for build sides that fit one LDS table
     int diag = 0;         // RJ_DIAG: 1 = join phase stamps, 2 = host-side timings on stderr
     int varchar_dev_rows = 200000;  // RJ_TUNE_VARCHAR_DEV: root VARCHAR columns of at least this many

@@ -115,7 +115,19 @@ void launch_scan_fine(const Launch& L, const uint32_t* fine, uint32_t F1, uint32
 // aos3 (key_words == 1, carry_words == 2, last pass of a plan): out.w[0] receives 12-byte
 // {hashed key, carry lo, carry hi} tuples instead of a key array + a pair array
 void launch_pass_scatter_src(const Launch& L, const TupleSrc& src, int key_words, int carry_words,
-                             const PassParams& pp, uint32_t n_groups, const Words& out, bool aos3 = false);
+                             const PassParams& pp, uint32_t n_groups, const Words& out, bool aos3 = false,
+                             const SpecParams* spec = nullptr);
+// Speculative first pass (SpecParams; `spec` above and in launch_pass_scatter_src_packed selects the scatter
+// that checks its reservations): the sampled histogram — launch_pass_hist_src's grid and bins —, the
+// capacities out of it (start[nbins], limit[nbins], cursor[nbins]; nothing beyond cap_max; z = the normal
+// quantile of the margin) and, behind the scatter, the second pass' input segments [start[i], seg_end[i]) and
+// output segment bases oseg_off[F + 1] (F <= PT_MAXF digits of 8 sub-ranges each)
+void launch_pass_sample_src(const Launch& L, const TupleSrc& src, int key_words, const PassParams& pp,
+                            const SpecParams& sp, uint32_t n_groups);
+void launch_spec_caps(const Launch& L, const uint32_t* sample, uint32_t nbins, uint32_t sample_log2, float z,
+                      uint32_t cap_max, uint32_t* start, uint32_t* limit, unsigned long long* cursor);
+void launch_spec_close(const Launch& L, const unsigned long long* cursor, const uint32_t* start, const uint32_t* limit,
+                       uint32_t F, uint32_t* seg_end, uint32_t* oseg_off);
 // Dense pass: re-partition every segment of already partitioned word arrays.
 void launch_pass_hist_dense(const Launch& L, const Words& in, const PassParams& pp,
                             uint32_t n_groups);
@@ -137,7 +149,8 @@ void launch_pass_scatter_aos3(const Launch& L, const uint32_t* in_tuples, const 
 void launch_pass_hist_packed(const Launch& L, const uint32_t* in_pairs, const PassParams& pp,
                              uint32_t n_groups);
 void launch_pass_scatter_src_packed(const Launch& L, const TupleSrc& src, const PassParams& pp,
-                                    uint32_t n_groups, uint32_t* out_pairs, bool blocked_out = false);
+                                    uint32_t n_groups, uint32_t* out_pairs, bool blocked_out = false,
+                                    const SpecParams* spec = nullptr);
 // (pairs between the passes of a packed plan in blocks of 256 keys + 256 carries: the next histogram reads the keys only)
 void launch_pass_hist_blocked(const Launch& L, const uint32_t* in_blocked, const PassParams& pp, uint32_t n_groups);
 void launch_pass_scatter_blocked(const Launch& L, const uint32_t* in_blocked, const PassParams& pp, uint32_t n_groups,

@@ -763,6 +763,128 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_hist(Loader ld, PassParams 
     }
 }
 
+// ============================================== speculative first pass: sample, capacities, closing
+// k_pass_hist over the source with a 2^-sample_log2 sample: grid, workgroup -> tile-group mapping and bins
+// (hist[(d << 3) | (blockIdx.x & 7)]) are k_pass_hist's, but of every tile only one slice of
+// PT_TILE >> sample_log2 consecutive rows is read.  Sub-range x of digit d is therefore sampled from exactly the
+// rows that the workgroups with g & 7 == x will scatter.  The slice's place inside its tile moves with the tile
+// index by 7 slices (an odd number: every place comes up before one repeats), so that data with a fixed period
+// does not meet the sample at the same phase in every tile.  NULL keys, rows behind the relation's end and
+// hashing are the scatter's (SrcLoader::drop_invalid / hash_keys).  A partial last tile is sampled from its
+// first rows on.
+static_assert((PT_TILE & (PT_TILE - 1)) == 0, "a tile's sample slice is a power-of-two fraction of it");
+template <int KW>
+__global__ __launch_bounds__(PT_THREADS) void k_pass_sample(TupleSrc s, PassParams pp, SpecParams sp) {
+    __shared__ uint32_t s_h[PT_MAXF];
+    uint32_t            seg, begin, end;
+    if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
+    const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
+    for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) s_h[d] = 0;
+    lds_barrier();
+    const uint32_t slog = (uint32_t)__builtin_ctz((unsigned)PT_TILE) - sp.sample_log2, slice = 1u << slog;
+    const uint32_t ntiles = (end - begin + (uint32_t)PT_TILE - 1u) / (uint32_t)PT_TILE;
+    const uint32_t total = ntiles << slog;  // sample positions of this group
+    constexpr int  U = 4;                   // positions a thread has in flight
+    for (uint32_t i0 = threadIdx.x; i0 < total; i0 += U * PT_THREADS) {
+        uint32_t lo[U], hi[U];
+        bool     ok[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t i = i0 + u * PT_THREADS, ic = min(i, total - 1u);
+            const uint32_t t = ic >> slog, r = ic & (slice - 1u);
+            const uint32_t tb = begin + t * (uint32_t)PT_TILE, rows = min((uint32_t)PT_TILE, end - tb);
+            const uint32_t rot = ((tb / (uint32_t)PT_TILE) * 7u << slog) & ((uint32_t)PT_TILE - 1u);
+            const uint32_t at = rows > slice ? min(rot, rows - slice) : 0u;
+            const uint32_t row = tb + min(at + r, rows - 1u);
+            ok[u] = i < total && r < rows;
+            if constexpr (KW == 1) {
+                lo[u] = col_load32(s.key, row);
+                hi[u] = 0;
+            } else {
+                const uint64_t k = col_load64(s.key, row);
+                lo[u] = (uint32_t)k;
+                hi[u] = (uint32_t)(k >> 32);
+            }
+            if (s.key.valid && !s.key.valid[row]) ok[u] = false;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            uint32_t h;
+            if constexpr (KW == 1) {
+                h = s.prehashed ? lo[u] : fmix32(lo[u]);
+            } else {
+                const uint64_t k = (uint64_t)lo[u] | ((uint64_t)hi[u] << 32);
+                if (s.key_f64 && (k & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (k & 0x000fffffffffffffull))
+                    ok[u] = false;  // NaN never matches (see SrcLoader::hash_keys)
+                h = (uint32_t)fmix64(k);
+            }
+            if (ok[u]) atomicAdd(&s_h[pass_digit(pp, h, mask)], 1u);
+        }
+    }
+    lds_barrier();
+    for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) {
+        uint32_t c = s_h[d];
+        if (c) atomicAdd(&pp.hist[(((size_t)seg * F + d) << pp.xcd_log2) | (blockIdx.x & ((1u << pp.xcd_log2) - 1u))], c);
+    }
+}
+
+// Capacities from the sample counts, one workgroup.  A sub-range whose sample holds c tuples gets room for
+//   cap = 2^s (c + z sqrt(c + 1) + z^2 / 2)   tuples, rounded up to a multiple of 32
+// — a one-sided normal bound on a binomial count: for rows in random order a sub-range overflows with
+// probability Phi(-z).  start[] is the exclusive scan of cap in bin order (x minor under d: a digit's eight
+// sub-ranges stay adjacent), limit[] = start + cap, cursor[] = {start, cap}.  Nothing reaches beyond cap_max,
+// the tuples the host made room for from its bound on the sum (Exec::partition): a sub-range that would is cut
+// there, and overflows like any other that is too small.
+__global__ __launch_bounds__(1024) void k_spec_caps(const uint32_t* sample, uint32_t nbins, uint32_t sample_log2, float z,
+                                                    uint32_t cap_max, uint32_t* start, uint32_t* limit,
+                                                    unsigned long long* cursor) {
+    __shared__ unsigned long long s_sum[1024];
+    const uint32_t                chunk = (nbins + 1023u) / 1024u;
+    const uint32_t                b = min(nbins, threadIdx.x * chunk), e = min(nbins, b + chunk);
+    auto                          cap_of = [&](uint32_t c) -> unsigned long long {
+        const double zz = (double)z, x = (double)c + zz * sqrt((double)c + 1.0) + 0.5 * zz * zz;
+        const unsigned long long t = (unsigned long long)ceil(ldexp(x, (int)sample_log2));
+        return (t + 31ull) & ~31ull;
+    };
+    unsigned long long sum = 0;
+    for (uint32_t i = b; i < e; ++i) sum += cap_of(sample[i]);
+    s_sum[threadIdx.x] = sum;
+    __syncthreads();
+    unsigned long long run = 0;
+    for (uint32_t k = 0; k < threadIdx.x; ++k) run += s_sum[k];
+    for (uint32_t i = b; i < e; ++i) {
+        const unsigned long long nx = run + cap_of(sample[i]);
+        const uint32_t           st = (uint32_t)min(run, (unsigned long long)cap_max);
+        const uint32_t           lim = (uint32_t)min(nx, (unsigned long long)cap_max);
+        start[i] = st;
+        limit[i] = lim;
+        cursor[i] = (unsigned long long)st | ((unsigned long long)(lim - st) << 32);
+        run = nx;
+    }
+}
+
+// Closing the speculative pass, one workgroup, thread d = digit d: sub-range i of the output holds
+// [start[i], seg_end[i]), seg_end = min(where its cursor stands, its limit) — the input segments of the second
+// pass — and digit d, the OUTPUT segment of its eight sub-ranges, has the sum of their sizes; oseg_off is the
+// exclusive scan of those: where the partitions of digit d begin in the dense output of the second pass.
+__global__ __launch_bounds__(PT_MAXF) void k_spec_close(const unsigned long long* cursor, const uint32_t* start,
+                                                        const uint32_t* limit, uint32_t F, uint32_t* seg_end,
+                                                        uint32_t* oseg_off) {
+    __shared__ uint32_t s_wsum[PT_MAXF / 64];
+    const uint32_t      d = threadIdx.x;
+    uint32_t            v = 0;
+    if (d < F)
+        for (uint32_t x = 0; x < 8; ++x) {
+            const uint32_t i = (d << 3) | x, en = min((uint32_t)cursor[i], limit[i]);
+            seg_end[i] = en;
+            v += en - start[i];
+        }
+    uint32_t       total;
+    const uint32_t ex = block_excl_scan(v, s_wsum, total);
+    if (d < F) oseg_off[d] = ex;
+    if (d == 0) oseg_off[F] = total;
+}
+
 // Two-pass plans whose final partition count fits an LDS histogram (<= 2^PT_FINEBITS bins)
 // count BOTH digits in the one read of the source: bin q = d1 * F2 + d2 is the final
 // partition, its exclusive scan is at once the pass-2 offsets and (every F2-th entry) the
@@ -955,179 +1077,21 @@ struct is_src_loader<SrcLoader<KW, CW, WIDE>> : std::true_type {};
 // (Prefetching the next tile's loads behind the second half's staging lost at 1 B rows, pass 1
 // 10.4-11.3 -> 12.0 ms: a burst of loads next to the copy-out's stores only gets in their way.
 // Taken out again; profiles/r03_h_scatter_tile_prefetch_ab.log is the record.)
+// SPEC (k_spec_scatter, the speculative first pass: SpecParams): a digit's run is reserved from the 64-bit
+// {position, room} cursor of its sub-range; a run that does not fit raises sp.flag and goes, with the unchanged
+// copy-out, to the spare tile at sp.sink — inside the allocation and in nobody's sub-range.  Kernels of their
+// own names (the exact ones keep theirs, their arguments and their machine code); both include the one body,
+// rj_pass_scatter.inc, with SPEC as a constant.
 template <int NW, class Loader, int PAIR, bool AOS>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassParams pp, Words out) {
-    static_assert(PAIR < 0 || (PAIR >= 1 && PAIR + 1 < NW), "pair = two carry words behind the key");
-    static_assert(!AOS || (NW == 3 && PAIR == 1), "12-byte tuples: one key word + a two-word carry");
-    __shared__ uint2    s_stage2[PT_TILE];  // 128 KiB: a word array uses the first half
-    uint32_t* const     s_stage = reinterpret_cast<uint32_t*>(s_stage2);
-    __shared__ uint32_t s_cnt[PT_MAXF + PT_DUMMY];  // (see rank_tile)
-    __shared__ uint32_t s_base[PT_MAXF];
-    __shared__ uint32_t s_delta[PT_MAXF];
-    __shared__ uint32_t s_wsum[PT_THREADS / 64];
-    uint32_t            seg, begin, end;
-    if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
-    const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
-
-    // Thread d owns digit d's write cursor in a REGISTER: the reservation's round trip is
-    // not waited for until the first tile has been loaded and ranked.
-    uint32_t run = 0;  // thread d: where digit d's run of the current tile starts in the output
-    uint32_t w[PT_ITEMS][NW];
-
-    for (uint32_t base = begin; base < end; base += PT_TILE) {
-        for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) s_cnt[d] = 0;
-        lds_barrier();
-
-        // every load of the tile is issued before the first rank is taken; the ranks wait for the keys only
-        const uint32_t ok = ld.template load_tile<NW>(base, end, w);
-        // first pass of key + two-word carry: ranks and positions two per register, branch-free (rank_tile).
-        // Everything else keeps a rank per register and a branch per item.  The later passes of that shape
-        // and the packed kernel gained nothing measurable from the branch-free form
-        // (profiles/scatter_rank_ab.log), and with up to four words per tuple in registers there is no room
-        // for PT_ITEMS ranks in flight (compiled that way, the four-word kernels spilled more than they do)
-        constexpr bool BATCHED = NW == 3 && PAIR == 1 && is_src_loader<Loader>::value;
-        uint32_t       ps[PT_ITEMS / 2];  // BATCHED: ranks, then LDS positions, two per register
-        uint32_t       dr[PT_ITEMS];      // otherwise: digit << 16 | rank, then LDS position; 0xffffffff = no tuple
-        if constexpr (BATCHED) {
-            rank_tile<NW>(pp, mask, ok, w, s_cnt, ps);
-        } else {
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; ++j) {
-                dr[j] = 0xffffffffu;
-                if ((ok >> j) & 1u) {
-                    uint32_t d = pass_digit(pp, w[j][0], mask);
-                    uint32_t r = atomicAdd(&s_cnt[d], 1u);
-                    dr[j] = (d << 16) | r;
-                }
-            }
-        }
-        lds_barrier();
-
-        // PT_THREADS >= PT_MAXF: thread d scans digit d
-        // Thread d reserves digit d's range of this tile with one global atomic; its round
-        // trip is not waited for until word 0 has been staged.
-        uint32_t c = threadIdx.x < F ? s_cnt[threadIdx.x] : 0u;
-        if (c) {
-            run = atomicAdd(&pp.cursor[(((size_t)seg * F + threadIdx.x) << pp.xcd_log2) |
-                                       (blockIdx.x & ((1u << pp.xcd_log2) - 1u))], c);
-        }
-        uint32_t total;
-        uint32_t ex = block_excl_scan(c, s_wsum, total);
-        if (threadIdx.x < F) s_base[threadIdx.x] = ex;
-        lds_barrier();
-
-        // LDS position of every tuple, computed once for all word arrays
-        if constexpr (BATCHED) {
-            place_tile<NW>(pp, mask, ok, w, s_base, ps);
-        } else {
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; ++j)
-                if (dr[j] != 0xffffffffu) dr[j] = s_base[dr[j] >> 16] + (dr[j] & 0xffffu);
-        }
-
-        // key + two-word carry (NW == 3): keys and carry pairs of half the sorted tile are staged
-        // TOGETHER and copied out together — as 12-byte tuples (AOS) or into the key array and the
-        // pair array — so no per-element destination has to be kept in registers between the two
-        // arrays (the 16 extra VGPRs spilled to scratch)
-        // (the copy-out's thread index is opaque to the compiler: its element indices and LDS addresses,
-        // 3 * PT_ITEMS values that do not change from tile to tile, were otherwise hoisted out of the tile
-        // loop and held in registers — or spilled — through the phases that have every load in flight)
-        const uint32_t tid = BATCHED ? tile_tid() : threadIdx.x;  // (the other shapes compile to more scratch with it)
-        if constexpr (NW == 3 && PAIR == 1) {
-            constexpr uint32_t HALF = PT_TILE / 2;
-            uint2* const       s_p = s_stage2;                                      // [HALF] carries
-            uint32_t* const    s_k = reinterpret_cast<uint32_t*>(s_stage2 + HALF);  // [HALF] keys
-            if (!BATCHED && threadIdx.x < F) s_delta[threadIdx.x] = run - ex;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                for (int j = 0; j < PT_ITEMS; ++j) {
-                    const uint32_t lp = (BATCHED ? tile_pos(ps, j) : dr[j]) - h * HALF;  // (no tuple: PT_NO_POS stays out of range)
-                    if (lp < HALF) {
-                        s_k[lp] = w[j][0];
-                        s_p[lp] = make_uint2(w[j][1], w[j][2]);
-                    }
-                }
-                // global index = delta + sorted position.  BATCHED: behind the first half's staging, since the
-                // reservation was issued after the carry loads and waiting for it waits for all of them
-                if (BATCHED && h == 0 && threadIdx.x < F) s_delta[threadIdx.x] = run - ex;
-                lds_barrier();
-#pragma unroll
-                for (int k = 0; k < PT_ITEMS / 2; ++k) {
-                    const uint32_t i = k * PT_THREADS + tid, gi = h * HALF + i;
-                    if (gi < total) {
-                        const uint32_t v = s_k[i];
-                        const uint2    c = s_p[i];
-                        const uint32_t g = s_delta[pass_digit(pp, v, mask)] + gi;
-                        if constexpr (AOS) {
-                            uint32_t* o = out.w[0] + (size_t)g * 3u;
-                            o[0] = v;
-                            o[1] = c.x;
-                            o[2] = c.y;
-                            if (pp.side_out) pp.side_out[g] = (uint16_t)((v >> pp.next_shift) & pp.next_mask);
-                        } else {
-                            out.w[0][g] = v;
-                            reinterpret_cast<uint2*>(out.w[1])[g] = c;
-                        }
-                    }
-                }
-                lds_barrier();
-            }
-            continue;
-        }
-        // word 0 (the hashed key): stage in digit order, copy out.  The digit of a staged
-        // key is recomputed from the key itself, and the global destination of each LDS
-        // position is kept in a register for the remaining word arrays.
-#pragma unroll
-        for (int j = 0; j < PT_ITEMS; ++j)
-            if (dr[j] != 0xffffffffu) s_stage[dr[j]] = w[j][0];
-        if (threadIdx.x < F) s_delta[threadIdx.x] = run - ex;  // global index = delta + LDS position
-        lds_barrier();
-        uint32_t dest[PT_ITEMS];
-#pragma unroll
-        for (int k = 0; k < PT_ITEMS; ++k) {
-            const uint32_t i = k * PT_THREADS + tid;
-            dest[k] = 0;
-            if (i < total) {
-                const uint32_t v = s_stage[i];
-                dest[k] = s_delta[pass_digit(pp, v, mask)] + i;
-                out.w[0][dest[k]] = v;
-            }
-        }
-        lds_barrier();
-#pragma unroll
-        for (int a = 1; a < NW; ++a) {
-            if constexpr (PAIR >= 0) {
-                if (a == PAIR + 1) continue;  // went out with word PAIR
-                if (a == PAIR) {
-#pragma unroll
-                    for (int j = 0; j < PT_ITEMS; ++j)
-                        if (dr[j] != 0xffffffffu)
-                            s_stage2[dr[j]] = make_uint2(w[j][a], w[j][a + 1 < NW ? a + 1 : a]);
-                    lds_barrier();
-                    uint2* dst2 = reinterpret_cast<uint2*>(out.w[a]);
-#pragma unroll
-                    for (int k = 0; k < PT_ITEMS; ++k) {
-                        const uint32_t i = k * PT_THREADS + tid;
-                        if (i < total) dst2[dest[k]] = s_stage2[i];
-                    }
-                    lds_barrier();
-                    continue;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < PT_ITEMS; ++j)
-                if (dr[j] != 0xffffffffu) s_stage[dr[j]] = w[j][a];
-            lds_barrier();
-            uint32_t* dst = out.w[a];
-#pragma unroll
-            for (int k = 0; k < PT_ITEMS; ++k) {
-                const uint32_t i = k * PT_THREADS + tid;
-                if (i < total) dst[dest[k]] = s_stage[i];
-            }
-            lds_barrier();
-        }
-    }
+    constexpr bool       SPEC = false;
+    constexpr SpecParams sp{};
+#include "rj_pass_scatter.inc"
+}
+template <int NW, class Loader, int PAIR>
+__global__ __launch_bounds__(PT_THREADS) void k_spec_scatter(Loader ld, PassParams pp, Words out, SpecParams sp) {
+    constexpr bool SPEC = true, AOS = false;
+#include "rj_pass_scatter.inc"
 }
 
 // Packed variant for {hashed key, one carry word} tuples (the BASELINE shape): the tile is
@@ -1138,72 +1102,15 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassPara
 // rate follows; it also needs one staging round and two barriers less per tile.
 template <class Loader, bool BLK_OUT = false>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter_packed(Loader ld, PassParams pp, uint2* out) {
-    __shared__ uint2    s_stage[PT_TILE];
-    __shared__ uint32_t s_cnt[PT_MAXF];
-    __shared__ uint32_t s_base[PT_MAXF];
-    __shared__ uint32_t s_delta[PT_MAXF];
-    __shared__ uint32_t s_wsum[PT_THREADS / 64];
-    uint32_t            seg, begin, end;
-    if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
-    const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
-
-    uint32_t run = 0;  // thread d: where digit d's run of the current tile starts in the output
-    // the next tile's loads are issued as soon as this tile has been staged (its registers are
-    // dead then) and fly during the copy-out
-    uint32_t w[PT_ITEMS][2];
-    uint32_t ok_raw = ld.template issue_tile<2>(begin, end, w);
-    for (uint32_t base = begin; base < end; base += PT_TILE) {
-        for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) s_cnt[d] = 0;
-        lds_barrier();
-
-        uint32_t       dr[PT_ITEMS];  // digit << 16 | rank, 0xffffffff = no tuple
-        const uint32_t ok = ld.template finish_tile<2>(base, end, ok_raw, w);  // (source tuples: NULL drop + hashing)
-#pragma unroll
-        for (int j = 0; j < PT_ITEMS; ++j) {
-            dr[j] = 0xffffffffu;
-            if ((ok >> j) & 1u) {
-                uint32_t d = pass_digit(pp, w[j][0], mask);
-                uint32_t r = atomicAdd(&s_cnt[d], 1u);
-                dr[j] = (d << 16) | r;
-            }
-        }
-        lds_barrier();
-
-        uint32_t c = threadIdx.x < F ? s_cnt[threadIdx.x] : 0u;
-        if (c)
-            run = atomicAdd(&pp.cursor[(((size_t)seg * F + threadIdx.x) << pp.xcd_log2) |
-                                       (blockIdx.x & ((1u << pp.xcd_log2) - 1u))], c);
-        uint32_t total;
-        uint32_t ex = block_excl_scan(c, s_wsum, total);
-        if (threadIdx.x < F) s_base[threadIdx.x] = ex;
-        lds_barrier();
-
-#pragma unroll
-        for (int j = 0; j < PT_ITEMS; ++j)
-            if (dr[j] != 0xffffffffu)
-                s_stage[s_base[dr[j] >> 16] + (dr[j] & 0xffffu)] = make_uint2(w[j][0], w[j][1]);
-        if (base + PT_TILE < end) ok_raw = ld.template issue_tile<2>(base + PT_TILE, end, w);
-        if (threadIdx.x < F) s_delta[threadIdx.x] = run - ex;  // global index = delta + LDS position
-        lds_barrier();
-
-#pragma unroll
-        for (int k = 0; k < PT_ITEMS; ++k) {
-            const uint32_t i = k * PT_THREADS + threadIdx.x;
-            if (i < total) {
-                const uint2    v = s_stage[i];
-                const uint32_t g = s_delta[pass_digit(pp, v.x, mask)] + i;
-                if constexpr (BLK_OUT) {  // (see BlockedLoader)
-                    uint32_t* o = reinterpret_cast<uint32_t*>(out) + BlockedLoader::key_at(g);
-                    o[0] = v.x;
-                    o[BlockedLoader::BLK] = v.y;
-                } else {
-                    out[g] = v;
-                }
-                if (pp.side_out) pp.side_out[g] = (uint16_t)((v.x >> pp.next_shift) & pp.next_mask);
-            }
-        }
-        // no barrier: the next tile passes two barriers before it overwrites s_stage / s_delta
-    }
+    constexpr bool       SPEC = false;
+    constexpr SpecParams sp{};
+#include "rj_pass_scatter_packed.inc"
+}
+// (the speculative first pass: see k_spec_scatter)
+template <class Loader, bool BLK_OUT>
+__global__ __launch_bounds__(PT_THREADS) void k_spec_scatter_packed(Loader ld, PassParams pp, uint2* out, SpecParams sp) {
+    constexpr bool SPEC = true;
+#include "rj_pass_scatter_packed.inc"
 }
 
 // ============================================================= heavy task list
@@ -1259,6 +1166,25 @@ void launch_pass_hist_src(const Launch& L, const TupleSrc& src, int key_words, c
     }
 }
 
+void launch_pass_sample_src(const Launch& L, const TupleSrc& src, int key_words, const PassParams& pp,
+                            const SpecParams& sp, uint32_t n_groups) {
+    if (!n_groups) return;
+    if (key_words == 1)
+        RJ_KLAUNCH(L, "pass1_sample", (k_pass_sample<1>), n_groups, PT_THREADS, src, pp, sp);
+    else
+        RJ_KLAUNCH(L, "pass1_sample", (k_pass_sample<2>), n_groups, PT_THREADS, src, pp, sp);
+}
+
+void launch_spec_caps(const Launch& L, const uint32_t* sample, uint32_t nbins, uint32_t sample_log2, float z,
+                      uint32_t cap_max, uint32_t* start, uint32_t* limit, unsigned long long* cursor) {
+    RJ_KLAUNCH(L, "spec_caps", k_spec_caps, 1, 1024, sample, nbins, sample_log2, z, cap_max, start, limit, cursor);
+}
+
+void launch_spec_close(const Launch& L, const unsigned long long* cursor, const uint32_t* start, const uint32_t* limit,
+                       uint32_t F, uint32_t* seg_end, uint32_t* oseg_off) {
+    RJ_KLAUNCH(L, "spec_close", k_spec_close, 1, PT_MAXF, cursor, start, limit, F, seg_end, oseg_off);
+}
+
 void launch_fine_hist_src(const Launch& L, const TupleSrc& src, int key_words, uint32_t shift,
                           uint32_t b1, uint32_t b2, uint32_t grid, uint32_t* fine, uint32_t xcd_tpg,
                           uint32_t* coarse_x) {
@@ -1299,17 +1225,23 @@ void launch_scan_fine(const Launch& L, const uint32_t* fine, uint32_t F1, uint32
 // (carries of two or more words: the last two travel as one array of 8-byte pairs)
 template <int KW, int CW, int WIDE = WIDE_NONE>
 static void scatter_src_t(const Launch& L, const TupleSrc& src, const PassParams& pp,
-                          uint32_t n_groups, const Words& out) {
+                          uint32_t n_groups, const Words& out, const SpecParams* spec) {
     SrcLoader<KW, CW, WIDE> ld{src};
+    if (spec) {
+        RJ_KLAUNCH(L, "pass1_scatter", (k_spec_scatter<KW + CW, SrcLoader<KW, CW, WIDE>, (CW >= 2 ? KW + CW - 2 : -1)>),
+                   n_groups, PT_THREADS, ld, pp, out, *spec);
+        return;
+    }
     RJ_KLAUNCH(L, "pass1_scatter", (k_pass_scatter<KW + CW, SrcLoader<KW, CW, WIDE>, (CW >= 2 ? KW + CW - 2 : -1), false>),
                n_groups, PT_THREADS, ld, pp, out);
 }
 
 void launch_pass_scatter_src(const Launch& L, const TupleSrc& src, int key_words, int carry_words,
-                             const PassParams& pp, uint32_t n_groups, const Words& out, bool aos3) {
+                             const PassParams& pp, uint32_t n_groups, const Words& out, bool aos3, const SpecParams* spec) {
     if (!n_groups) return;
     const int wide = src.carry_mode == CARRY_WIDE ? src.wide : WIDE_NONE;
     if (aos3) {
+        if (spec) launch_failed("pass1_scatter", "no speculative kernel writes 12-byte tuples", true);
         if (key_words != 1 || carry_words != 2) launch_failed("pass1_scatter", "12-byte tuples need KW=1, CW=2", true);
         if (wide == WIDE_32S) {
             SrcLoader<1, 2, WIDE_32S> ld{src};
@@ -1322,17 +1254,17 @@ void launch_pass_scatter_src(const Launch& L, const TupleSrc& src, int key_words
     }
     if (wide != WIDE_NONE) {
         switch (key_words * 100 + carry_words * 10 + wide) {
-        case 121: scatter_src_t<1, 2, WIDE_32S>(L, src, pp, n_groups, out); break;
-        case 131: scatter_src_t<1, 3, WIDE_32S>(L, src, pp, n_groups, out); break;
-        case 132: scatter_src_t<1, 3, WIDE_64_32>(L, src, pp, n_groups, out); break;
-        case 221: scatter_src_t<2, 2, WIDE_32S>(L, src, pp, n_groups, out); break;
+        case 121: scatter_src_t<1, 2, WIDE_32S>(L, src, pp, n_groups, out, spec); break;
+        case 131: scatter_src_t<1, 3, WIDE_32S>(L, src, pp, n_groups, out, spec); break;
+        case 132: scatter_src_t<1, 3, WIDE_64_32>(L, src, pp, n_groups, out, spec); break;
+        case 221: scatter_src_t<2, 2, WIDE_32S>(L, src, pp, n_groups, out, spec); break;
         default: launch_failed("pass1_scatter", "no kernel for this wide carry layout", true);
         }
         return;
     }
     for_shape("pass1_scatter", key_words, carry_words, [&](auto KW, auto CW) {
         if constexpr (CW <= 2)  // (three carry words travel only as a wide carry, above)
-            scatter_src_t<KW, CW>(L, src, pp, n_groups, out);
+            scatter_src_t<KW, CW>(L, src, pp, n_groups, out, spec);
         else
             launch_failed("pass1_scatter", "no kernel for this key/carry word count", true);
     });
@@ -1407,9 +1339,18 @@ void launch_pass_hist_packed(const Launch& L, const uint32_t* in_pairs, const Pa
 }
 
 void launch_pass_scatter_src_packed(const Launch& L, const TupleSrc& src, const PassParams& pp,
-                                    uint32_t n_groups, uint32_t* out_pairs, bool blocked_out) {
+                                    uint32_t n_groups, uint32_t* out_pairs, bool blocked_out, const SpecParams* spec) {
     if (!n_groups) return;
     SrcLoader<1, 1> ld{src};
+    if (spec) {
+        if (blocked_out)
+            RJ_KLAUNCH(L, "pass1_scatter", (k_spec_scatter_packed<SrcLoader<1, 1>, true>), n_groups, PT_THREADS, ld,
+                       pp, reinterpret_cast<uint2*>(out_pairs), *spec);
+        else
+            RJ_KLAUNCH(L, "pass1_scatter", (k_spec_scatter_packed<SrcLoader<1, 1>, false>), n_groups, PT_THREADS, ld,
+                       pp, reinterpret_cast<uint2*>(out_pairs), *spec);
+        return;
+    }
     if (blocked_out)
         RJ_KLAUNCH(L, "pass1_scatter", (k_pass_scatter_packed<SrcLoader<1, 1>, true>), n_groups, PT_THREADS, ld,
                    pp, reinterpret_cast<uint2*>(out_pairs));
