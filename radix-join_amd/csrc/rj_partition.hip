@@ -770,8 +770,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_hist(Loader ld, PassParams 
 // rows that the workgroups with g & 7 == x will scatter.  The slice's place inside its tile moves with the tile
 // index by 7 slices (an odd number: every place comes up before one repeats), so that data with a fixed period
 // does not meet the sample at the same phase in every tile.  NULL keys, rows behind the relation's end and
-// hashing are the scatter's (SrcLoader::drop_invalid / hash_keys).  A partial last tile is sampled from its
-// first rows on.
+// hashing are the scatter's (SrcLoader::drop_invalid / hash_keys).  In a partial last tile the slice ends with the
+// tile at the latest (its place is min(that place, rows - slice)); a tile of no more rows than a slice is read whole.
 static_assert((PT_TILE & (PT_TILE - 1)) == 0, "a tile's sample slice is a power-of-two fraction of it");
 template <int KW>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_sample(TupleSrc s, PassParams pp, SpecParams sp) {

@@ -65,11 +65,11 @@ SHAPES = {
 EXACT_HIST = "k_pass_hist<SrcLoader<1,0,0>>"
 
 
-def context(env):
+def context(env, radix_bits=RADIX_BITS):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)  # read once, when the context is created
     try:
-        return capi.Context(radix_bits=RADIX_BITS)
+        return capi.Context(radix_bits=radix_bits)
     finally:
         for k, v in old.items():
             if v is None:

@@ -1,6 +1,7 @@
 """The kernel handles compiled into librj.so (tests/_elfsyms.py, no GPU): every kernel family of
 the join path is there, the compact names agree with c++filt, and the kernel matrix
-(test_gpu_kernel_matrix.py) names only instantiations that exist and covers all of them."""
+(test_gpu_kernel_matrix.py) names only instantiations that exist and covers all of them; so does the table of the
+speculative first pass (test_gpu_spec_matrix.py) for its three families."""
 import os
 import shutil
 
@@ -8,6 +9,7 @@ import pytest
 
 import _elfsyms
 import test_gpu_kernel_matrix as km
+import test_gpu_spec_matrix as sm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "radix-join_amd", "librj.so")
@@ -63,3 +65,25 @@ def test_matrix_rows_cover_every_compiled_instantiation(handles):
     named = {e for c in km.CASES for e in c.expect}
     assert not scope - named - set(km.UNREACHABLE), sorted(scope - named - set(km.UNREACHABLE))
     assert not named & set(km.UNREACHABLE)
+
+
+def test_speculative_matrix_names_exactly_the_compiled_instantiations(handles):
+    """The same two checks for the speculative first pass (test_gpu_spec_matrix.py): every name a row expects is
+    compiled, and every compiled k_pass_sample / k_spec_scatter / k_spec_scatter_packed is named by some row.  All of
+    them are reachable: there is no UNREACHABLE list."""
+    assert sm.FAMILIES == ("k_pass_sample", "k_spec_scatter", "k_spec_scatter_packed")
+    assert not hasattr(sm, "UNREACHABLE")
+    compiled = set(map(_elfsyms.short_name, handles))
+    for c in sm.CASES:
+        for name in c.expect:
+            assert name in compiled, f"row {c.id} expects {name}, which librj.so does not compile"
+        for name in c.expect[:-1]:
+            assert sm.exact_of(name) in compiled, f"row {c.id}: no exact kernel {sm.exact_of(name)}"
+    for name in sm.VARCHAR_EXPECT:
+        assert name in compiled, f"the VARCHAR row expects {name}, which librj.so does not compile"
+    scope = {n for n in compiled if n.split("<")[0] in sm.FAMILIES}
+    assert scope == set(sm.compiled_in_scope())
+    # (without the VARCHAR row: it repeats a shape, a table row must name it too)
+    named = {e for c in sm.CASES for e in c.expect}
+    assert not scope - named, sorted(scope - named)
+    assert len(scope) == 14
