@@ -36,6 +36,10 @@ void Tuning::from_env() {
     spec_min_rows = env_int("RJ_TUNE_SPEC_MIN_ROWS", spec_min_rows);
     spec_sample = std::min(5, std::max(1, env_int("RJ_TUNE_SPEC_SAMPLE", spec_sample)));
     spec_z = std::max(0, env_int("RJ_TUNE_SPEC_Z", spec_z));
+    spec_p2 = env_int("RJ_TUNE_SPEC_P2", spec_p2);
+    spec2_min_rows = env_int("RJ_TUNE_SPEC2_MIN_ROWS", spec2_min_rows);
+    spec2_sample = std::min(4, std::max(1, env_int("RJ_TUNE_SPEC2_SAMPLE", spec2_sample)));
+    spec2_z = std::max(0, env_int("RJ_TUNE_SPEC2_Z", spec2_z));
     bcast = env_int("RJ_TUNE_BCAST", bcast);
     diag = env_int("RJ_DIAG", diag);
     varchar_dev_rows = env_int("RJ_TUNE_VARCHAR_DEV", varchar_dev_rows);

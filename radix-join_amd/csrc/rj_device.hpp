@@ -175,6 +175,25 @@ struct SpecParams {
                                      // a run that did not fit is written (sink + its offset inside the tile)
     uint32_t            sample_log2; // k_pass_sample: PT_TILE >> sample_log2 rows of every tile are counted
 };
+// ---- Speculative LAST pass of a two-pass inner join (no second histogram: DESIGN.md §4) ---------
+// The same estimate / check / repeat, one level down: the final partitions (up to 2^18 of them) get their room
+// from a sample of the first pass' output (k_last_sample, k_last_caps), the scatter (k_last_scatter*) reserves
+// from one cursor per final partition (xcd_log2 = 0) and checks the run's end against the partition's limit, and
+// k_last_close leaves end[q] = min(position, limit[q]) next to begin[q] ({begin, end} pairs: JoinParams::off_pairs):
+// the join reads [begin[q], end[q]) and never the room behind it.  (A 32-bit cursor and a limit array instead of SpecParams' {position, room} words: the scatter keeps
+// a group's limits in the LDS and, per digit thread, the registers of the exact kernel.  The fields the shared
+// scatter bodies name in their first-pass branch are here too, unused.)
+struct LastParams {
+    unsigned long long* cursor;      // NEVER READ OR SET.  It is here only because the shared bodies' first-pass branch,
+                                     // `res = atomicAdd(&sp.cursor[at], ...)` (rj_pass_scatter.inc and
+                                     // rj_pass_scatter_packed.inc, the `else if constexpr (SPEC)` arm of the reservation),
+                                     // is discarded in the k_last_* kernels but must still be well-formed with this struct
+    uint32_t*           flag;        // OR 1: some run did not fit, the output is to be thrown away
+    uint32_t            sink;        // first tuple of the PT_TILE spare tuples behind the partitions
+    uint32_t            sample_log2; // k_last_sample: PT_TILE >> sample_log2 keys of every tile are counted
+    uint32_t*           cursor32;    // [bins] next free position of final partition (oseg, d2)
+    const uint32_t*     limit;       // [bins] begin + capacity
+};
 
 // ---- Build/probe -------------------------------------------------------------
 #ifndef RJ_JN_THREADS
@@ -238,8 +257,8 @@ struct OutStream {
 
 struct JoinParams {
     Words           R, S;
-    const uint32_t* offR;   // [NP+1]
-    const uint32_t* offS;   // [NP+1]
+    const uint32_t* offR;   // [NP+1] neighbouring offsets, or [2 NP] {begin, end} pairs: see off_pairs
+    const uint32_t* offS;   // (the same)
     uint32_t        NP;
     uint32_t        radix_bits;  // low bits of word 0 shared by a partition's tuples
     uint32_t        n_pass;      // radix passes and their bit widths: partition index
@@ -252,7 +271,10 @@ struct JoinParams {
     uint32_t        heavy_grid;  // the first heavy_grid workgroups of the launch take heavy tasks
     int32_t         packR, packS; // R.w[0] / S.w[0] is an array of {hashed key, carry} pairs
     int32_t         aosR, aosS;   // R.w[0] / S.w[0] is an array of 12-byte {hashed key, carry lo, carry hi}
-    int32_t         pad;
+    // Partition q holds tuples [off[q << sh], off[(q << sh) + 1]).  sh = 0: exact partitions, one behind the other
+    // (off[NP + 1]).  sh = 1: a speculative last pass (LastParams) left unused room behind each partition and
+    // off[2 NP] holds {begin, end} pairs.  Bit 0: offR's sh, bit 1: offS's (a side that fell back is exact again)
+    uint32_t        off_pairs;
     unsigned long long* diag;    // phase cycle counters (RJ_DIAG=1 only), else nullptr
 };
 

@@ -85,6 +85,11 @@ struct Parted {
     uint64_t n_tuples = 0;        // tuples that went in (NULL keys are dropped on the way: an upper bound)
     bool     spec = false;        // the first pass ran without its histogram (partition(): spec_flag); the caller's flag word tells
                                   // whether everything found room — if not, what is in here is in bounds but not the partition
+    // Partition q holds tuples [off[q << off_shift], off[(q << off_shift) + 1]).  Exact partitions lie one behind the
+    // other (off_shift = 0, off = u32[NP + 1]); a speculative LAST pass (spec2, only behind a speculative first one
+    // and under the same flag word) leaves unused room behind each: off = u32[2 NP], {begin, end} pairs
+    uint32_t off_shift = 0;
+    bool     spec2 = false;
 };
 
 // Tuples that already sit in the partition layout (hashed word arrays, a pair array for a
@@ -493,13 +498,15 @@ class Exec {
     // `external`: caller-owned arrays that receive the output of a single-pass partition
     // spec_flag (optional, device, zeroed by the caller): the call may run its first pass speculatively (see `spec`
     // below); the word is then set on the device if the result has to be thrown away, Parted::spec says it was tried
+    // spec2_ok: ... and, behind a speculative first pass, its last pass too (only a caller whose kernels read a partition
+    // through Parted::off_shift: the inner join)
     // after_offsets (optional): called once the FIRST pass' partition offsets are enqueued to be
     // computed, before its scatter is enqueued — a caller that needs the counts on the host
     // (the sharded join's stage A) copies them out ahead of the scatter.
     Parted partition(const TupleSrc* srcp, const WordSrc* ws, int KW, int CW, uint32_t bits,
                      uint32_t shift0 = 0, bool single_pass = false, const Words* external = nullptr,
                      const std::function<void(const uint32_t*)>* after_offsets = nullptr,
-                     const PassShape* shape = nullptr, uint32_t* spec_flag = nullptr) {
+                     const PassShape* shape = nullptr, uint32_t* spec_flag = nullptr, bool spec2_ok = false) {
         Parted P;
         const bool preseg = shape && shape->nseg > 0;
         P.NW = KW + CW;
@@ -546,10 +553,6 @@ class Exec {
         const bool mid_side = aos_mid && !fine && ctx->tune.aos_mid != 3;
         BufP  A[MAX_WORDS], B[MAX_WORDS], AOS, MID[2], SIDE[2];
         Words wa{}, wb{}, waos{};
-        if (P.aos3) {
-            AOS = ctx->buf(std::max<uint64_t>(n, 1) * 12);
-            waos.w[0] = AOS->as<uint32_t>();
-        }
         if (aos_mid) {
             for (uint32_t k = 0; k < std::min<uint32_t>(passes - 1, 2); ++k) {
                 MID[k] = ctx->buf(std::max<uint64_t>(n, 1) * 12);
@@ -592,6 +595,27 @@ class Exec {
                           spec_cap_max < (uint64_t(1) << 31) && n < (uint64_t(1) << 31);  // (... and the room left, which goes down by at most n, stays a signed 32-bit number)
         P.spec = spec;
         const uint64_t n_first_out = spec ? spec_cap_max + PT_TILE : n;  // tuples the first pass' output arrays hold
+        // The speculative last pass (k_last_*): the same once more for the B = 2^bits final partitions,
+        // sampled from the first pass' output — at most a slice per tile of the second pass (a partial one at the end
+        // of each of its 8 << pbits[0] input segments) and never more than n positions — with knobs of its own.
+        // 12-byte-tuple plans and packed plans with blocked pairs between the passes have kernels for it.
+        const uint32_t spec2_s = (uint32_t)ctx->tune.spec2_sample;
+        const double   spec2_z = ctx->tune.spec2_z / 10.0;
+        uint64_t       spec2_cap_max = 0;
+        {
+            const double Bn = std::ldexp(1.0, (int)bits);
+            const double C = std::min((double)n, ((double)(n / PT_TILE) + (double)((uint64_t)8 << pbits[0])) * (double)(PT_TILE >> spec2_s));
+            const double bound = std::ldexp(C + spec2_z * std::sqrt(Bn * (C + Bn)) + 0.5 * spec2_z * spec2_z * Bn, (int)spec2_s) + 32.0 * Bn;
+            spec2_cap_max = bound < 4.0e9 ? (((uint64_t)std::ceil(bound) + 255u) & ~(uint64_t)255u) : ~(uint64_t)0 >> 1;
+        }
+        const bool spec2 = spec && spec2_ok && ctx->tune.spec_p2 != 0 && n >= (uint64_t)ctx->tune.spec2_min_rows &&
+                           (P.aos3 || (P.packed && ctx->tune.blocked_mid != 0)) && spec2_cap_max < (uint64_t(1) << 31);
+        P.spec2 = spec2;
+        const uint64_t n_last_out = spec2 ? spec2_cap_max + PT_TILE : n;  // tuples the last pass' output array holds
+        if (P.aos3) {
+            AOS = ctx->buf(std::max<uint64_t>(n_last_out, 1) * 12);
+            waos.w[0] = AOS->as<uint32_t>();
+        }
         for (int a = 0; a < (P.packed ? 1 : P.NW); ++a) {
             if (pair_word >= 0 && a == pair_word + 1) continue;
             const uint64_t wbytes = (P.packed || a == pair_word) ? 8 : 4;
@@ -604,7 +628,7 @@ class Exec {
             A[a] = ctx->buf(n_first_out * wbytes + 2048);
             wa.w[a] = A[a]->as<uint32_t>();
             if (passes > (P.aos3 ? 2u : 1u)) {
-                B[a] = ctx->buf(n * wbytes + 2048);
+                B[a] = ctx->buf(n_last_out * wbytes + 2048);
                 wb.w[a] = B[a]->as<uint32_t>();
             }
         }
@@ -613,6 +637,7 @@ class Exec {
         Words    cur = ws ? ws->w : Words{}, nxt = (P.aos3 && passes == 1) ? waos : wa;
         bool     cur_is_a = false;
         BufP       fine_off, fine_cursor, coarse_off, coarse_cursor;
+        BufP       last_limit, last_seg_sum, last_grp;  // per final partition of a speculative last pass: limit = begin + capacity, [begin, end) holds tuples
         BufP       spec_start, spec_limit, spec_end;  // per sub-range of a speculative first pass' output: [start, end) holds tuples, limit = start + capacity
         // tiles per group of the first pass (the fine histogram must know it: see fine_xcd)
         uint32_t tpg_first = tiles_per_group(n, 4096);
@@ -715,6 +740,7 @@ class Exec {
             }
             BufP off, hist, cursor;  // this pass' partition offsets, bin totals, write cursors
             SpecParams sp{};
+            LastParams lp{};
             if (p == 0 && spec) {
                 // sample -> capacities, {position, room} cursors; the partition offsets come from where the cursors
                 // stand once the scatter is through (launch_spec_close below)
@@ -735,6 +761,32 @@ class Exec {
                 launch_pass_sample_src(L, src, KW, pp, sp, n_groups);
                 launch_spec_caps(L, pp.hist, nb, spec_s, (float)spec_z, (uint32_t)spec_cap_max, spec_start->as<uint32_t>(),
                                  spec_limit->as<uint32_t>(), sp.cursor);
+            } else if (p == 1 && spec2) {
+                // sample of the first pass' output -> capacities; `off` = where the final partitions begin
+                const uint32_t nb = (uint32_t)bins;
+                hist = ctx->buf((uint64_t)nb * 4);
+                off = ctx->buf((uint64_t)nb * 8);  // {begin, end} pairs
+                cursor = ctx->buf((uint64_t)nb * 4);
+                last_limit = ctx->buf((uint64_t)nb * 4);
+                last_seg_sum = ctx->buf((uint64_t)n_oseg * 8);
+                RJ_HIP(hipMemsetAsync(hist->p, 0, (uint64_t)nb * 4, ctx->stream));
+                pp.hist = hist->as<uint32_t>();
+                lp.cursor32 = cursor->as<uint32_t>();
+                lp.limit = last_limit->as<uint32_t>();
+                lp.flag = spec_flag;
+                lp.sink = (uint32_t)spec2_cap_max;
+                lp.sample_log2 = spec2_s;
+                // (the sample's own groups, eight tiles each whatever the scatter's are: a group of the scatter's two
+                // tiles would flush its 512 bins for 4096 sampled keys, as many global adds as the exact histogram's)
+                PassParams ps = pp;
+                ps.tiles_per_group = 8;
+                const uint64_t gts = (uint64_t)ps.tiles_per_group * PT_TILE;
+                last_grp = ctx->buf(((uint64_t)nseg_in + 1) * 4);
+                launch_group_table(L, pp.seg_off, nseg_in, (uint32_t)gts, last_grp->as<uint32_t>(), in_end);
+                ps.grp_start = last_grp->as<uint32_t>();
+                launch_last_sample(L, cur.w[0], P.packed, ps, lp, (uint32_t)(n / gts + nseg_in) + (pp.xcd_remap ? 8u : 0u));
+                launch_last_caps(L, pp.hist, n_oseg, F, spec2_s, (float)spec2_z, (uint32_t)spec2_cap_max,
+                                 last_seg_sum->as<unsigned long long>(), off->as<uint32_t>(), last_limit->as<uint32_t>(), lp.cursor32);
             } else if (fine) {  // offsets and cursors of both passes came out of the fine histogram
                 off = p == 0 ? coarse_off : fine_off;
                 cursor = p == 0 ? coarse_cursor : fine_cursor;
@@ -823,7 +875,15 @@ class Exec {
                 chunk_ev.make();
                 RJ_HIP(hipEventRecord(chunk_ev.e, ctx->stream));
             }
-            if (aos_mid) {
+            if (p == 1 && spec2) {
+                if (P.packed)
+                    launch_last_scatter_blocked(L, cur.w[0], pp, n_groups, nxt.w[0], lp);
+                else
+                    launch_last_scatter_dense(L, cur, pp, n_groups, nxt, lp);
+                launch_last_close(L, lp.cursor32, last_limit->as<uint32_t>(), (uint32_t)bins, off->as<uint32_t>());
+                if (ctx->tune.diag >= 1) spec_report(cursor, last_limit, off, (uint32_t)bins, n, n_last_out, 2);
+                P.off_shift = 1;
+            } else if (aos_mid) {
                 const bool last = p + 1 == passes;
                 Words      o{};
                 o.w[0] = last ? waos.w[0] : MID[p % 2]->as<uint32_t>();
@@ -861,7 +921,7 @@ class Exec {
             if (p == 0 && spec) {
                 launch_spec_close(L, sp.cursor, spec_start->as<uint32_t>(), spec_limit->as<uint32_t>(), F, spec_end->as<uint32_t>(),
                                   off->as<uint32_t>());
-                if (ctx->tune.diag >= 1) spec_report(cursor, spec_limit, spec_start, (uint32_t)bins << 3, n, n_first_out);
+                if (ctx->tune.diag >= 1) spec_report(cursor, spec_limit, spec_start, (uint32_t)bins << 3, n, n_first_out, 1);
             }
             seg_off = off;
             nseg = (uint32_t)bins;
@@ -887,12 +947,19 @@ class Exec {
     }
 
     // RJ_DIAG >= 1: how full the sub-ranges of a speculative first pass came out (waits for the stream)
-    void spec_report(const BufP& cursor, const BufP& limit, const BufP& start, uint32_t nb, uint64_t n, uint64_t n_alloc) {
-        std::vector<unsigned long long> c(nb);
+    void spec_report(const BufP& cursor, const BufP& limit, const BufP& start, uint32_t nb, uint64_t n, uint64_t n_alloc, int pass) {
+        std::vector<unsigned long long> c(nb);  // (pass 1: {position, room} words; pass 2: 32-bit positions)
         std::vector<uint32_t>           lim(nb), st(nb);
-        read_back(c.data(), cursor->p, (size_t)nb * 8);
+        if (pass == 1) {
+            read_back(c.data(), cursor->p, (size_t)nb * 8);
+            read_back(st.data(), start->p, (size_t)nb * 4);
+        } else {  // (`start`: {begin, end} pairs)
+            std::vector<uint32_t> c32(nb), be(2 * (size_t)nb);
+            read_back(c32.data(), cursor->p, (size_t)nb * 4);
+            read_back(be.data(), start->p, (size_t)nb * 8);
+            for (uint32_t i = 0; i < nb; ++i) c[i] = c32[i], st[i] = be[2 * (size_t)i];
+        }
         read_back(lim.data(), limit->p, (size_t)nb * 4);
-        read_back(st.data(), start->p, (size_t)nb * 4);
         double   worst = 0;
         uint32_t over = 0;
         for (uint32_t i = 0; i < nb; ++i) {
@@ -900,8 +967,8 @@ class Exec {
             if (used > room) ++over;
             if (room > 0) worst = std::max(worst, used / room);
         }
-        fprintf(stderr, "[rj diag] speculative pass 1: rows=%llu sub-ranges=%u fullest=%.4f of its capacity, over=%u, room for %llu tuples (+%.3f)\n",
-                (unsigned long long)n, nb, worst, over, (unsigned long long)n_alloc, (double)n_alloc / (double)std::max<uint64_t>(n, 1) - 1.0);
+        fprintf(stderr, "[rj diag] speculative pass %d: rows=%llu sub-ranges=%u fullest=%.4f of its capacity, over=%u, room for %llu tuples (+%.3f)\n",
+                pass, (unsigned long long)n, nb, worst, over, (unsigned long long)n_alloc, (double)n_alloc / (double)std::max<uint64_t>(n, 1) - 1.0);
     }
 
     // ---------------------------------------------------------------- join
@@ -1189,15 +1256,16 @@ class Exec {
     // counters (optional, from zeroed_counters()): either side's first pass may run speculatively (partition():
     // spec_flag), with the node's two flag words; emit_with_retry then sees them with the row count, and
     // repartition_exact() is what its caller does about a flag that is set
-    CoParts partition_sides(JoinState& st, const JoinSpec& js, uint32_t bits, const BufP* counters = nullptr) {
+    // spec2_ok: the node's kernels read a partition through Parted::off_shift, so the last pass may be speculative as well
+    CoParts partition_sides(JoinState& st, const JoinSpec& js, uint32_t bits, const BufP* counters = nullptr, bool spec2_ok = false) {
         CoParts        cp;
         const TupleSrc sb = make_src(st, st.bs(), js), sp = make_src(st, st.ps(), js);
         uint32_t*      fl = counters ? (*counters)->as<uint32_t>() + 4 : nullptr;
-        cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits, 0, false, nullptr, nullptr, nullptr, fl);
-        cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits, 0, false, nullptr, nullptr, nullptr, fl ? fl + 1 : nullptr);
+        cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits, 0, false, nullptr, nullptr, nullptr, fl, spec2_ok);
+        cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits, 0, false, nullptr, nullptr, nullptr, fl ? fl + 1 : nullptr, spec2_ok);
         return cp;
     }
-    // A speculative first pass found a sub-range too small (flag_b / flag_p: on which side).  What the node has
+    // A speculative pass (the first, or an inner join's last) found a sub-range too small (flag_b / flag_p: on which side).  What the node has
     // produced since is thrown away: that side is partitioned again, with its histogram, the heavy tasks are listed
     // again (which zeroes the row cursor) and the flags are cleared.  The caller then points its kernel parameters
     // at the new partitions and runs the probe again.
@@ -1206,12 +1274,12 @@ class Exec {
                            bool flag_p) {
         ++spec_fallbacks;
         if (ctx->tune.diag >= 1)
-            fprintf(stderr, "[rj diag] %s: speculative pass 1 overflowed (build side %d, probe side %d): exact partition again (fallback %d of this plan)\n",
+            fprintf(stderr, "[rj diag] %s: a speculative pass overflowed (build side %d, probe side %d): exact partition again (fallback %d of this plan)\n",
                     st.kind->name, (int)flag_b, (int)flag_p, spec_fallbacks);
         if (flag_b) {
             const TupleSrc sb = make_src(st, st.bs(), js);
             cp.B = Parted();  // (its arrays go back to the block cache first)
-            cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits);
+            cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits);  // (no flag word: both passes exact)
         }
         if (flag_p) {
             const TupleSrc sp = make_src(st, st.ps(), js);
@@ -1234,7 +1302,7 @@ class Exec {
         return cp;
     }
     // [0..7] out cursor (u64), [8..11] n_heavy, [12..15] the aggregation's overflow flag, [16..19] / [20..23] a join's
-    // build / probe side: its speculative first pass did not fit (SpecParams::flag)
+    // build / probe side: a speculative pass of it (the first, or the last) did not fit (SpecParams::flag)
     static constexpr size_t COUNTER_BYTES = 32;
     BufP zeroed_counters() {
         BufP counters = ctx->buf(COUNTER_BYTES);
@@ -1344,7 +1412,9 @@ class Exec {
                     (unsigned long long)bs.rel->n, (unsigned long long)ps.rel->n, bits, bs.CW, ps.CW);
         if (broadcast_form(st, js)) return join_finish(st, js, nullptr, bits, root_res);
         BufP    counters = zeroed_counters();
-        CoParts cp = partition_sides(st, js, bits, &counters);
+        // (the last pass may be speculative too where k_join reads {begin, end} pairs: rj_join.hip, PAIRS)
+        const bool pairs = st.KW == 1 && bs.CW >= 1 && bs.CW <= 2 && ps.CW >= 1 && ps.CW <= 2;
+        CoParts cp = partition_sides(st, js, bits, &counters, pairs);
         return join_finish(st, js, &cp, bits, root_res, counters);
     }
 
@@ -1387,6 +1457,9 @@ class Exec {
             jp.aosS = PP.aos3 ? 1 : 0;
             jp.offR = PB.off->as<uint32_t>();
             jp.offS = PP.off->as<uint32_t>();
+            jp.off_pairs = PB.off_shift | (PP.off_shift << 1);
+            if (jp.off_pairs && !(KW == 1 && bs.CW >= 1 && bs.CW <= 2 && ps.CW >= 1 && ps.CW <= 2))
+                throw_fmt(RJ_ERR_DEVICE, "join: {begin, end} pairs for a shape whose kernel does not read them");
             jp.n_pass = (uint32_t)PB.pbits.size();
             for (size_t i = 0; i < PB.pbits.size() && i < 4; ++i) jp.pass_bits[i] = PB.pbits[i];
             jp.key = key;
@@ -3002,7 +3075,7 @@ class Exec {
                                    const BufP& counters, uint32_t max_tasks) {
         RJ_HIP(hipMemsetAsync(counters->p, 0, 16, ctx->stream));
         launch_heavy_tasks(L, PB.off->as<uint32_t>(), PP.off->as<uint32_t>(), PB.NP,
-                           tasks->as<uint32_t>(), counters->as<uint32_t>() + 2, max_tasks);
+                           tasks->as<uint32_t>(), counters->as<uint32_t>() + 2, max_tasks, PB.off_shift | (PP.off_shift << 1));
     }
 
     // VARCHAR at the root: row ids -> host, strings gathered from the base table's

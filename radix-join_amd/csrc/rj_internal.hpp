@@ -222,6 +222,12 @@ struct Tuning {
     int spec_min_rows = 40 << 20;  // RJ_TUNE_SPEC_MIN_ROWS: ... for passes over at least this many tuples (XCD placement must be on for them too)
     int spec_sample = 5;  // RJ_TUNE_SPEC_SAMPLE: log2 of the sampling rate's inverse (1 .. 5: of every tile of 16384 rows, 16384 >> it)
     int spec_z = 60;      // RJ_TUNE_SPEC_Z: the safety margin's normal quantile z, in tenths (0: no margin at all — tests)
+    // ... and the last pass of an inner join's such plans without its histogram either (knobs of its own: 2^18 final
+    // partitions instead of 4096 sub-ranges, and the join reads partitions with unused room between them)
+    int spec_p2 = 1;      // RJ_TUNE_SPEC_P2: 0 = never
+    int spec2_min_rows = 40 << 20;  // RJ_TUNE_SPEC2_MIN_ROWS: ... for passes over at least this many tuples (and only behind a speculative first pass)
+    int spec2_sample = 2;  // RJ_TUNE_SPEC2_SAMPLE: log2 of the sampling rate's inverse (1 .. 4: slices of whole 256-key blocks)
+    int spec2_z = 70;      // RJ_TUNE_SPEC2_Z: the margin's normal quantile z, in tenths (2 * 2^18 bins per step: Phi(-7) each)
     int bcast = 1;        // RJ_TUNE_BCAST: broadcast join for build sides that fit one LDS table
     int diag = 0;         // RJ_DIAG: 1 = join phase stamps, 2 = host-side timings on stderr
     int varchar_dev_rows = 200000;  // RJ_TUNE_VARCHAR_DEV: root VARCHAR columns of at least this many

@@ -92,6 +92,12 @@ __global__ __launch_bounds__(jn_threads(TG ? 2 : KW + CWR), jn_min_waves(TG ? 2 
     // with a skewed probe side they are the long pole), the others one partition each.
     const bool     heavy_wg = blockIdx.x < jp.heavy_grid;
     const uint32_t wg = heavy_wg ? blockIdx.x : blockIdx.x - jp.heavy_grid;
+    // {begin, end} pairs (JoinParams::off_pairs) reach only the shapes whose sides a speculative last pass can
+    // write: one key word and a carry of one or two words on BOTH sides (Exec::join_core).  Every other
+    // instantiation reads neighbouring offsets as it always did — the pipelined kernels of 3- and 4-word tables,
+    // which share one load between a partition's end and its successor's begin, ran 2–7 % slower with the
+    // shift (profiles/spec_pass2_ab.log) — and is compiled to the code it had.
+    constexpr bool PAIRS = KW == 1 && CWR >= 1 && CWR <= 2 && CWS >= 1 && CWS <= 2;
     auto get_task = [&](uint32_t k) {
         Task t{0, 0, 0, 0, 0, false};
         if (heavy_wg) {
@@ -99,18 +105,21 @@ __global__ __launch_bounds__(jn_threads(TG ? 2 : KW + CWR), jn_min_waves(TG ? 2 
                 t.q = jp.heavy_tasks[3 * wg + 0];
                 t.sbeg = jp.heavy_tasks[3 * wg + 1];
                 t.send = jp.heavy_tasks[3 * wg + 2];
-                t.rbeg = jp.offR[t.q];
-                t.rend = jp.offR[t.q + 1];
+                const uint32_t ir = PAIRS ? t.q << (jp.off_pairs & 1u) : t.q;
+                t.rbeg = jp.offR[ir];
+                t.rend = jp.offR[ir + 1];
                 t.active = t.rbeg < t.rend && t.sbeg < t.send;
             }
             return t;
         }
         t.q = wg * PPW + k;
         if (k < (uint32_t)PPW && t.q < jp.NP) {
-            t.rbeg = jp.offR[t.q];
-            t.rend = jp.offR[t.q + 1];
-            t.sbeg = jp.offS[t.q];
-            t.send = jp.offS[t.q + 1];
+            // (neighbouring offsets, or {begin, end} pairs behind a speculative last pass: JoinParams::off_pairs)
+            const uint32_t ir = PAIRS ? t.q << (jp.off_pairs & 1u) : t.q, is = PAIRS ? t.q << (jp.off_pairs >> 1) : t.q;
+            t.rbeg = jp.offR[ir];
+            t.rend = jp.offR[ir + 1];
+            t.sbeg = jp.offS[is];
+            t.send = jp.offS[is + 1];
             // partitions above JN_HEAVY probe tuples are split into tasks (k_heavy_tasks)
             t.active = t.rbeg < t.rend && t.sbeg < t.send && t.send - t.sbeg <= JN_HEAVY;
         }

@@ -159,8 +159,29 @@ void launch_pass_scatter_packed(const Launch& L, const uint32_t* in_pairs, const
                                 uint32_t n_groups, uint32_t* out_pairs);
 
 // ---- the probe partitions above JN_HEAVY tuples, cut into tasks for the build + probe kernels
+// (off_pairs: JoinParams')
 void launch_heavy_tasks(const Launch& L, const uint32_t* offR, const uint32_t* offS, uint32_t NP,
-                        uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks);
+                        uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks, uint32_t off_pairs = 0);
+
+// ---- Speculative LAST pass of a two-pass inner join (rj_device.hpp: SpecParams).  `pp` is the exact second
+// pass' (grid, group table over the input segments, xcd_remap; xcd_log2 = 0), pp.hist the zeroed sample bins,
+// one per final partition.  in_keys: the first pass' key array, or (blocked) its blocked pairs.
+//   sample  -> pp.hist[oseg * F + d2]
+//   caps    -> pairs[2 q] = begin of final partition q (exclusive scan of the capacities), limit[q] = begin + capacity,
+//              cursor[q] = begin; nothing beyond cap_max.  seg_sum: nseg words of scratch
+//   scatter -> 12-byte tuples (dense key array + pair array in) or pairs (blocked pairs in)
+//   close   -> pairs[2 q + 1] = end = min(position, limit[q])
+void launch_last_sample(const Launch& L, const uint32_t* in_keys, bool blocked, const PassParams& pp, const LastParams& sp,
+                        uint32_t n_groups);
+void launch_last_caps(const Launch& L, const uint32_t* sample, uint32_t nseg, uint32_t F, uint32_t sample_log2, float z,
+                      uint32_t cap_max, unsigned long long* seg_sum, uint32_t* pairs, uint32_t* limit,
+                      uint32_t* cursor);
+void launch_last_scatter_dense(const Launch& L, const Words& in, const PassParams& pp, uint32_t n_groups, const Words& out,
+                               const LastParams& sp);
+void launch_last_scatter_blocked(const Launch& L, const uint32_t* in_blocked, const PassParams& pp, uint32_t n_groups,
+                                 uint32_t* out_pairs, const LastParams& sp);
+void launch_last_close(const Launch& L, const uint32_t* cursor, const uint32_t* limit, uint32_t nbins,
+                       uint32_t* pairs);
 
 // ========================================================================================================= rj_join.hip
 // ---- build + probe (replaces reference src/execute.cpp:196-249)

@@ -1048,6 +1048,15 @@ __device__ __forceinline__ uint32_t tile_pos(const uint32_t (&ps)[PT_ITEMS / 2],
     return (j & 1) ? ps[j / 2] >> 16 : ps[j / 2] & 0xffffu;
 }
 
+// (the shared scatter bodies name the last pass' cursor and limit arrays through these, so that their SPEC_LAST
+// branch, which the other kernels discard, is well-formed with either parameter struct.  The SpecParams overloads
+// are never called: a kernel whose `sp` is a SpecParams has SPEC_LAST = false.  The other direction is
+// LastParams::cursor, rj_device.hpp)
+__device__ __forceinline__ uint32_t*       last_cursor(const LastParams& p) { return p.cursor32; }
+__device__ __forceinline__ uint32_t*       last_cursor(const SpecParams&) { return nullptr; }
+__device__ __forceinline__ const uint32_t* last_limit(const LastParams& p) { return p.limit; }
+__device__ __forceinline__ const uint32_t* last_limit(const SpecParams&) { return nullptr; }
+
 template <class L>
 struct is_src_loader : std::false_type {};
 template <int KW, int CW, int WIDE>
@@ -1084,13 +1093,13 @@ struct is_src_loader<SrcLoader<KW, CW, WIDE>> : std::true_type {};
 // rj_pass_scatter.inc, with SPEC as a constant.
 template <int NW, class Loader, int PAIR, bool AOS>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter(Loader ld, PassParams pp, Words out) {
-    constexpr bool       SPEC = false;
+    constexpr bool       SPEC = false, SPEC_LAST = false;
     constexpr SpecParams sp{};
 #include "rj_pass_scatter.inc"
 }
 template <int NW, class Loader, int PAIR>
 __global__ __launch_bounds__(PT_THREADS) void k_spec_scatter(Loader ld, PassParams pp, Words out, SpecParams sp) {
-    constexpr bool SPEC = true, AOS = false;
+    constexpr bool SPEC = true, SPEC_LAST = false, AOS = false;
 #include "rj_pass_scatter.inc"
 }
 
@@ -1102,28 +1111,153 @@ __global__ __launch_bounds__(PT_THREADS) void k_spec_scatter(Loader ld, PassPara
 // rate follows; it also needs one staging round and two barriers less per tile.
 template <class Loader, bool BLK_OUT = false>
 __global__ __launch_bounds__(PT_THREADS) void k_pass_scatter_packed(Loader ld, PassParams pp, uint2* out) {
-    constexpr bool       SPEC = false;
+    constexpr bool       SPEC = false, SPEC_LAST = false;
     constexpr SpecParams sp{};
 #include "rj_pass_scatter_packed.inc"
 }
 // (the speculative first pass: see k_spec_scatter)
 template <class Loader, bool BLK_OUT>
 __global__ __launch_bounds__(PT_THREADS) void k_spec_scatter_packed(Loader ld, PassParams pp, uint2* out, SpecParams sp) {
-    constexpr bool SPEC = true;
+    constexpr bool SPEC = true, SPEC_LAST = false;
 #include "rj_pass_scatter_packed.inc"
+}
+
+// ================================================== speculative last pass: sample, capacities, scatter, closing
+// (rj_device.hpp: LastParams.  Kernels of their own family names, k_last_*: every exact kernel and every kernel of
+// the speculative first pass keeps its name, its arguments and its machine code.)
+// k_last_sample: k_pass_hist of a later pass — its grid, a group table (of its own, see Exec::partition), xcd_remap
+// and LDS bins — over the input segments a speculative first pass left behind, but of every tile only one slice of PT_TILE >> sample_log2
+// consecutive keys is read, four keys per 16-byte load.  The slice's place moves from tile to tile as in
+// k_pass_sample; in a partial last tile of a segment it ends with the tile at the latest (its place is the
+// largest multiple of four that allows it, so that the loads stay aligned), and a tile of no more rows than a
+// slice is read whole.  Bin (oseg, d2) is sampled from exactly the rows that will be scattered into it: all
+// tuples of an output segment come from its own eight input segments.  A load may reach up to three keys
+// behind the segment's end (never behind the array's: the spare tile follows the sub-ranges); they are masked out.
+__device__ __forceinline__ u32x4a sample_keys4(const DenseLoader& ld, uint32_t g) {
+    return *reinterpret_cast<const u32x4a*>(ld.in.w[0] + g);
+}
+__device__ __forceinline__ u32x4a sample_keys4(const BlockedLoader& ld, uint32_t g) {  // (g % 4 == 0: one block)
+    return *reinterpret_cast<const u32x4a*>(ld.in + BlockedLoader::key_at(g));
+}
+static_assert(BlockedLoader::BLK % 4 == 0, "four consecutive keys of a blocked array share a block");
+template <class Loader>
+__global__ __launch_bounds__(PT_THREADS) void k_last_sample(Loader ld, PassParams pp, LastParams sp) {
+    __shared__ uint32_t s_h[PT_MAXF];
+    uint32_t            seg, begin, end;
+    if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
+    const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
+    for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) s_h[d] = 0;
+    lds_barrier();
+    const uint32_t slog = (uint32_t)__builtin_ctz((unsigned)PT_TILE) - sp.sample_log2, slice = 1u << slog;
+    const uint32_t ntiles = (end - begin + (uint32_t)PT_TILE - 1u) / (uint32_t)PT_TILE;
+    const uint32_t total = ntiles << (slog - 2u);  // units of four consecutive keys
+    constexpr int  U = 4;                          // units a thread has in flight
+    for (uint32_t i0 = threadIdx.x; i0 < total; i0 += U * PT_THREADS) {
+        u32x4a   k[U];
+        uint32_t nv[U];  // keys of the unit that count
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t i = i0 + u * PT_THREADS, ic = min(i, total - 1u);
+            const uint32_t t = ic >> (slog - 2u), r = (ic & ((slice >> 2) - 1u)) << 2;
+            const uint32_t tb = begin + t * (uint32_t)PT_TILE, rows = min((uint32_t)PT_TILE, end - tb);
+            const uint32_t rot = ((tb / (uint32_t)PT_TILE) * 7u << slog) & ((uint32_t)PT_TILE - 1u);
+            const uint32_t at = rows > slice ? min(rot, (rows - slice) & ~3u) : 0u;
+            const uint32_t first = at + r;  // the unit's first row inside the tile
+            k[u] = sample_keys4(ld, tb + min(first, (rows - 1u) & ~3u));
+            nv[u] = (i < total && first < rows) ? min(4u, rows - first) : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if ((uint32_t)e < nv[u]) atomicAdd(&s_h[pass_digit(pp, k[u][e], mask)], 1u);
+    }
+    lds_barrier();
+    for (uint32_t d = threadIdx.x; d < F; d += PT_THREADS) {
+        uint32_t c = s_h[d];
+        if (c) atomicAdd(&pp.hist[(size_t)seg * F + d], c);
+    }
+}
+
+// Capacities of the final partitions from their sample counts — k_spec_caps' formula over up to 2^18 bins, so as
+// a grid and a two-level scan: one workgroup per output segment (the F final partitions of a first-pass
+// partition, which stay adjacent), thread d = digit d.  LEVEL 0 leaves the segment's sum of capacities in
+// seg_sum[seg]; LEVEL 1 starts from the sum of the segments below and writes the exclusive scan — the partition's
+// begin, into pairs[2 i] of the {begin, end} pairs — limit[] = begin + capacity and cursor[] = begin.  Nothing reaches beyond cap_max, the tuples the
+// host made room for (Exec::partition): a partition that would is cut there and overflows like any other.
+template <int LEVEL>
+__global__ __launch_bounds__(PT_MAXF) void k_last_caps(const uint32_t* sample, uint32_t nseg, uint32_t F, uint32_t sample_log2,
+                                                       float z, uint32_t cap_max, unsigned long long* seg_sum,
+                                                       uint32_t* pairs, uint32_t* limit, uint32_t* cursor) {
+    __shared__ unsigned long long s_sum[PT_MAXF];
+    const uint32_t                seg = blockIdx.x, d = threadIdx.x;
+    const size_t                  i = (size_t)seg * F + d;
+    unsigned long long            cap = 0;
+    if (d < F) {
+        const double zz = (double)z, x = (double)sample[i] + zz * sqrt((double)sample[i] + 1.0) + 0.5 * zz * zz;
+        cap = ((unsigned long long)ceil(ldexp(x, (int)sample_log2)) + 31ull) & ~31ull;
+    }
+    s_sum[d] = cap;
+    __syncthreads();
+    if constexpr (LEVEL == 0) {
+        if (d == 0) {
+            unsigned long long sum = 0;
+            for (uint32_t k = 0; k < F; ++k) sum += s_sum[k];
+            seg_sum[seg] = sum;
+        }
+    } else {
+        unsigned long long run = 0;
+        for (uint32_t k = 0; k < d && k < F; ++k) run += s_sum[k];
+        __syncthreads();
+        unsigned long long below = 0;  // the segments below this one
+        for (uint32_t k = d; k < seg; k += PT_MAXF) below += seg_sum[k];
+        s_sum[d] = below;
+        __syncthreads();
+        for (uint32_t k = 0; k < (uint32_t)PT_MAXF; ++k) run += s_sum[k];
+        if (d < F) {
+            const uint32_t st = (uint32_t)min(run, (unsigned long long)cap_max);
+            const uint32_t lim = (uint32_t)min(run + cap, (unsigned long long)cap_max);
+            pairs[2 * i] = st;
+            limit[i] = lim;
+            cursor[i] = st;
+        }
+    }
+}
+
+// (k_pass_scatter's and k_pass_scatter_packed's bodies with the speculative switch, for the LAST pass: 12-byte
+// tuples out of the dense key array + pair array, pairs out of blocked pairs)
+template <int NW, class Loader, int PAIR>
+__global__ __launch_bounds__(PT_THREADS) void k_last_scatter(Loader ld, PassParams pp, Words out, LastParams sp) {
+    constexpr bool SPEC = true, SPEC_LAST = true, AOS = true;
+#include "rj_pass_scatter.inc"
+}
+template <class Loader>
+__global__ __launch_bounds__(PT_THREADS) void k_last_scatter_packed(Loader ld, PassParams pp, uint2* out, LastParams sp) {
+    constexpr bool SPEC = true, SPEC_LAST = true, BLK_OUT = false;
+#include "rj_pass_scatter_packed.inc"
+}
+
+// Closing the pass: final partition q holds [begin[q], end[q]), end = min(where its cursor stands, its limit), next
+// to begin in the pairs.  Nothing is compacted: the join skips the unused room behind a partition.
+__global__ __launch_bounds__(256) void k_last_close(const uint32_t* cursor, const uint32_t* limit, uint32_t nbins,
+                                                    uint32_t* pairs) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nbins) pairs[2 * (size_t)i + 1] = min(cursor[i], limit[i]);
 }
 
 // ============================================================= heavy task list
 // Probe partitions above JN_HEAVY tuples are cut into tasks so that a skewed
 // (Zipf) probe side does not serialise on one workgroup; each task rebuilds the
 // (small) build table of its partition.
+// (off_pairs: JoinParams' — neighbouring offsets, or {begin, end} pairs behind a speculative last pass)
 __global__ void k_heavy_tasks(const uint32_t* offR, const uint32_t* offS, uint32_t NP,
-                              uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks) {
+                              uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks, uint32_t off_pairs) {
     uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= NP) return;
-    uint32_t sb = offS[q], se = offS[q + 1];
+    const uint32_t ir = q << (off_pairs & 1u), is = q << (off_pairs >> 1);
+    uint32_t sb = offS[is], se = offS[is + 1];
     uint32_t len = se - sb;
-    if (len <= JN_HEAVY || offR[q + 1] == offR[q]) return;
+    if (len <= JN_HEAVY || offR[ir + 1] == offR[ir]) return;
     uint32_t nt = (len + JN_HEAVY - 1) / JN_HEAVY;
     uint32_t b = atomicAdd(n_heavy, nt);
     for (uint32_t t = 0; t < nt; ++t) {
@@ -1384,17 +1518,57 @@ void launch_pass_scatter_packed(const Launch& L, const uint32_t* in_pairs, const
                reinterpret_cast<uint2*>(out_pairs));
 }
 
+void launch_last_sample(const Launch& L, const uint32_t* in_keys, bool blocked, const PassParams& pp, const LastParams& sp,
+                        uint32_t n_groups) {
+    if (!n_groups) return;
+    if (blocked) {
+        RJ_KLAUNCH(L, "pass2_sample", (k_last_sample<BlockedLoader>), n_groups, PT_THREADS, BlockedLoader{in_keys}, pp, sp);
+    } else {
+        Words in{};
+        in.w[0] = const_cast<uint32_t*>(in_keys);
+        RJ_KLAUNCH(L, "pass2_sample", (k_last_sample<DenseLoader>), n_groups, PT_THREADS, DenseLoader{in}, pp, sp);
+    }
+}
+
+void launch_last_caps(const Launch& L, const uint32_t* sample, uint32_t nseg, uint32_t F, uint32_t sample_log2, float z,
+                      uint32_t cap_max, unsigned long long* seg_sum, uint32_t* pairs, uint32_t* limit,
+                      uint32_t* cursor) {
+    RJ_KLAUNCH(L, "last_caps", (k_last_caps<0>), nseg, PT_MAXF, sample, nseg, F, sample_log2, z, cap_max, seg_sum, pairs,
+               limit, cursor);
+    RJ_KLAUNCH(L, "last_caps", (k_last_caps<1>), nseg, PT_MAXF, sample, nseg, F, sample_log2, z, cap_max, seg_sum, pairs,
+               limit, cursor);
+}
+
+void launch_last_scatter_dense(const Launch& L, const Words& in, const PassParams& pp, uint32_t n_groups, const Words& out,
+                               const LastParams& sp) {
+    if (!n_groups) return;
+    RJ_KLAUNCH(L, "pass2_scatter", (k_last_scatter<3, DenseLoaderT<1>, 1>), n_groups, PT_THREADS, DenseLoaderT<1>{in}, pp, out,
+               sp);
+}
+
+void launch_last_scatter_blocked(const Launch& L, const uint32_t* in_blocked, const PassParams& pp, uint32_t n_groups,
+                                 uint32_t* out_pairs, const LastParams& sp) {
+    if (!n_groups) return;
+    RJ_KLAUNCH(L, "pass2_scatter", (k_last_scatter_packed<BlockedLoader>), n_groups, PT_THREADS, BlockedLoader{in_blocked}, pp,
+               reinterpret_cast<uint2*>(out_pairs), sp);
+}
+
+void launch_last_close(const Launch& L, const uint32_t* cursor, const uint32_t* limit, uint32_t nbins,
+                       uint32_t* pairs) {
+    RJ_KLAUNCH(L, "last_close", k_last_close, (nbins + 255u) / 256u, 256, cursor, limit, nbins, pairs);
+}
+
 void launch_heavy_tasks(const Launch& L, const uint32_t* offR, const uint32_t* offS, uint32_t NP,
-                        uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks) {
+                        uint32_t* tasks, uint32_t* n_heavy, uint32_t max_tasks, uint32_t off_pairs) {
     RJ_KLAUNCH(L, "heavy_tasks", k_heavy_tasks, (NP + 255) / 256, 256, offR, offS, NP, tasks,
-               n_heavy, max_tasks);
+               n_heavy, max_tasks, off_pairs);
 }
 
 // RJ_CTX_PREWARM: one harmless launch, so that HIP loads this translation unit's code object when the context is
 // built (as prewarm_varchar_dev does).  NP = 0: every thread of k_heavy_tasks leaves at `q >= NP`, its first check,
 // before any pointer is read.
 void prewarm_partition(const Launch& L, uint32_t* zeroed) {
-    RJ_KLAUNCH(L, "prewarm", k_heavy_tasks, 1, 256, zeroed, zeroed, 0u, zeroed, zeroed, 0u);
+    RJ_KLAUNCH(L, "prewarm", k_heavy_tasks, 1, 256, zeroed, zeroed, 0u, zeroed, zeroed, 0u, 0u);
 }
 
 }  // namespace rj

@@ -1,5 +1,5 @@
 // rj_pass_scatter.inc — the body of k_pass_scatter and of k_spec_scatter (rj_partition.hip), which include it with
-// NW, Loader, PAIR, AOS, SPEC and ld, pp, out, sp in scope.  Text shared by inclusion, not through a function: the
+// NW, Loader, PAIR, AOS, SPEC, SPEC_LAST and ld, pp, out, sp in scope.  Text shared by inclusion, not through a function: the
 // exact kernels are then compiled from what they were compiled from before the speculative ones existed, and come
 // out instruction for instruction the same (profiles/spec_pass1_codeobj.log).
     static_assert(PAIR < 0 || (PAIR >= 1 && PAIR + 1 < NW), "pair = two carry words behind the key");
@@ -13,6 +13,14 @@
     uint32_t            seg, begin, end;
     if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
     const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
+    // SPEC_LAST (k_last_scatter*, the speculative last pass: LastParams): the reservation is the exact kernel's 32-bit add,
+    // and the run fits if it ends at or before the partition's limit.  The limits of the group's output segment are
+    // loaded once, into the LDS: thread d keeps nothing more in registers than the exact kernel does (with the first
+    // pass' 64-bit {position, room} word the 12-byte kernel spilled two VGPRs in every tile).
+    __shared__ uint32_t s_limit[SPEC && SPEC_LAST ? PT_MAXF : 1];
+    if constexpr (SPEC && SPEC_LAST) {
+        if (threadIdx.x < F) s_limit[threadIdx.x] = last_limit(sp)[(size_t)seg * F + threadIdx.x];  // (the tile loop's first barrier is behind it)
+    }
 
     // Thread d owns digit d's write cursor in a REGISTER: the reservation's round trip is
     // not waited for until the first tile has been loaded and ranked.
@@ -55,7 +63,9 @@
         uint32_t c = threadIdx.x < F ? s_cnt[threadIdx.x] : 0u;
         if (c) {
             const size_t at = (((size_t)seg * F + threadIdx.x) << pp.xcd_log2) | (blockIdx.x & ((1u << pp.xcd_log2) - 1u));
-            if constexpr (SPEC)
+            if constexpr (SPEC && SPEC_LAST)
+                run = atomicAdd(&last_cursor(sp)[at], c);
+            else if constexpr (SPEC)
                 res = atomicAdd(&sp.cursor[at], (unsigned long long)c | ((unsigned long long)(0u - c) << 32));
             else
                 run = atomicAdd(&pp.cursor[at], c);
@@ -67,7 +77,13 @@
         // thread d: global index of digit d's tuples = delta + position in the sorted tile.  (SPEC: looked at
         // here, where the exact kernel first uses `run`, so the reservation's round trip stays hidden as it is)
         auto delta_of = [&]() -> uint32_t {
-            if constexpr (SPEC) {
+            if constexpr (SPEC && SPEC_LAST) {
+                if (c && run + c > s_limit[threadIdx.x]) {
+                    atomicOr(sp.flag, 1u);
+                    return sp.sink;
+                }
+                return run - ex;
+            } else if constexpr (SPEC) {
                 if (c && (int32_t)(uint32_t)(res >> 32) < (int32_t)c) {
                     atomicOr(sp.flag, 1u);
                     return sp.sink;

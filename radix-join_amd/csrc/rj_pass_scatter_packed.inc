@@ -1,5 +1,5 @@
 // rj_pass_scatter_packed.inc — the body of k_pass_scatter_packed and of k_spec_scatter_packed (rj_partition.hip),
-// which include it with Loader, BLK_OUT, SPEC and ld, pp, out, sp in scope (see rj_pass_scatter.inc).
+// which include it with Loader, BLK_OUT, SPEC, SPEC_LAST and ld, pp, out, sp in scope (see rj_pass_scatter.inc).
     __shared__ uint2    s_stage[PT_TILE];
     __shared__ uint32_t s_cnt[PT_MAXF];
     __shared__ uint32_t s_base[PT_MAXF];
@@ -8,6 +8,11 @@
     uint32_t            seg, begin, end;
     if (!group_range(pp, blockIdx.x, seg, begin, end)) return;
     const uint32_t F = 1u << pp.fanout_log2, mask = F - 1u;
+    // (SPEC_LAST: see rj_pass_scatter.inc)
+    __shared__ uint32_t s_limit[SPEC && SPEC_LAST ? PT_MAXF : 1];
+    if constexpr (SPEC && SPEC_LAST) {
+        if (threadIdx.x < F) s_limit[threadIdx.x] = last_limit(sp)[(size_t)seg * F + threadIdx.x];
+    }
 
     uint32_t run = 0;  // thread d: where digit d's run of the current tile starts in the output
     [[maybe_unused]] unsigned long long res = 0;  // SPEC: what the reservation returned, {position, room}
@@ -35,7 +40,9 @@
         uint32_t c = threadIdx.x < F ? s_cnt[threadIdx.x] : 0u;
         if (c) {
             const size_t at = (((size_t)seg * F + threadIdx.x) << pp.xcd_log2) | (blockIdx.x & ((1u << pp.xcd_log2) - 1u));
-            if constexpr (SPEC)
+            if constexpr (SPEC && SPEC_LAST)
+                run = atomicAdd(&last_cursor(sp)[at], c);
+            else if constexpr (SPEC)
                 res = atomicAdd(&sp.cursor[at], (unsigned long long)c | ((unsigned long long)(0u - c) << 32));
             else
                 run = atomicAdd(&pp.cursor[at], c);
@@ -51,7 +58,14 @@
                 s_stage[s_base[dr[j] >> 16] + (dr[j] & 0xffffu)] = make_uint2(w[j][0], w[j][1]);
         if (base + PT_TILE < end) ok_raw = ld.template issue_tile<2>(base + PT_TILE, end, w);
         if (threadIdx.x < F) {  // global index = delta + LDS position
-            if constexpr (SPEC) {
+            if constexpr (SPEC && SPEC_LAST) {
+                if (c && run + c > s_limit[threadIdx.x]) {
+                    atomicOr(sp.flag, 1u);
+                    s_delta[threadIdx.x] = sp.sink;
+                } else {
+                    s_delta[threadIdx.x] = run - ex;
+                }
+            } else if constexpr (SPEC) {
                 if (c && (int32_t)(uint32_t)(res >> 32) < (int32_t)c) {  // the run does not fit: to the spare tile
                     atomicOr(sp.flag, 1u);
                     s_delta[threadIdx.x] = sp.sink;
