@@ -789,6 +789,60 @@ int rj_debug_fsum(const uint64_t* bits, const uint8_t* is_null /* may be NULL */
 int rj_debug_map_eval(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, const int32_t* col_type,
                       const uint64_t* col_bits, const uint8_t* col_null, uint64_t out_cap, uint64_t* out_bits,
                       uint8_t* out_null, int32_t* out_kind, uint64_t* n_out);
+/* The pass plan of ONE radix partition call, as the library's driver would take it (csrc/rj_radix_plan.cpp): every
+ * decision that is taken before the first launch, from the facts of the request, the RJ_TUNE_* variables (read from
+ * the environment by this call, as a context reads them when it is made) and a compute-unit count.  Needs neither
+ * a context nor a GPU.  RJ_ERR_ARG: a NULL pointer, key_words outside 1..2 or carry_words outside 0..3 or more than
+ * 4 words together, more than 32 bits, a single pass of more than 9 bits, a packed word source that is not one
+ * key word + one carry word.                                                                                     */
+typedef struct rj_partition_request {
+    uint64_t n;                        /* rows of the source                                                    */
+    int32_t  key_words, carry_words;
+    uint32_t bits, shift0;
+    int32_t  single_pass;
+    int32_t  word_source;              /* 0 = columns, 1 = tuples in word arrays, 2 = ... in packed pairs       */
+    int32_t  external;                 /* caller-owned output arrays                                            */
+    int32_t  composite;                /* composite digit (stage A of a sharded join)                           */
+    uint32_t preseg_nseg, preseg_n_oseg; /* pre-segmented input (stage B): input runs, output segments; 0 = not */
+    int32_t  after_offsets;            /* the caller takes the first pass' offsets ahead of its scatter         */
+    int32_t  flag_word;                /* a flag word was given: the first pass may be speculative              */
+    int32_t  spec2_ok;                 /* ... and the last pass too                                             */
+} rj_partition_request;
+enum { RJ_PLAN_MAX_PASSES = 4 };
+typedef enum rj_plan_mid {             /* how tuples travel between the passes                                  */
+    RJ_MID_DENSE = 0, RJ_MID_PACKED = 1, RJ_MID_PACKED_SIDE = 2, RJ_MID_BLOCKED = 3, RJ_MID_AOS3 = 4, RJ_MID_AOS3_SIDE = 5
+} rj_plan_mid;
+typedef enum rj_plan_last { RJ_LAST_DENSE = 0, RJ_LAST_PACKED = 1, RJ_LAST_AOS3 = 2 } rj_plan_last;
+typedef enum rj_plan_offsets {         /* where a pass gets its partition offsets from                          */
+    RJ_OFF_FINE = 0, RJ_OFF_HIST = 1, RJ_OFF_SAMPLE = 2, RJ_OFF_CHUNKED = 3
+} rj_plan_offsets;
+typedef enum rj_plan_hist {            /* the launcher that counts for a pass                                   */
+    RJ_HIST_NONE = 0, RJ_HIST_FINE_SRC, RJ_HIST_FINE_WORDS, RJ_HIST_SRC, RJ_HIST_DIGITS, RJ_HIST_AOS3, RJ_HIST_BLOCKED,
+    RJ_HIST_PACKED, RJ_HIST_DENSE, RJ_HIST_SAMPLE_SRC, RJ_HIST_LAST_SAMPLE
+} rj_plan_hist;
+typedef enum rj_plan_scatter {         /* the launcher that writes a pass                                       */
+    RJ_SCATTER_SRC = 0, RJ_SCATTER_SRC_PACKED, RJ_SCATTER_DENSE, RJ_SCATTER_PACKED, RJ_SCATTER_BLOCKED, RJ_SCATTER_AOS3,
+    RJ_SCATTER_LAST_BLOCKED, RJ_SCATTER_LAST_DENSE
+} rj_plan_scatter;
+typedef struct rj_partition_pass {
+    uint32_t bits, tiles_per_group, xcd_log2, xcd_remap;
+    uint32_t nseg_in, n_oseg, n_groups;
+    int32_t  offsets, hist, scatter;   /* rj_plan_offsets, rj_plan_hist, rj_plan_scatter                        */
+    uint64_t bins;
+} rj_partition_pass;
+typedef struct rj_partition_plan {
+    uint32_t passes;
+    uint32_t pbits[RJ_PLAN_MAX_PASSES];
+    int32_t  fine, fine_xcd;
+    uint32_t fine_grid;
+    int32_t  mid, last;                /* rj_plan_mid, rj_plan_last                                             */
+    int32_t  spec, spec2;
+    uint64_t spec_cap_max, spec2_cap_max;  /* the bounds, whether or not the pass is speculative                */
+    uint64_t n_first_out, n_last_out;  /* tuples the first / last pass' output arrays hold                      */
+    uint32_t tpg_first, reserved;
+    rj_partition_pass pass[RJ_PLAN_MAX_PASSES];
+} rj_partition_plan;
+int rj_debug_partition_plan(const rj_partition_request* req, uint32_t compute_units, rj_partition_plan* out);
 uint64_t rj_table_num_rows(const rj_table* t);
 uint64_t rj_table_col_pages(const rj_table* t, uint64_t col);
 int      rj_table_copy_pages(rj_context* ctx, const rj_table* t, uint64_t col, void* const* dst, uint64_t n_dst);

@@ -6,6 +6,7 @@
 
 #include "rj_fsum.hpp"
 #include "rj_internal.hpp"
+#include "rj_radix_plan.hpp"
 #include "rj_sortkey.hpp"
 #include "rj_xplan.hpp"
 
@@ -220,6 +221,45 @@ int rj_debug_map_eval(const rj_expr_op* ops, uint64_t n_ops, uint64_t n_cols, co
         g_create_error = e.what();
         return RJ_ERR_DEVICE;
     }
+}
+
+int rj_debug_partition_plan(const rj_partition_request* req, uint32_t compute_units, rj_partition_plan* out) {
+    if (!req || !out) return RJ_ERR_ARG;
+    if (req->key_words < 1 || req->key_words > 2 || req->carry_words < 0 || req->key_words + req->carry_words > MAX_WORDS) return RJ_ERR_ARG;
+    if (req->bits > 32 || (req->single_pass && req->bits > (uint32_t)PT_MAXBITS)) return RJ_ERR_ARG;
+    if (req->word_source < 0 || req->word_source > 2 || (req->word_source == 2 && (req->key_words != 1 || req->carry_words != 1))) return RJ_ERR_ARG;
+    RadixFacts f;
+    f.n = req->n;
+    f.KW = req->key_words, f.CW = req->carry_words, f.bits = req->bits, f.shift0 = req->shift0;
+    f.single_pass = req->single_pass != 0;
+    f.word_src = req->word_source != 0, f.word_src_packed = req->word_source == 2;
+    f.external = req->external != 0, f.composite = req->composite != 0;
+    f.preseg_nseg = req->preseg_nseg, f.preseg_n_oseg = req->preseg_n_oseg;
+    f.after_offsets = req->after_offsets != 0, f.spec_flag = req->flag_word != 0, f.spec2_ok = req->spec2_ok != 0;
+    Tuning tune;
+    tune.from_env();
+    const RadixPlan pl = radix_plan(f, tune, (int)compute_units);
+    static_assert((int)RadixMid::Aos3Side == RJ_MID_AOS3_SIDE && (int)RadixLast::Aos3 == RJ_LAST_AOS3 &&
+                      (int)RadixOffsets::Chunked == RJ_OFF_CHUNKED && (int)RadixHist::LastSample == RJ_HIST_LAST_SAMPLE &&
+                      (int)RadixScatter::LastDense == RJ_SCATTER_LAST_DENSE,
+                  "include/rj.h lists the plan's enums in the order of rj_radix_plan.hpp");
+    *out = rj_partition_plan{};
+    out->passes = pl.passes();
+    out->fine = pl.fine, out->fine_xcd = pl.fine_xcd, out->fine_grid = pl.fine_grid;
+    out->mid = (int32_t)pl.mid, out->last = (int32_t)pl.last;
+    out->spec = pl.spec, out->spec2 = pl.spec2;
+    out->spec_cap_max = pl.spec_cap_max, out->spec2_cap_max = pl.spec2_cap_max;
+    out->n_first_out = pl.n_first_out, out->n_last_out = pl.n_last_out;
+    out->tpg_first = pl.tpg_first;
+    for (uint32_t p = 0; p < pl.passes() && p < RJ_PLAN_MAX_PASSES; ++p) {
+        const RadixPass&   ps = pl.pass[p];
+        rj_partition_pass& o = out->pass[p];
+        out->pbits[p] = pl.pbits[p];
+        o.bits = ps.bits, o.tiles_per_group = ps.tiles_per_group, o.xcd_log2 = ps.xcd_log2, o.xcd_remap = ps.xcd_remap;
+        o.nseg_in = ps.nseg_in, o.n_oseg = ps.n_oseg, o.n_groups = ps.n_groups, o.bins = ps.bins;
+        o.offsets = (int32_t)ps.offsets, o.hist = (int32_t)ps.hist, o.scatter = (int32_t)ps.scatter;
+    }
+    return RJ_OK;
 }
 
 int rj_debug_launch_log(rj_context* ctx, int on) {

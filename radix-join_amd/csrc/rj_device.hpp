@@ -160,7 +160,7 @@ __host__ __device__ inline uint32_t pass_digit(const PassParams& pp, uint32_t w,
 // The first pass of a big two-pass plan sizes the 2^fanout_log2 * 8 output sub-ranges from a SAMPLE
 // of the keys instead of counting them all: sub-range i gets cap[i] tuples of room (k_spec_caps), the
 // scatter checks the room in the reservation itself, and a sub-range that turns out too small sends
-// the whole partition() call back to the exact histogram path.  The speculative kernels take these
+// the whole radix_partition() call back to the exact histogram path.  The speculative kernels take these
 // parameters as an argument of their own: PassParams, and with it every kernel of the exact path,
 // stays as it is.
 constexpr uint32_t SPEC_BINS = (1u << PT_MAXBITS) * 8u;  // sub-ranges of a 9-bit first pass: 4096

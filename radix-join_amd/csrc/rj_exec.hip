@@ -19,6 +19,7 @@
 
 #include "rj_expr.hpp"
 #include "rj_internal.hpp"
+#include "rj_radix.hpp"
 #include "rj_xplan.hpp"
 
 namespace rj {
@@ -71,52 +72,6 @@ struct DCol {
 struct Rel {
     uint64_t          n = 0;
     std::vector<DCol> cols;
-};
-
-struct Parted {
-    int      NW = 0;
-    BufP     wbuf[MAX_WORDS];
-    Words    w{};
-    BufP     off;  // u32[NP+1]
-    uint32_t NP = 0;
-    std::vector<uint32_t> pbits;  // radix bits of each pass
-    bool     packed = false;      // w[0] = {hashed key, carry} pairs, no w[1]
-    bool     aos3 = false;        // w[0] = 12-byte {hashed key, carry lo, carry hi} tuples, no w[1..2]
-    uint64_t n_tuples = 0;        // tuples that went in (NULL keys are dropped on the way: an upper bound)
-    bool     spec = false;        // the first pass ran without its histogram (partition(): spec_flag); the caller's flag word tells
-                                  // whether everything found room — if not, what is in here is in bounds but not the partition
-    // Partition q holds tuples [off[q << off_shift], off[(q << off_shift) + 1]).  Exact partitions lie one behind the
-    // other (off_shift = 0, off = u32[NP + 1]); a speculative LAST pass (spec2, only behind a speculative first one
-    // and under the same flag word) leaves unused room behind each: off = u32[2 NP], {begin, end} pairs
-    uint32_t off_shift = 0;
-    bool     spec2 = false;
-};
-
-// Tuples that already sit in the partition layout (hashed word arrays, a pair array for a
-// two-word carry, or one array of packed {key, carry} pairs): what a rank holds after the
-// exchange step of a sharded join.
-struct WordSrc {
-    Words    w{};
-    uint64_t n = 0;
-    bool     packed = false;
-};
-
-// How the FIRST pass of a partition() call differs from the plain "one segment, one bit field"
-// case — both forms belong to the sharded join:
-//   * composite digit (stage A): owner rank from the top hash bits, first local digit from the
-//     low ones, in one pass (PassParams::hi_shift / lo_bits);
-//   * pre-segmented input (stage B): what arrived in the exchange is a set of runs, one per
-//     (source rank, local digit), listed digit-major; `world` of them feed one output segment
-//     (ExchangePlan::seg_begin / seg_end / part_off, rj_xplan.hpp).
-struct PassShape {
-    uint32_t        hi_shift = 0, lo_bits = 0;
-    const uint32_t* seg_begin = nullptr;  // device, [nseg]
-    const uint32_t* seg_end = nullptr;    // device, [nseg]
-    uint32_t        nseg = 0;
-    uint32_t        oseg_shift = 0;       // input segment i feeds output segment i >> oseg_shift
-    const uint32_t* oseg_off = nullptr;   // device, [n_oseg + 1]
-    uint32_t        n_oseg = 0;
-    std::vector<uint32_t> prior_bits;     // digits consumed before this call (for the partition index)
 };
 
 struct JoinSpec {
@@ -242,7 +197,11 @@ class Exec {
         Words    ext{};
         ext.w[0] = static_cast<uint32_t*>(out->key);
         ext.w[1] = static_cast<uint32_t*>(out->carry);
-        Parted P = partition(&src, nullptr, 1, 1, rb, /*shift0=*/rb ? 32 - rb : 31, /*single pass*/ true, &ext);
+        PartitionRequest rq = PartitionRequest::columns(src, 1, 1, rb);
+        rq.shift0 = rb ? 32 - rb : 31;
+        rq.single_pass = true;
+        rq.external = &ext;
+        Parted P = partition(rq);
         std::vector<uint32_t> off(n_ranks + 1);
         read_back(off.data(), P.off->p, (n_ranks + 1) * 4);
         for (uint32_t r = 0; r < n_ranks; ++r) counts[r] = off[r + 1] - off[r];
@@ -294,18 +253,8 @@ class Exec {
         if (r.n > 0xfffffff0ull) throw_fmt(RJ_ERR_UNSUPPORTED, "more than 2^32 rows in one relation");
     }
 
-    // `bytes` from the device into `dst`, waited for.  `dst` is the end of a copy that may still be
-    // queued when something throws: the stream drains before the exception travels on, so that the
-    // caller's variable outlives the copy.
-    void read_back(void* dst, const void* src, size_t bytes) {
-        try {
-            RJ_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            ctx->sync();
-        } catch (...) {
-            (void)hipStreamSynchronize(ctx->stream);
-            throw;
-        }
-    }
+    // `bytes` from the device into `dst`, waited for (the stream drains before an exception travels on)
+    void read_back(void* dst, const void* src, size_t bytes) { rj::read_back(ctx, dst, src, bytes); }
 
     // Where the columns of a one-child node's output go: below the root into the Rel its parent reads,
     // at the root into the Result as Page images.
@@ -487,489 +436,8 @@ class Exec {
     }
 
     // -------------------------------------------------------- radix partition
-    static uint32_t tiles_per_group(uint64_t tuples_per_segment, uint64_t target_groups) {
-        uint64_t k = (tuples_per_segment + (uint64_t)PT_TILE * target_groups - 1) /
-                     ((uint64_t)PT_TILE * target_groups);
-        return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(k, 1), 8);
-    }
-
-    // Source = columns (`src`: page decode, NULL drop and hashing ride on the first pass) or
-    // tuples already in the partition layout (`ws`, sharded stage B).
-    // `external`: caller-owned arrays that receive the output of a single-pass partition
-    // spec_flag (optional, device, zeroed by the caller): the call may run its first pass speculatively (see `spec`
-    // below); the word is then set on the device if the result has to be thrown away, Parted::spec says it was tried
-    // spec2_ok: ... and, behind a speculative first pass, its last pass too (only a caller whose kernels read a partition
-    // through Parted::off_shift: the inner join)
-    // after_offsets (optional): called once the FIRST pass' partition offsets are enqueued to be
-    // computed, before its scatter is enqueued — a caller that needs the counts on the host
-    // (the sharded join's stage A) copies them out ahead of the scatter.
-    Parted partition(const TupleSrc* srcp, const WordSrc* ws, int KW, int CW, uint32_t bits,
-                     uint32_t shift0 = 0, bool single_pass = false, const Words* external = nullptr,
-                     const std::function<void(const uint32_t*)>* after_offsets = nullptr,
-                     const PassShape* shape = nullptr, uint32_t* spec_flag = nullptr, bool spec2_ok = false) {
-        Parted P;
-        const bool preseg = shape && shape->nseg > 0;
-        P.NW = KW + CW;
-        const TupleSrc none{};
-        const TupleSrc& src = srcp ? *srcp : none;
-        const uint64_t  n = ws ? ws->n : src.n_rows;
-        uint32_t       passes = single_pass ? 1 : (bits + PT_MAXBITS - 1) / PT_MAXBITS;
-        if (passes == 0) passes = 1;
-        std::vector<uint32_t> pbits(passes, bits / passes);
-        for (uint32_t i = 0; i < bits % passes; ++i) pbits[i]++;
-        // tuning knobs (experiments): RJ_TUNE_P1_BITS moves bits between pass 1 and pass 2
-        if (passes == 2 && ctx->tune.p1_bits > 0) {
-            uint32_t b1 = (uint32_t)ctx->tune.p1_bits;
-            if (b1 < bits && b1 <= PT_CAPBITS && bits - b1 <= PT_CAPBITS) {
-                pbits[0] = b1;
-                pbits[1] = bits - b1;
-            }
-        }
-
-        // Two passes whose final partitions fit one LDS histogram: both digits are counted in a
-        // single read of the source, the scatters reserve their ranges tile by tile, and the
-        // second histogram pass (4 B/tuple) disappears.
-        const bool fine = passes == 2 && bits <= (uint32_t)PT_FINEBITS && !external && !shape &&
-                          ctx->tune.fine != 0;
-        // key + one carry word travel as 8-byte pairs in one array (half the streams, twice the
-        // bytes per run); RJ_TUNE_PACK: 0 = never, 1 = every plan, 2 = fine-histogram plans only
-        // (a later pass' plain histogram reads 8 instead of 4 bytes per tuple from pairs)
-        const int pack_mode = ctx->tune.pack;
-        P.packed = ws ? ws->packed
-                      : (!external && KW == 1 && CW == 1 && (pack_mode == 1 || (pack_mode == 2 && fine)));
-        // one key word + a two-word carry: the LAST pass writes 12-byte tuples into one array
-        // (RJ_TUNE_AOS3=0: key array + pair array, as the earlier passes do)
-        P.aos3 = KW == 1 && CW == 2 && !external && !single_pass && ctx->tune.aos3 != 0;
-        // ... and so do the passes before it (one output stream of 384-byte runs instead of a
-        // 128-byte-run key stream + a 256-byte-run pair stream; a later pass' histogram then
-        // reads a 16-bit digit side array instead of the keys)
-        // RJ_TUNE_AOS_MID: 0 never, 1 always, 2 (default) only for fine-histogram plans, which
-        // need no digit side array — with it the first pass loses more (+0.8 ms at 1 B rows) than
-        // the histogram gains (−0.4 ms): profiles/r02_y_aos_between_passes_ab.log
-        // RJ_TUNE_AOS_MID=3: always, and WITHOUT the side array (the next histogram reads the keys
-        // out of the 12-byte tuples)
-        const bool aos_mid = P.aos3 && passes >= 2 &&
-                             (ctx->tune.aos_mid == 1 || ctx->tune.aos_mid == 3 || (ctx->tune.aos_mid == 2 && fine));
-        const bool mid_side = aos_mid && !fine && ctx->tune.aos_mid != 3;
-        BufP  A[MAX_WORDS], B[MAX_WORDS], AOS, MID[2], SIDE[2];
-        Words wa{}, wb{}, waos{};
-        if (aos_mid) {
-            for (uint32_t k = 0; k < std::min<uint32_t>(passes - 1, 2); ++k) {
-                MID[k] = ctx->buf(std::max<uint64_t>(n, 1) * 12);
-                if (mid_side) SIDE[k] = ctx->buf(std::max<uint64_t>(n, 1) * 2 + 16);
-            }
-        }
-        // packed pairs above the fine histogram's limit: a later pass' histogram would read the
-        // 8-byte pairs for their 4-byte keys — the pass before it writes the NEXT digit of every
-        // tuple as a 16-bit side array instead (2 bytes written + 2 read per tuple instead of 8 read)
-        const bool packed_side = P.packed && !fine && passes >= 2 && ctx->tune.packed_side != 0 &&
-                                 n >= (uint64_t)ctx->tune.xcd_min_rows;
-        if (packed_side)
-            for (uint32_t k = 0; k < std::min<uint32_t>(passes - 1, 2); ++k)
-                SIDE[k] = ctx->buf(std::max<uint64_t>(n, 1) * 2 + 16);
-        // the last two words of a carry of two or three words are ONE array of 8-byte pairs (at word
-        // pair_word); key + one carry word one array of pairs altogether (packed)
-        const int pair_word = CW >= 2 ? KW + CW - 2 : -1;
-        // The speculative first pass (SpecParams; only for a caller that handed in a flag word and
-        // repeats the call without it when the flag comes back set): no histogram over the source, the 8 << pbits[0]
-        // sub-ranges of its output are sized from a 2^-s sample of the keys plus a margin of z standard deviations,
-        // and the second pass reads them as input segments with gaps between them.
-        // The arrays of that output are made before any count exists.  With C sampled row positions (at most a
-        // slice per tile), B sub-ranges and sample counts c_i, sum c_i <= C, the capacities k_spec_caps hands out sum to
-        //   sum 2^s (c_i + z sqrt(c_i + 1) + z^2 / 2) + 32 B  <=  2^s C + 2^s z sqrt(B (C + B)) + 2^s z^2 / 2 B + 32 B
-        // (Cauchy–Schwarz on the square roots; 32 B: each is rounded up to a multiple of 32) — 1.071 n at 1 B rows,
-        // s = 5, z = 6.  One more tile behind them takes the runs that found no room.  Positions stay 32-bit even
-        // if every tuple were reserved behind a full sub-range: cap_max and n are both below 2^31.
-        const uint32_t spec_s = (uint32_t)ctx->tune.spec_sample;
-        const double   spec_z = ctx->tune.spec_z / 10.0;
-        uint64_t       spec_cap_max = 0;
-        {
-            const double Bn = (double)((uint64_t)8 << pbits[0]);
-            const double C = (double)((n + PT_TILE - 1) / PT_TILE) * (double)(PT_TILE >> spec_s);
-            const double bound = std::ldexp(C + spec_z * std::sqrt(Bn * (C + Bn)) + 0.5 * spec_z * spec_z * Bn, (int)spec_s) + 32.0 * Bn;
-            spec_cap_max = bound < 4.0e9 ? (((uint64_t)std::ceil(bound) + 255u) & ~(uint64_t)255u) : ~(uint64_t)0 >> 1;
-        }
-        const bool spec = spec_flag && ctx->tune.spec_p1 != 0 && passes == 2 && !fine && !ws && !external && !shape &&
-                          !after_offsets && !aos_mid && !packed_side && ctx->tune.mall_chunk <= 0 && ctx->tune.xcd_split &&
-                          n >= (uint64_t)ctx->tune.xcd_min_rows && n >= (uint64_t)ctx->tune.spec_min_rows &&
-                          spec_cap_max < (uint64_t(1) << 31) && n < (uint64_t(1) << 31);  // (... and the room left, which goes down by at most n, stays a signed 32-bit number)
-        P.spec = spec;
-        const uint64_t n_first_out = spec ? spec_cap_max + PT_TILE : n;  // tuples the first pass' output arrays hold
-        // The speculative last pass (k_last_*): the same once more for the B = 2^bits final partitions,
-        // sampled from the first pass' output — at most a slice per tile of the second pass (a partial one at the end
-        // of each of its 8 << pbits[0] input segments) and never more than n positions — with knobs of its own.
-        // 12-byte-tuple plans and packed plans with blocked pairs between the passes have kernels for it.
-        const uint32_t spec2_s = (uint32_t)ctx->tune.spec2_sample;
-        const double   spec2_z = ctx->tune.spec2_z / 10.0;
-        uint64_t       spec2_cap_max = 0;
-        {
-            const double Bn = std::ldexp(1.0, (int)bits);
-            const double C = std::min((double)n, ((double)(n / PT_TILE) + (double)((uint64_t)8 << pbits[0])) * (double)(PT_TILE >> spec2_s));
-            const double bound = std::ldexp(C + spec2_z * std::sqrt(Bn * (C + Bn)) + 0.5 * spec2_z * spec2_z * Bn, (int)spec2_s) + 32.0 * Bn;
-            spec2_cap_max = bound < 4.0e9 ? (((uint64_t)std::ceil(bound) + 255u) & ~(uint64_t)255u) : ~(uint64_t)0 >> 1;
-        }
-        const bool spec2 = spec && spec2_ok && ctx->tune.spec_p2 != 0 && n >= (uint64_t)ctx->tune.spec2_min_rows &&
-                           (P.aos3 || (P.packed && ctx->tune.blocked_mid != 0)) && spec2_cap_max < (uint64_t(1) << 31);
-        P.spec2 = spec2;
-        const uint64_t n_last_out = spec2 ? spec2_cap_max + PT_TILE : n;  // tuples the last pass' output array holds
-        if (P.aos3) {
-            AOS = ctx->buf(std::max<uint64_t>(n_last_out, 1) * 12);
-            waos.w[0] = AOS->as<uint32_t>();
-        }
-        for (int a = 0; a < (P.packed ? 1 : P.NW); ++a) {
-            if (pair_word >= 0 && a == pair_word + 1) continue;
-            const uint64_t wbytes = (P.packed || a == pair_word) ? 8 : 4;
-            if (external) {
-                wa.w[a] = external->w[a];
-                continue;
-            }
-            if ((P.aos3 && passes == 1) || aos_mid) continue;  // every pass writes 12-byte tuples
-            // (+2048: a blocked array ends with a whole block, see BlockedLoader)
-            A[a] = ctx->buf(n_first_out * wbytes + 2048);
-            wa.w[a] = A[a]->as<uint32_t>();
-            if (passes > (P.aos3 ? 2u : 1u)) {
-                B[a] = ctx->buf(n_last_out * wbytes + 2048);
-                wb.w[a] = B[a]->as<uint32_t>();
-            }
-        }
-        BufP     seg_off;  // offsets produced by the previous pass
-        uint32_t nseg = 1, shift = shift0;
-        Words    cur = ws ? ws->w : Words{}, nxt = (P.aos3 && passes == 1) ? waos : wa;
-        bool     cur_is_a = false;
-        BufP       fine_off, fine_cursor, coarse_off, coarse_cursor;
-        BufP       last_limit, last_seg_sum, last_grp;  // per final partition of a speculative last pass: limit = begin + capacity, [begin, end) holds tuples
-        BufP       spec_start, spec_limit, spec_end;  // per sub-range of a speculative first pass' output: [start, end) holds tuples, limit = start + capacity
-        // tiles per group of the first pass (the fine histogram must know it: see fine_xcd)
-        uint32_t tpg_first = tiles_per_group(n, 4096);
-        if (ctx->tune.tpg1 > 0) tpg_first = (uint32_t)ctx->tune.tpg1;
-        bool fine_xcd = false;
-        if (fine) {
-            const uint32_t NB = 1u << bits, F1 = 1u << pbits[0], F2 = 1u << pbits[1];
-            BufP           fh = ctx->buf((uint64_t)NB * 4);
-            const uint64_t tiles = (n + PT_TILE - 1) / PT_TILE;
-            uint32_t       fgrid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)ctx->compute_units());
-            // XCD-aware placement of the first pass: per-sub-range counts out of the histogram
-            // (its grid then is a multiple of 8: workgroup w counts for sub-range w & 7)
-            fine_xcd = ctx->tune.xcd_split && n >= (uint64_t)ctx->tune.xcd_min_rows && fgrid >= 8;
-            if (fine_xcd) fgrid &= ~7u;
-            fine_off = ctx->buf(((uint64_t)NB + 1) * 4);
-            fine_cursor = ctx->buf((uint64_t)NB * 4);
-            coarse_off = ctx->buf(((uint64_t)F1 + 1) * 4);
-            coarse_cursor = ctx->buf((uint64_t)F1 * 4 * (fine_xcd ? 8 : 1));
-            BufP coarse_x;
-            RJ_HIP(hipMemsetAsync(fh->p, 0, (uint64_t)NB * 4, ctx->stream));
-            if (fine_xcd) {
-                coarse_x = ctx->buf((uint64_t)F1 * 8 * 4);
-                RJ_HIP(hipMemsetAsync(coarse_x->p, 0, (uint64_t)F1 * 8 * 4, ctx->stream));
-            }
-            uint32_t* cx = fine_xcd ? coarse_x->as<uint32_t>() : nullptr;
-            if (ws)
-                launch_fine_hist_words(L, ws->w, ws->packed, (uint32_t)n, shift0, pbits[0], pbits[1], fgrid,
-                                       fh->as<uint32_t>(), fine_xcd ? tpg_first : 0u, cx);
-            else
-                launch_fine_hist_src(L, src, KW, shift0, pbits[0], pbits[1], fgrid, fh->as<uint32_t>(),
-                                     fine_xcd ? tpg_first : 0u, cx);
-            launch_scan_fine(L, fh->as<uint32_t>(), F1, F2, fine_off->as<uint32_t>(),
-                             fine_cursor->as<uint32_t>(), coarse_off->as<uint32_t>(),
-                             coarse_cursor->as<uint32_t>(), cx);
-        }
-        // RJ_TUNE_MALL_CHUNK: the second pass of a big packed two-pass plan runs chunk by chunk (below)
-        struct Ev2 {
-            hipEvent_t e = nullptr;
-            void       make() { RJ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-            ~Ev2() {
-                if (e) (void)hipEventDestroy(e);
-            }
-        } chunk_ev;
-        const bool chunk_second = ctx->tune.mall_chunk > 0 && passes == 2 && !fine && !shape && !ws && !external && P.packed &&
-                                  !packed_side && ctx->tune.xcd_split && n >= (uint64_t)ctx->tune.xcd_min_rows;
-        // RJ_TUNE_BLOCKED_MID: between the passes of a packed plan the pairs lie in blocks of 256 keys + 256 carries
-        // (BlockedLoader), so that the next pass' histogram reads 4 instead of 8 bytes per tuple
-        const bool blocked_mid = ctx->tune.blocked_mid != 0 && P.packed && passes >= 2 && !fine && !shape && !ws && !external &&
-                                 !packed_side && !chunk_second;
-        for (uint32_t p = 0; p < passes; ++p) {
-            const uint32_t F = 1u << pbits[p];
-            PassParams     pp{};
-            pp.nseg = nseg;
-            pp.n = (uint32_t)n;
-            pp.shift = shift;
-            pp.fanout_log2 = pbits[p];
-            uint32_t n_groups;
-            BufP     grp_start;
-            // segments this pass reads / output segments it fills (the same unless the input is a
-            // set of exchanged runs, several of which feed one output segment)
-            // (... or the sub-ranges a speculative first pass left behind, eight per output segment)
-            const bool      first_preseg = p == 0 && preseg, spec_in = p == 1 && spec;
-            const uint32_t  nseg_in = first_preseg ? shape->nseg : (spec_in ? nseg << 3 : nseg);
-            const uint32_t  n_oseg = first_preseg ? shape->n_oseg : nseg;
-            const uint64_t  bins = (uint64_t)n_oseg * F;
-            const uint32_t* in_end = first_preseg ? shape->seg_end : (spec_in ? spec_end->as<uint32_t>() : nullptr);
-            if (p == 0 && shape && shape->hi_shift) {
-                pp.hi_shift = shape->hi_shift;
-                pp.lo_bits = shape->lo_bits;
-            }
-            if (p == 0 && !preseg) {
-                pp.tiles_per_group = tpg_first;
-                uint64_t gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                n_groups = (uint32_t)((n + gt - 1) / gt);
-            } else {
-                pp.tiles_per_group = tiles_per_group(n / (spec_in ? n_oseg : nseg_in) + 1, 16);  // (spec_in: as for whole segments)
-                // the last pass of 12-byte-tuple plans (one 384-byte-run output stream) does
-                // better with short groups — 2 tiles per workgroup: 9.3-10.3 -> 8.9-9.1 ms per step
-                // at 1 B rows; packed 8-byte tuples lose with them
-                // (profiles/r03_l_later_pass_group_size_ab.log)
-                if (P.aos3 && p + 1 == passes) pp.tiles_per_group = std::min<uint32_t>(pp.tiles_per_group, 2u);
-                uint64_t gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                if (ctx->tune.tpg2 > 0) {
-                    pp.tiles_per_group = (uint32_t)ctx->tune.tpg2;
-                    gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                }
-                n_groups = (uint32_t)(n / gt + nseg_in);  // upper bound; exact count lives on device
-                if (ctx->tune.xcd_split && n >= (uint64_t)ctx->tune.xcd_min_rows) {
-                    pp.xcd_remap = 1;
-                    n_groups += 8;  // 8 * ceil(G / 8) workgroups
-                }
-                const uint32_t* in_off = first_preseg ? shape->seg_begin : (spec_in ? spec_start->as<uint32_t>() : seg_off->as<uint32_t>());
-                grp_start = ctx->buf(((uint64_t)nseg_in + 1) * 4);
-                launch_group_table(L, in_off, nseg_in, (uint32_t)gt, grp_start->as<uint32_t>(), in_end);
-                pp.nseg = nseg_in;
-                pp.seg_off = in_off;
-                pp.seg_end = in_end;
-                pp.oseg_shift = first_preseg ? shape->oseg_shift : (spec_in ? 3u : 0u);
-                pp.grp_start = grp_start->as<uint32_t>();
-            }
-            BufP off, hist, cursor;  // this pass' partition offsets, bin totals, write cursors
-            SpecParams sp{};
-            LastParams lp{};
-            if (p == 0 && spec) {
-                // sample -> capacities, {position, room} cursors; the partition offsets come from where the cursors
-                // stand once the scatter is through (launch_spec_close below)
-                pp.xcd_log2 = 3u;
-                const uint32_t nb = (uint32_t)bins << 3;
-                hist = ctx->buf((uint64_t)nb * 4);
-                off = ctx->buf((bins + 1) * 4);
-                cursor = ctx->buf((uint64_t)nb * 8);
-                spec_start = ctx->buf((uint64_t)nb * 4);
-                spec_limit = ctx->buf((uint64_t)nb * 4);
-                spec_end = ctx->buf((uint64_t)nb * 4);
-                RJ_HIP(hipMemsetAsync(hist->p, 0, (uint64_t)nb * 4, ctx->stream));
-                pp.hist = hist->as<uint32_t>();
-                sp.cursor = cursor->as<unsigned long long>();
-                sp.flag = spec_flag;
-                sp.sink = (uint32_t)spec_cap_max;
-                sp.sample_log2 = spec_s;
-                launch_pass_sample_src(L, src, KW, pp, sp, n_groups);
-                launch_spec_caps(L, pp.hist, nb, spec_s, (float)spec_z, (uint32_t)spec_cap_max, spec_start->as<uint32_t>(),
-                                 spec_limit->as<uint32_t>(), sp.cursor);
-            } else if (p == 1 && spec2) {
-                // sample of the first pass' output -> capacities; `off` = where the final partitions begin
-                const uint32_t nb = (uint32_t)bins;
-                hist = ctx->buf((uint64_t)nb * 4);
-                off = ctx->buf((uint64_t)nb * 8);  // {begin, end} pairs
-                cursor = ctx->buf((uint64_t)nb * 4);
-                last_limit = ctx->buf((uint64_t)nb * 4);
-                last_seg_sum = ctx->buf((uint64_t)n_oseg * 8);
-                RJ_HIP(hipMemsetAsync(hist->p, 0, (uint64_t)nb * 4, ctx->stream));
-                pp.hist = hist->as<uint32_t>();
-                lp.cursor32 = cursor->as<uint32_t>();
-                lp.limit = last_limit->as<uint32_t>();
-                lp.flag = spec_flag;
-                lp.sink = (uint32_t)spec2_cap_max;
-                lp.sample_log2 = spec2_s;
-                // (the sample's own groups, eight tiles each whatever the scatter's are: a group of the scatter's two
-                // tiles would flush its 512 bins for 4096 sampled keys, as many global adds as the exact histogram's)
-                PassParams ps = pp;
-                ps.tiles_per_group = 8;
-                const uint64_t gts = (uint64_t)ps.tiles_per_group * PT_TILE;
-                last_grp = ctx->buf(((uint64_t)nseg_in + 1) * 4);
-                launch_group_table(L, pp.seg_off, nseg_in, (uint32_t)gts, last_grp->as<uint32_t>(), in_end);
-                ps.grp_start = last_grp->as<uint32_t>();
-                launch_last_sample(L, cur.w[0], P.packed, ps, lp, (uint32_t)(n / gts + nseg_in) + (pp.xcd_remap ? 8u : 0u));
-                launch_last_caps(L, pp.hist, n_oseg, F, spec2_s, (float)spec2_z, (uint32_t)spec2_cap_max,
-                                 last_seg_sum->as<unsigned long long>(), off->as<uint32_t>(), last_limit->as<uint32_t>(), lp.cursor32);
-            } else if (fine) {  // offsets and cursors of both passes came out of the fine histogram
-                off = p == 0 ? coarse_off : fine_off;
-                cursor = p == 0 ? coarse_cursor : fine_cursor;
-                pp.cursor = cursor->as<uint32_t>();
-                pp.xcd_log2 = (p == 0 && fine_xcd) ? 3u : 0u;
-            } else {
-                // sub-ranges per XCD only where a partition gets many runs (big inputs)
-                pp.xcd_log2 = (ctx->tune.xcd_split && p == 0 && !preseg && n >= (uint64_t)ctx->tune.xcd_min_rows) ? 3u : 0u;
-                hist = ctx->buf((bins << pp.xcd_log2) * 4);
-                off = ctx->buf((bins + 1) * 4);
-                cursor = ctx->buf((bins << pp.xcd_log2) * 4);
-                RJ_HIP(hipMemsetAsync(hist->p, 0, (bins << pp.xcd_log2) * 4, ctx->stream));
-                pp.hist = hist->as<uint32_t>();
-                pp.cursor = cursor->as<uint32_t>();
-                if (p == 1 && chunk_second) {
-                    // ---- histogram / scan / scatter of this pass, `mall_chunk` input segments at a time,
-                    // chunks alternating between the context's two compute streams: the scatter of a
-                    // chunk re-reads what its histogram launch has just pulled through the Infinity
-                    // Cache.  Segments never share bins, cursors or output ranges, so the chunks are
-                    // independent; grids are exact (the segment sizes are on the host by now).
-                    RJ_HIP(hipEventSynchronize(chunk_ev.e));
-                    const uint32_t* hoff = static_cast<const uint32_t*>(ctx->small_pinned());
-                    const uint64_t  gt = (uint64_t)pp.tiles_per_group * PT_TILE;
-                    std::vector<uint32_t> gstart(nseg_in + 1, 0);
-                    for (uint32_t sgi = 0; sgi < nseg_in; ++sgi)
-                        gstart[sgi + 1] = gstart[sgi] + (uint32_t)(((uint64_t)(hoff[sgi + 1] - hoff[sgi]) + gt - 1) / gt);
-                    Ev2 e_in, e_aux;
-                    e_in.make();
-                    e_aux.make();
-                    hipStream_t aux = ctx->aux_stream();
-                    RJ_HIP(hipEventRecord(e_in.e, ctx->stream));  // (behind the previous scatter and the bin memset)
-                    RJ_HIP(hipStreamWaitEvent(aux, e_in.e, 0));
-                    Launch L2 = L;
-                    L2.stream = aux;
-                    const uint32_t CH = (uint32_t)ctx->tune.mall_chunk;
-                    uint32_t       c = 0;
-                    for (uint32_t s0 = 0; s0 < nseg_in; s0 += CH, ++c) {
-                        const uint32_t s1 = std::min(nseg_in, s0 + CH), G = gstart[s1] - gstart[s0];
-                        const Launch& Lc = (c & 1u) ? L2 : L;
-                        PassParams    pc = pp;
-                        pc.nseg = s1 - s0;
-                        pc.seg_off = pp.seg_off + s0;
-                        pc.grp_start = pp.grp_start + s0;
-                        pc.grp_base = gstart[s0];
-                        pc.hist = pp.hist + (size_t)s0 * F;
-                        pc.cursor = pp.cursor + (size_t)s0 * F;
-                        const uint32_t grid = pp.xcd_remap ? ((G + 7u) & ~7u) : G;
-                        if (G) launch_pass_hist_packed(Lc, cur.w[0], pc, grid);
-                        // (empty segments still need their partition offsets)
-                        launch_scan_segments(Lc, pc.hist, pc.seg_off, pc.nseg, F, 0, off->as<uint32_t>() + (size_t)s0 * F, pc.cursor);
-                        if (G) launch_pass_scatter_packed(Lc, cur.w[0], pc, grid, nxt.w[0]);
-                    }
-                    RJ_HIP(hipEventRecord(e_aux.e, aux));
-                    RJ_HIP(hipStreamWaitEvent(ctx->stream, e_aux.e, 0));  // (before any buffer of this pass is reused)
-                    seg_off = off;
-                    nseg = (uint32_t)bins;
-                    shift += pbits[p];
-                    cur = nxt;
-                    cur_is_a = (p % 2 == 0);
-                    nxt = cur_is_a ? wb : wa;
-                    continue;
-                }
-                if (p == 0 && !ws)
-                    launch_pass_hist_src(L, src, KW, pp, n_groups);
-                else if ((mid_side || packed_side) && p > 0)
-                    launch_pass_hist_digits(L, SIDE[(p - 1) % 2]->as<uint16_t>(), pp, n_groups);
-                else if (aos_mid && p > 0)
-                    launch_pass_hist_aos3(L, MID[(p - 1) % 2]->as<uint32_t>(), pp, n_groups);
-                else if (P.packed && blocked_mid && p > 0)
-                    launch_pass_hist_blocked(L, cur.w[0], pp, n_groups);
-                else if (P.packed)
-                    launch_pass_hist_packed(L, cur.w[0], pp, n_groups);
-                else
-                    launch_pass_hist_dense(L, cur, pp, n_groups);
-                // (one workgroup per OUTPUT segment; its base = where that segment starts)
-                launch_scan_segments(L, pp.hist,
-                                     first_preseg ? shape->oseg_off : (p == 0 ? nullptr : (spec_in ? seg_off->as<uint32_t>() : pp.seg_off)),
-                                     n_oseg, F, pp.xcd_log2, off->as<uint32_t>(), pp.cursor);
-            }
-            if (p == 0 && after_offsets) (*after_offsets)(off->as<uint32_t>());
-            // the second pass in chunks needs this pass' partition sizes on the HOST (exact grids per
-            // chunk): they leave now, before the scatter is enqueued, and are read while it runs
-            if (p == 0 && chunk_second) {
-                if ((bins + 1) * 4 > Context::SMALL_PINNED / 4) throw_fmt(RJ_ERR_DEVICE, "chunked pass: too many segments");
-                RJ_HIP(hipMemcpyAsync(ctx->small_pinned(), off->p, (bins + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-                chunk_ev.make();
-                RJ_HIP(hipEventRecord(chunk_ev.e, ctx->stream));
-            }
-            if (p == 1 && spec2) {
-                if (P.packed)
-                    launch_last_scatter_blocked(L, cur.w[0], pp, n_groups, nxt.w[0], lp);
-                else
-                    launch_last_scatter_dense(L, cur, pp, n_groups, nxt, lp);
-                launch_last_close(L, lp.cursor32, last_limit->as<uint32_t>(), (uint32_t)bins, off->as<uint32_t>());
-                if (ctx->tune.diag >= 1) spec_report(cursor, last_limit, off, (uint32_t)bins, n, n_last_out, 2);
-                P.off_shift = 1;
-            } else if (aos_mid) {
-                const bool last = p + 1 == passes;
-                Words      o{};
-                o.w[0] = last ? waos.w[0] : MID[p % 2]->as<uint32_t>();
-                if (!last && mid_side) {
-                    pp.side_out = SIDE[p % 2]->as<uint16_t>();
-                    pp.next_shift = shift + pbits[p];
-                    pp.next_mask = (1u << pbits[p + 1]) - 1u;
-                }
-                if (p == 0 && !ws)
-                    launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, o, true);
-                else if (p == 0)
-                    launch_pass_scatter_dense(L, cur, P.NW, KW, pp, n_groups, o, true);
-                else
-                    launch_pass_scatter_aos3(L, MID[(p - 1) % 2]->as<uint32_t>(), pp, n_groups, o.w[0]);
-                nxt = o;
-            } else if (P.packed) {
-                if (packed_side && p + 1 < passes) {
-                    pp.side_out = SIDE[p % 2]->as<uint16_t>();
-                    pp.next_shift = shift + pbits[p];
-                    pp.next_mask = (1u << pbits[p + 1]) - 1u;
-                }
-                const bool blk_out = blocked_mid && p + 1 < passes;
-                if (p == 0 && !ws)
-                    launch_pass_scatter_src_packed(L, src, pp, n_groups, nxt.w[0], blk_out, p == 0 && spec ? &sp : nullptr);
-                else if (blocked_mid)
-                    launch_pass_scatter_blocked(L, cur.w[0], pp, n_groups, nxt.w[0], blk_out);
-                else
-                    launch_pass_scatter_packed(L, cur.w[0], pp, n_groups, nxt.w[0]);
-            } else if (p == 0 && !ws) {
-                launch_pass_scatter_src(L, src, KW, CW, pp, n_groups, nxt, P.aos3 && p + 1 == passes, p == 0 && spec ? &sp : nullptr);
-            } else {
-                launch_pass_scatter_dense(L, cur, P.NW, pair_word, pp, n_groups, nxt,
-                                          P.aos3 && p + 1 == passes);
-            }
-            if (p == 0 && spec) {
-                launch_spec_close(L, sp.cursor, spec_start->as<uint32_t>(), spec_limit->as<uint32_t>(), F, spec_end->as<uint32_t>(),
-                                  off->as<uint32_t>());
-                if (ctx->tune.diag >= 1) spec_report(cursor, spec_limit, spec_start, (uint32_t)bins << 3, n, n_first_out, 1);
-            }
-            seg_off = off;
-            nseg = (uint32_t)bins;
-            shift += pbits[p];
-            cur = nxt;
-            cur_is_a = (p % 2 == 0);
-            nxt = cur_is_a ? wb : wa;
-            if (P.aos3 && p + 2 == passes) nxt = waos;  // the next pass is the last one
-            if (aos_mid) {
-                // (MID / SIDE buffers of a pass are read by the next one only; they go back to
-                // the block cache when this function returns — all on one stream)
-            }
-        }
-        P.w = cur;
-        for (int a = 0; a < P.NW; ++a) P.wbuf[a] = cur_is_a ? A[a] : B[a];
-        if (P.aos3) P.wbuf[0] = AOS;
-        P.off = seg_off;
-        P.NP = nseg;
-        P.pbits = pbits;
-        if (shape && !shape->prior_bits.empty()) P.pbits.insert(P.pbits.begin(), shape->prior_bits.begin(), shape->prior_bits.end());
-        P.n_tuples = n;
-        return P;
-    }
-
-    // RJ_DIAG >= 1: how full the sub-ranges of a speculative first pass came out (waits for the stream)
-    void spec_report(const BufP& cursor, const BufP& limit, const BufP& start, uint32_t nb, uint64_t n, uint64_t n_alloc, int pass) {
-        std::vector<unsigned long long> c(nb);  // (pass 1: {position, room} words; pass 2: 32-bit positions)
-        std::vector<uint32_t>           lim(nb), st(nb);
-        if (pass == 1) {
-            read_back(c.data(), cursor->p, (size_t)nb * 8);
-            read_back(st.data(), start->p, (size_t)nb * 4);
-        } else {  // (`start`: {begin, end} pairs)
-            std::vector<uint32_t> c32(nb), be(2 * (size_t)nb);
-            read_back(c32.data(), cursor->p, (size_t)nb * 4);
-            read_back(be.data(), start->p, (size_t)nb * 8);
-            for (uint32_t i = 0; i < nb; ++i) c[i] = c32[i], st[i] = be[2 * (size_t)i];
-        }
-        read_back(lim.data(), limit->p, (size_t)nb * 4);
-        double   worst = 0;
-        uint32_t over = 0;
-        for (uint32_t i = 0; i < nb; ++i) {
-            const double used = (double)((uint32_t)c[i] - st[i]), room = (double)(lim[i] - st[i]);
-            if (used > room) ++over;
-            if (room > 0) worst = std::max(worst, used / room);
-        }
-        fprintf(stderr, "[rj diag] speculative pass %d: rows=%llu sub-ranges=%u fullest=%.4f of its capacity, over=%u, room for %llu tuples (+%.3f)\n",
-                pass, (unsigned long long)n, nb, worst, over, (unsigned long long)n_alloc, (double)n_alloc / (double)std::max<uint64_t>(n, 1) - 1.0);
-    }
+    // (the driver and its pass plan: rj_radix.hip, rj_radix_plan.cpp)
+    Parted partition(const PartitionRequest& rq) { return radix_partition(ctx, L, rq); }
 
     // ---------------------------------------------------------------- join
     struct Side {
@@ -1253,7 +721,7 @@ class Exec {
         BufP     tasks;  // [max_tasks][3]
         uint32_t max_tasks = 0;
     };
-    // counters (optional, from zeroed_counters()): either side's first pass may run speculatively (partition():
+    // counters (optional, from zeroed_counters()): either side's first pass may run speculatively (PartitionRequest::
     // spec_flag), with the node's two flag words; emit_with_retry then sees them with the row count, and
     // repartition_exact() is what its caller does about a flag that is set
     // spec2_ok: the node's kernels read a partition through Parted::off_shift, so the last pass may be speculative as well
@@ -1261,8 +729,12 @@ class Exec {
         CoParts        cp;
         const TupleSrc sb = make_src(st, st.bs(), js), sp = make_src(st, st.ps(), js);
         uint32_t*      fl = counters ? (*counters)->as<uint32_t>() + 4 : nullptr;
-        cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits, 0, false, nullptr, nullptr, nullptr, fl, spec2_ok);
-        cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits, 0, false, nullptr, nullptr, nullptr, fl ? fl + 1 : nullptr, spec2_ok);
+        PartitionRequest rb = PartitionRequest::columns(sb, st.KW, st.bs().CW, bits), rp = PartitionRequest::columns(sp, st.KW, st.ps().CW, bits);
+        rb.spec_flag = fl;
+        rp.spec_flag = fl ? fl + 1 : nullptr;
+        rb.spec2_ok = rp.spec2_ok = spec2_ok;
+        cp.B = partition(rb);
+        cp.P = partition(rp);
         return cp;
     }
     // A speculative pass (the first, or an inner join's last) found a sub-range too small (flag_b / flag_p: on which side).  What the node has
@@ -1279,12 +751,12 @@ class Exec {
         if (flag_b) {
             const TupleSrc sb = make_src(st, st.bs(), js);
             cp.B = Parted();  // (its arrays go back to the block cache first)
-            cp.B = partition(&sb, nullptr, st.KW, st.bs().CW, bits);  // (no flag word: both passes exact)
+            cp.B = partition(PartitionRequest::columns(sb, st.KW, st.bs().CW, bits));  // (no flag word: both passes exact)
         }
         if (flag_p) {
             const TupleSrc sp = make_src(st, st.ps(), js);
             cp.P = Parted();
-            cp.P = partition(&sp, nullptr, st.KW, st.ps().CW, bits);
+            cp.P = partition(PartitionRequest::columns(sp, st.KW, st.ps().CW, bits));
         }
         RJ_HIP(hipMemsetAsync(counters->as<uint32_t>() + 4, 0, 8, ctx->stream));
         cp.tasks = BufP();
@@ -1862,7 +1334,7 @@ class Exec {
         for (int attempt = 0;; ++attempt) {
             // [0..7] out cursor (u64), [8..11] n_heavy, [12..15] merge table overflow
             BufP counters = zeroed_counters();
-            Parted P = partition(&src, nullptr, KW, s.CW, bits);
+            Parted P = partition(PartitionRequest::columns(src, KW, s.CW, bits));
             const uint32_t max_tasks = (uint32_t)(2 * (P.n_tuples / JN_HEAVY) + 2);
             BufP           tasks = ctx->buf((uint64_t)max_tasks * 12);
             // (one relation: a partition is "its own build side", so every partition above JN_HEAVY is cut)
@@ -3228,16 +2700,7 @@ class ShardedExec {
         }
     }
 
-    struct Ev {  // RAII event on a lane's device
-        hipEvent_t e = nullptr;
-        Ev() = default;
-        Ev(const Ev&) = delete;
-        Ev& operator=(const Ev&) = delete;
-        void make() { RJ_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-        ~Ev() {
-            if (e) (void)hipEventDestroy(e);
-        }
-    };
+    using Ev = Event;  // (made on a lane's device)
 
     std::vector<Rel> node(uint64_t idx, std::vector<Result*>* root_res, int depth) {
         if (idx >= plan_->n_nodes) throw_fmt(RJ_ERR_ARG, "bad node index");
@@ -3441,8 +2904,12 @@ class ShardedExec {
                     }
                     // one field when only one of the two digits exists: the owner's (top bits) or the local one's (low bits)
                     const uint32_t shiftA = sbits ? 0u : (rb_ ? 32 - rb_ : 31);
-                    X.A = E.partition(&src, nullptr, KW, s.CW, rb_ + sbits, shiftA, /*single pass*/ true, nullptr, &counts_out,
-                                      shape.hi_shift ? &shape : nullptr);
+                    PartitionRequest rq = PartitionRequest::columns(src, KW, s.CW, rb_ + sbits);
+                    rq.shift0 = shiftA;
+                    rq.single_pass = true;
+                    rq.after_offsets = &counts_out;
+                    rq.shape = shape.hi_shift ? &shape : nullptr;
+                    X.A = E.partition(rq);
                     // (test hook: this rank's probe-side slices are "never" ready — 7 s — so that the
                     // bounded wait for their exchange can be seen to expire; the counts left earlier)
                     if (g_->tune.debug_shard_fail == 4 && g_->tune.debug_shard_fail_rank == rank_base_ + l && side == 1)
@@ -3569,7 +3036,7 @@ class ShardedExec {
         std::vector<Rel> out((size_t)nl_);
         auto stage_b = [&](int l, SideX& X, int CW) {
             Exec& E = *ex_[l];
-            if (S == 1) return E.partition(nullptr, &X.ws, KW, CW, Lbits);
+            if (S == 1) return E.partition(PartitionRequest::words(X.ws, KW, CW, Lbits));
             const size_t ns = X.plan.seg_begin.size();
             PassShape    shape;
             shape.seg_begin = X.segs->as<uint32_t>();
@@ -3579,7 +3046,10 @@ class ShardedExec {
             shape.n_oseg = S;
             shape.oseg_shift = rb_;  // `world` runs per digit
             shape.prior_bits = {sbits};
-            return E.partition(nullptr, &X.ws, KW, CW, Lbits - sbits, sbits, false, nullptr, nullptr, &shape);
+            PartitionRequest rq = PartitionRequest::words(X.ws, KW, CW, Lbits - sbits);
+            rq.shift0 = sbits;
+            rq.shape = &shape;
+            return E.partition(rq);
         };
         // (what fails on ONE rank from here on — an allocation, a result beyond 2^32 rows — is kept and
         // reported with the next join's first status word, or at the end of the plan: the peers are

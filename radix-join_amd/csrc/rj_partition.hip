@@ -833,7 +833,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_pass_sample(TupleSrc s, PassPara
 // — a one-sided normal bound on a binomial count: for rows in random order a sub-range overflows with
 // probability Phi(-z).  start[] is the exclusive scan of cap in bin order (x minor under d: a digit's eight
 // sub-ranges stay adjacent), limit[] = start + cap, cursor[] = {start, cap}.  Nothing reaches beyond cap_max,
-// the tuples the host made room for from its bound on the sum (Exec::partition): a sub-range that would is cut
+// the tuples the host made room for from its bound on the sum (radix_cap_bound, rj_radix_plan.cpp): a sub-range that would is cut
 // there, and overflows like any other that is too small.
 __global__ __launch_bounds__(1024) void k_spec_caps(const uint32_t* sample, uint32_t nbins, uint32_t sample_log2, float z,
                                                     uint32_t cap_max, uint32_t* start, uint32_t* limit,
@@ -1125,7 +1125,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_spec_scatter_packed(Loader ld, P
 // ================================================== speculative last pass: sample, capacities, scatter, closing
 // (rj_device.hpp: LastParams.  Kernels of their own family names, k_last_*: every exact kernel and every kernel of
 // the speculative first pass keeps its name, its arguments and its machine code.)
-// k_last_sample: k_pass_hist of a later pass — its grid, a group table (of its own, see Exec::partition), xcd_remap
+// k_last_sample: k_pass_hist of a later pass — its grid, a group table (of its own, see sample_last in rj_radix.hip), xcd_remap
 // and LDS bins — over the input segments a speculative first pass left behind, but of every tile only one slice of PT_TILE >> sample_log2
 // consecutive keys is read, four keys per 16-byte load.  The slice's place moves from tile to tile as in
 // k_pass_sample; in a partial last tile of a segment it ends with the tile at the latest (its place is the
@@ -1184,7 +1184,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_last_sample(Loader ld, PassParam
 // partition, which stay adjacent), thread d = digit d.  LEVEL 0 leaves the segment's sum of capacities in
 // seg_sum[seg]; LEVEL 1 starts from the sum of the segments below and writes the exclusive scan — the partition's
 // begin, into pairs[2 i] of the {begin, end} pairs — limit[] = begin + capacity and cursor[] = begin.  Nothing reaches beyond cap_max, the tuples the
-// host made room for (Exec::partition): a partition that would is cut there and overflows like any other.
+// host made room for (radix_cap_bound, rj_radix_plan.cpp): a partition that would is cut there and overflows like any other.
 template <int LEVEL>
 __global__ __launch_bounds__(PT_MAXF) void k_last_caps(const uint32_t* sample, uint32_t nseg, uint32_t F, uint32_t sample_log2,
                                                        float z, uint32_t cap_max, unsigned long long* seg_sum,

@@ -82,7 +82,7 @@ __device__ __forceinline__ void stream_store(const OutStream& o, uint64_t row, u
 }
 
 // ============================================= tuples of a partitioned relation
-// One tuple of a partitioned relation (the layouts partition() writes: 12-byte tuples, 8-byte
+// One tuple of a partitioned relation (the layouts radix_partition() writes: 12-byte tuples, 8-byte
 // pairs, or word arrays whose last two carry words are one pair array).
 template <int KW, int CW>
 __device__ __forceinline__ void part_tuple(const Words& W, int pack, int aos, uint32_t idx, uint32_t (&t)[KW + CW]) {

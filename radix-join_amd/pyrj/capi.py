@@ -168,6 +168,7 @@ EXPORTS = [
     "rj_debug_sort_key_value",
     "rj_debug_fsum",
     "rj_debug_map_eval",
+    "rj_debug_partition_plan",
     "rj_table_num_rows",
     "rj_table_col_pages",
     "rj_table_copy_pages",
@@ -725,6 +726,61 @@ def map_eval(prog, row):
         L.rj_last_error.argtypes = [C.c_void_p]
         raise RjError(rc, (L.rj_last_error(None) or b"").decode())
     return [(int(ok[e]), int(ob[e]), bool(on[e])) for e in range(int(n_out.value))]
+
+
+class rj_partition_request(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("key_words", C.c_int32), ("carry_words", C.c_int32), ("bits", C.c_uint32), ("shift0", C.c_uint32),
+                ("single_pass", C.c_int32), ("word_source", C.c_int32), ("external", C.c_int32), ("composite", C.c_int32),
+                ("preseg_nseg", C.c_uint32), ("preseg_n_oseg", C.c_uint32), ("after_offsets", C.c_int32), ("flag_word", C.c_int32),
+                ("spec2_ok", C.c_int32)]
+
+
+class rj_partition_pass(C.Structure):
+    _fields_ = [("bits", C.c_uint32), ("tiles_per_group", C.c_uint32), ("xcd_log2", C.c_uint32), ("xcd_remap", C.c_uint32),
+                ("nseg_in", C.c_uint32), ("n_oseg", C.c_uint32), ("n_groups", C.c_uint32), ("offsets", C.c_int32), ("hist", C.c_int32),
+                ("scatter", C.c_int32), ("bins", C.c_uint64)]
+
+
+class rj_partition_plan(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("pbits", C.c_uint32 * 4), ("fine", C.c_int32), ("fine_xcd", C.c_int32), ("fine_grid", C.c_uint32),
+                ("mid", C.c_int32), ("last", C.c_int32), ("spec", C.c_int32), ("spec2", C.c_int32), ("spec_cap_max", C.c_uint64),
+                ("spec2_cap_max", C.c_uint64), ("n_first_out", C.c_uint64), ("n_last_out", C.c_uint64), ("tpg_first", C.c_uint32),
+                ("reserved", C.c_uint32), ("pass_", rj_partition_pass * 4)]
+
+
+# rj_plan_mid / rj_plan_last / rj_plan_offsets / rj_plan_hist / rj_plan_scatter (include/rj.h), by value
+PLAN_MID = ["dense", "packed", "packed_side", "blocked", "aos3", "aos3_side"]
+PLAN_LAST = ["dense", "packed", "aos3"]
+PLAN_OFFSETS = ["fine", "hist", "sample", "chunked"]
+PLAN_HIST = ["none", "fine_src", "fine_words", "src", "digits", "aos3", "blocked", "packed", "dense", "sample_src", "last_sample"]
+PLAN_SCATTER = ["src", "src_packed", "dense", "packed", "blocked", "aos3", "last_blocked", "last_dense"]
+
+
+def partition_plan(n, kw=1, cw=1, bits=0, *, cus=256, shift0=0, single_pass=False, word_source=0, external=False, composite=False,
+                   preseg=(0, 0), after_offsets=False, flag_word=False, spec2_ok=False) -> dict:
+    """rj_debug_partition_plan: the pass plan of one radix partition call (csrc/rj_radix_plan.cpp), under the RJ_TUNE_*
+    variables of the environment at the time of the call.  word_source: 0 columns, 1 word arrays, 2 packed pairs;
+    preseg: (input runs, output segments).  Enums come back as the names above.  Needs no GPU."""
+    L = load()
+    L.rj_debug_partition_plan.restype = C.c_int
+    L.rj_debug_partition_plan.argtypes = [C.POINTER(rj_partition_request), C.c_uint32, C.POINTER(rj_partition_plan)]
+    rq = rj_partition_request(int(n), kw, cw, bits, shift0, int(single_pass), int(word_source), int(external), int(composite),
+                              preseg[0], preseg[1], int(after_offsets), int(flag_word), int(spec2_ok))
+    out = rj_partition_plan()
+    rc = L.rj_debug_partition_plan(C.byref(rq), cus, C.byref(out))
+    if rc != 0:
+        raise RjError(rc, "rj_debug_partition_plan: bad request")
+    d = {k: int(getattr(out, k)) for k in ("passes", "fine_grid", "spec_cap_max", "spec2_cap_max", "n_first_out", "n_last_out", "tpg_first")}
+    d.update({k: bool(getattr(out, k)) for k in ("fine", "fine_xcd", "spec", "spec2")})
+    d["pbits"] = [int(out.pbits[p]) for p in range(d["passes"])]
+    d["mid"], d["last"] = PLAN_MID[out.mid], PLAN_LAST[out.last]
+    d["pass"] = []
+    for p in range(d["passes"]):
+        ps = out.pass_[p]
+        e = {k: int(getattr(ps, k)) for k in ("bits", "tiles_per_group", "xcd_log2", "xcd_remap", "nseg_in", "n_oseg", "n_groups", "bins")}
+        e["offsets"], e["hist"], e["scatter"] = PLAN_OFFSETS[ps.offsets], PLAN_HIST[ps.hist], PLAN_SCATTER[ps.scatter]
+        d["pass"].append(e)
+    return d
 
 
 def make_comm_id() -> bytes:

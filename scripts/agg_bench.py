@@ -38,7 +38,7 @@ AGG_TARGET, PT_MAXBITS = 384, 9  # rj_device.hpp: mean tuples per partition, rad
 
 
 def radix_passes(rows):
-    """Passes of the node's automatic bit plan (Exec::agg_bits, partition())."""
+    """Passes of the node's automatic bit plan (Exec::agg_bits, radix_plan())."""
     bits = min(max((max(-(-rows // AGG_TARGET), 1) - 1).bit_length(), 1), 21)
     return -(-bits // PT_MAXBITS)
 

@@ -8,11 +8,11 @@ Plain numpy and integers.  Nothing here is taken from the device code; every pie
                    (rj_device.hpp, PassParams::shift: "digit = (word0 >> shift) & (F-1)").  Rows that hold no tuple:
                    NULL keys, and NaN for FP64 (rj_partition.hip, above k_pass_sample: "NULL keys, rows behind the
                    relation's end and hashing are the scatter's"; SrcLoader::hash_keys: "NaN never matches")
-  bits per pass    rj_exec.hip, Exec::partition: passes = ceil(bits / 9), the bits split evenly, the first passes
+  bits per pass    rj_radix_plan.cpp, radix_plan: passes = ceil(bits / 9), the bits split evenly, the first passes
                    take the remainder (pbits)
   tiles, groups    tile t = rows [16384 t, 16384 (t + 1)); a group is tiles_per_group consecutive tiles, workgroup g
                    takes group g and "counts and writes into sub-range g & 7" (rj_device.hpp, PassParams::xcd_log2);
-                   tiles_per_group(n, 4096) is Exec::tiles_per_group, RJ_TUNE_TPG1 replaces it.  Bin of a tuple:
+                   tiles_per_group(n, 4096) is radix_tiles_per_group, RJ_TUNE_TPG1 replaces it.  Bin of a tuple:
                    (digit << 3) | (group & 7) (above k_pass_sample: "hist[(d << 3) | (blockIdx.x & 7)]")
   sample slice     above k_pass_sample: "of every tile only one slice of PT_TILE >> sample_log2 consecutive rows is
                    read ... The slice's place inside its tile moves with the tile index by 7 slices ... In a partial
@@ -24,7 +24,7 @@ Plain numpy and integers.  Nothing here is taken from the device code; every pie
                    32", start = exclusive scan in bin order, "Nothing reaches beyond cap_max ... a sub-range that
                    would is cut there".  z arrives as a float (launch_spec_caps' parameter), so it is rounded to
                    float32 first; the expression itself is evaluated in double
-  cap_max          rj_exec.hip, above `spec` in Exec::partition: C = tiles * (16384 >> s) sampled positions, B = 8 <<
+  cap_max          rj_radix_plan.cpp, radix_cap_bound and `spec`: C = tiles * (16384 >> s) sampled positions, B = 8 <<
                    pbits[0] sub-ranges, bound = 2^s (C + z sqrt(B (C + B)) + z^2 / 2 B) + 32 B, rounded up to a
                    multiple of 256
   the flag         rj_device.hpp, SpecParams::cursor: a tile reserves its c tuples with one add whatever comes back,

@@ -43,12 +43,12 @@ I32, I64, F64, VC = pl.INT32, pl.INT64, pl.FP64, pl.VARCHAR
 FAMILIES = ("k_join", "k_join_bcast", "k_pass_hist", "k_fine_hist", "k_pass_scatter", "k_pass_scatter_packed")
 
 # Compiled, but no plan can select them.  Both sides of a join are partitioned by the same
-# partition() code with the same radix bits, so the packed-pairs flag (PK bit 1 / 2: one key word +
+# radix_partition() code with the same radix bits, so the packed-pairs flag (PK bit 1 / 2: one key word +
 # one carry word, RJ_TUNE_PACK) and the 12-byte-tuple flag (PK bit 4 / 8: one key word + two carry
-# words, RJ_TUNE_AOS3) come out equal for two sides of equal carry width (rj_exec.hip partition():
+# words, RJ_TUNE_AOS3) come out equal for two sides of equal carry width (rj_radix_plan.cpp choose_layout():
 # P.packed / P.aos3 depend on KW, CW and context knobs only).  join_t compiles every subset of
 # CAN, so the one-sided subsets of a same-width pair are dead.
-_ONE_SIDED = "both sides have the same carry width, and partition() sets the {} flag from KW, CW and the knobs alone: one side cannot have it without the other"
+_ONE_SIDED = "both sides have the same carry width, and the radix plan sets the {} flag from KW, CW and the knobs alone: one side cannot have it without the other"
 UNREACHABLE = {
     f"k_join<1,1,1,{om},{pk},0>": _ONE_SIDED.format("packed-pairs")
     for om in (0, 1, 2) for pk in (1, 2)

@@ -25,7 +25,7 @@ Every row runs twice:
 
 VARCHAR keys.  A join on a VARCHAR key IS eligible: hash_varchar_keys (rj_exec.hip) replaces each side's key by a
 dense INT64 column of FNV-1a hashes and join_core then partitions both sides like any INT64 key, with the flag
-words — Exec::partition's `spec` condition asks nothing about the key's origin.  The keys are not `prehashed`
+words — radix_plan's `spec` condition (rj_radix_plan.cpp) asks nothing about the key's origin.  The keys are not `prehashed`
 (fmix64 is applied on top); both sides carry their row index (one carry word), so the row reaches k_pass_sample<2>
 and k_spec_scatter<3,SrcLoader<2,1,0>,-1> twice.  The model has no FNV-1a, so that row's no-fallback assertion rests
 on the random order of its rows alone.  `s.prehashed` in k_pass_sample is only ever set by rj_join_tuples (the

@@ -22,7 +22,7 @@ that the slice rotation takes twenty distinct values.
   b16 / b17 / b10         forced radix bits 16 (8 + 8: 2048 sub-ranges, k_spec_caps' threads take two each, F = 256 in
                           k_spec_close), 17 (9 + 8) and, with RJ_TUNE_FINE=0, 10 (5 + 5: 256 sub-ranges, fewer than
                           k_spec_caps has threads, F = 32); each taken and with z = 0.  All three leave `spec` true in
-                          Exec::partition: two passes, no fine histogram (16 and 17 are above its 15 bits, RJ_TUNE_FINE=0
+                          radix_plan (rj_radix_plan.cpp): two passes, no fine histogram (16 and 17 are above its 15 bits, RJ_TUNE_FINE=0
                           takes it from the 10-bit plan), nothing else of the condition depends on the bits
   tpg3                    RJ_TUNE_TPG1=3: groups of three tiles, sub-range x = (tile // 3) & 7
   i64                     INT64 keys, random, phase_in and phase_out: with the INT64 / FP64 rows of

@@ -1,5 +1,5 @@
 """The first radix pass without its histogram (csrc/rj_partition.hip: k_pass_sample, k_spec_caps, k_spec_scatter*,
-k_spec_close; csrc/rj_exec.hip: Exec::partition `spec`, repartition_exact).
+k_spec_close; csrc/rj_radix_plan.cpp: `spec`, csrc/rj_radix.hip: sample_first; csrc/rj_exec.hip: repartition_exact).
 
 A join's big two-pass plans size the 4096 output sub-ranges of the first pass from a 1/32 sample of the keys plus a
 safety margin, check the room in the scatter's reservation, and fall back to the exact histogram path when a

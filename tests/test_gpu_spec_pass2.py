@@ -1,5 +1,5 @@
 """The last radix pass of a big inner join without its histogram (csrc/rj_partition.hip: k_last_sample, k_last_caps,
-k_last_scatter*, k_last_close; csrc/rj_exec.hip: Exec::partition `spec2`, repartition_exact; csrc/rj_join.hip and
+k_last_scatter*, k_last_close; csrc/rj_radix_plan.cpp: `spec2`, csrc/rj_radix.hip: sample_last; csrc/rj_exec.hip: repartition_exact; csrc/rj_join.hip and
 k_heavy_tasks: a partition is [begin[q], end[q])).
 
 Behind a speculative first pass, an inner join's last pass sizes the final partitions from a sample of the first
