@@ -312,7 +312,8 @@ typedef enum rj_status {
  *
  * Window functions (ROW_NUMBER / RANK / DENSE_RANK and COUNT / SUM / MIN / MAX ... OVER (PARTITION BY
  * ... ORDER BY ...); no reference counterpart).
- * RJ_NODE_WINDOW has ONE child, `left`; `build_left` and `base_table_id` are ignored.
+ * RJ_NODE_WINDOW has ONE child, `left`; `build_left` is ignored, and so is `base_table_id` unless an
+ * output's function is RJ_WIN_LAG or above (the section behind this one).
  *   Keys: rj_node cannot grow, so RJ_WINDOW_N_KEYS(node) = `right` is the total number of keys
  *   (0 .. RJ_SORT_MAX_KEYS), RJ_WINDOW_KEYS(node) = `right_attr` a `const rj_sort_key*` that stays
  *   valid during the call, and RJ_WINDOW_N_PART(node) = `left_attr` says how many of them, the first
@@ -354,18 +355,72 @@ typedef enum rj_status {
  *   types and zero pages.  With no key at all there is one partition of all rows, in the child's
  *   order, and nothing is sorted.
  *   RJ_ERR_ARG: n_part > n_keys; a key or output column out of range; flag bits other than the two
- *   defined ones; n_keys != 0 with a NULL pointer; a function code above RJ_WIN_MAX; a ranking
+ *   defined ones; n_keys != 0 with a NULL pointer; a function code that rj_win_func does not define; a ranking
  *   function or RJ_WIN_COUNT_STAR with a column other than 0; a declared type other than the table
  *   above says (for RJ_WIN_COL the child column's type).
  *   RJ_ERR_UNSUPPORTED: a VARCHAR key; a VARCHAR column under a function (it travels as a row id);
  *   SUM over an FP64 column (it depends on the order of the rows); more than RJ_SORT_MAX_KEYS keys in
  *   total; more than 2^32 - 16 child rows.  The node is checked before its child's rows are looked
  *   at: an empty child does not hide an error.
- *   Out of scope: ROWS and every explicit frame; LAG / LEAD / FIRST_VALUE / NTILE; VARCHAR anywhere but
- *   passing through; sharding.
+ *   Out of scope: RANGE and GROUPS frames with offsets; EXCLUDE; NTH_VALUE; IGNORE NULLS; a default
+ *   for LAG / LEAD; VARCHAR anywhere but passing through; sharding.
  *   rj_execute_sharded refuses plans that hold the kind (RJ_ERR_UNSUPPORTED), rj_plan_shardable
  *   reports it, and rj_execute on a multi-device context runs such a plan on its first device.  A
  *   library older than this kind rejects it with RJ_ERR_ARG ("bad node kind").
+ *
+ * ROWS frames and LAG / LEAD / FIRST_VALUE / NTILE (further functions of RJ_NODE_WINDOW; no reference
+ * counterpart).  One node may hold any mix of the functions above and of these; everything the
+ * section above says about keys, partitions, the order of the result and sharding holds unchanged.
+ *   Arguments: rj_node cannot grow, so RJ_WINDOW_ARGS(node) = `base_table_id` is a `const rj_win_arg*`
+ *   to n_out entries, entry k for output k, valid during the call.  It is read ONLY when some output's
+ *   function is RJ_WIN_LAG or above, and then only the entries of those outputs; for every other plan
+ *   the field stays ignored.  The same (function, column) may appear several times with different
+ *   arguments, each an output of its own.
+ *   Positions: position i = 0, 1, ... counts the rows in the node's order — by (partition keys,
+ *   order keys), ties stable with respect to the child's order on the device.  The row at position i
+ *   lies in the partition [ps, pe].  As for ROW_NUMBER, a result that depends on the order among
+ *   peers (every function of this section can) is fully determined over a SCAN child and unspecified
+ *   among peers over any other child.
+ *   Frame: ROWS BETWEEN lo AND hi, both as SIGNED OFFSETS from the current row: negative = PRECEDING,
+ *   0 = CURRENT ROW, positive = FOLLOWING, RJ_WIN_UNBOUNDED_PRECEDING (INT64_MIN) and
+ *   RJ_WIN_UNBOUNDED_FOLLOWING (INT64_MAX).  The frame of position i is the positions [a, b] with
+ *   a = max(ps, i + lo) and b = min(pe, i + hi); it is EMPTY when a > b (ROWS BETWEEN 3 PRECEDING AND
+ *   1 PRECEDING at a partition's first row).  No offset overflows: any offset beyond +-2^32 acts as
+ *   unbounded, a relation having fewer than 2^32 - 16 rows (rj_debug_win_frame is this arithmetic).
+ *   A frame never leaves the partition and never looks at peers: it counts rows.
+ *     RJ_WIN_LAG / RJ_WIN_LEAD  arg.lo = k >= 0, arg.hi = 0: the value of the column at position i - k
+ *                        (LAG) or i + k (LEAD) if that lies in [ps, pe], else NULL; k = 0 is the row
+ *                        itself and any k up to INT64_MAX is legal.  The column's type, the value's own
+ *                        bits (nothing is canonicalised), always nullable.  There is no default argument:
+ *                        an RJ_X_COALESCE in a MAP above supplies one, and a NULL source value and a
+ *                        missing row then look alike.
+ *     RJ_WIN_FIRST_VALUE / RJ_WIN_LAST_VALUE  arg = the frame: the value of the column at a / at b; NULL
+ *                        if the frame is empty or that value is NULL.  The column's type, the value's own
+ *                        bits, always nullable.
+ *     RJ_WIN_NTILE       column must be 0, arg.lo = n >= 1, arg.hi = 0; INT64, never NULL.  PostgreSQL's
+ *                        rule: with N = pe - ps + 1 rows in the partition, r = i - ps, q = N / n and
+ *                        m = N % n the first m buckets hold q + 1 rows and the rest q, so the bucket is
+ *                        r / (q + 1) + 1 for r < m (q + 1) and m + (r - m (q + 1)) / q + 1 otherwise;
+ *                        n > N gives the buckets 1 .. N (rj_debug_win_ntile is this arithmetic).
+ *     RJ_WIN_ROWS_COUNT_STAR  arg = the frame: its rows; column must be 0; INT64, never NULL
+ *     RJ_WIN_ROWS_COUNT  non-NULL values of an INT32 / INT64 / FP64 column in the frame; INT64, never NULL
+ *     RJ_WIN_ROWS_SUM    sum of the non-NULL values of an INT32 / INT64 column in the frame, wrapping
+ *                        modulo 2^64; INT64; NULL if the frame has no non-NULL value
+ *     RJ_WIN_ROWS_MIN / RJ_WIN_ROWS_MAX  over the non-NULL values of an INT32 / INT64 / FP64 column in the
+ *                        frame; the column's type; NULL if the frame has none.  FP64 orders by the sort
+ *                        encoding and the result is the canonical value, as for RJ_WIN_MIN / RJ_WIN_MAX.
+ *   An empty frame gives COUNT 0 and NULL for SUM / MIN / MAX; NULL is decided by the count of non-NULL
+ *   values, never by a sentinel: an INT64_MAX under MIN next to NULLs comes out as a value.  A ROWS_SUM /
+ *   ROWS_MIN / ROWS_MAX column is nullable when the child column is, or when the frame can miss the
+ *   current row (lo > 0 or hi < 0): the plan decides that, never the data.
+ *   RJ_ERR_ARG: a function of this section with a NULL RJ_WINDOW_ARGS; a frame with lo > hi, with lo =
+ *   RJ_WIN_UNBOUNDED_FOLLOWING or with hi = RJ_WIN_UNBOUNDED_PRECEDING; LAG / LEAD with k < 0 or arg.hi
+ *   != 0; NTILE with n < 1 or arg.hi != 0; NTILE or ROWS_COUNT_STAR with a column other than 0; a column
+ *   out of range; a declared type other than the rules above give; a function code that rj_win_func
+ *   does not define (9 .. 15, and everything above RJ_WIN_ROWS_MAX).
+ *   RJ_ERR_UNSUPPORTED: a VARCHAR column under any function of this section (a row id cannot say
+ *   NULL, and its pages are not read here); ROWS_SUM over an FP64 column.
+ *   As above the node is checked before its child's rows are looked at.
  *
  * Computed columns (scalar expressions in a select list or under an aggregate; no reference counterpart).
  * RJ_NODE_MAP has ONE child, `left`; `build_left`, `base_table_id` and `left_attr` are ignored.
@@ -554,11 +609,23 @@ typedef enum rj_win_func {
     RJ_WIN_COUNT      = 5,
     RJ_WIN_SUM        = 6,
     RJ_WIN_MIN        = 7,
-    RJ_WIN_MAX        = 8
+    RJ_WIN_MAX        = 8,
+    /* 9 .. 15 are not assigned.  The functions below take an rj_win_arg each (RJ_WINDOW_ARGS). */
+    RJ_WIN_LAG = 16, RJ_WIN_LEAD = 17, RJ_WIN_FIRST_VALUE = 18, RJ_WIN_LAST_VALUE = 19, RJ_WIN_NTILE = 20,
+    RJ_WIN_ROWS_COUNT_STAR = 21, RJ_WIN_ROWS_COUNT = 22, RJ_WIN_ROWS_SUM = 23, RJ_WIN_ROWS_MIN = 24, RJ_WIN_ROWS_MAX = 25
 } rj_win_func;
 #define RJ_WIN_OUT(func, col) (((uint64_t)(func) << 56) | (uint64_t)(col))
 #define RJ_WIN_FUNC(x) ((uint32_t)((uint64_t)(x) >> 56))
 #define RJ_WIN_COL(x) ((uint64_t)(x) & 0x00ffffffffffffffull)
+
+/* The argument of one output of an RJ_NODE_WINDOW node whose function is RJ_WIN_LAG or above: a ROWS
+ * frame BETWEEN lo AND hi as signed offsets from the current row (negative = PRECEDING), the offset k
+ * of LAG / LEAD in lo, the bucket count of NTILE in lo.  RJ_WINDOW_ARGS(node) points to n_out of
+ * them, entry k for output k, and is read only when such a function is present. */
+typedef struct rj_win_arg { int64_t lo, hi; } rj_win_arg;
+#define RJ_WIN_UNBOUNDED_PRECEDING INT64_MIN
+#define RJ_WIN_UNBOUNDED_FOLLOWING INT64_MAX
+#define RJ_WINDOW_ARGS(node) ((const rj_win_arg*)(uintptr_t)(node)->base_table_id)
 
 /* The program of an RJ_NODE_MAP node (`node`: a const rj_node*) and the encoding of its out_idx values
  * (the bit layout of RJ_AGG_OUT). */
@@ -772,6 +839,16 @@ int rj_debug_sort_key(int32_t type, int32_t flags, uint64_t bits, int is_null, u
  * context nor a GPU (an INT32 key is its low 32 bits).  RJ_ERR_ARG: another type, other flag bits, a
  * NULL pointer.                                                                                     */
 int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t* bits);
+/* The frame arithmetic of RJ_NODE_WINDOW's ROWS frames, run on the host (the k_frame_* kernels share the
+ * code): the row at position i of a partition [ps, pe] (all three below 2^32) under ROWS BETWEEN lo
+ * AND hi as signed offsets.  -> 1 and the frame [*a, *b] = [max(ps, i + lo), min(pe, i + hi)], or 0
+ * when that is empty (a and b are then untouched) or a pointer is NULL.  Needs neither a context nor
+ * a GPU.                                                                                             */
+int rj_debug_win_frame(uint64_t i, uint64_t ps, uint64_t pe, int64_t lo, int64_t hi, uint64_t* a, uint64_t* b);
+/* RJ_WIN_NTILE on the host (the kernel shares the code): the bucket, 1-based, of the row that has r
+ * rows of its partition in front of it, the partition having N rows, under NTILE(n).  -> 0 for n < 1
+ * or r >= N.  Needs neither a context nor a GPU.                                                      */
+int64_t rj_debug_win_ntile(uint64_t r, uint64_t N, int64_t n);
 /* RJ_AGG_FSUM of ONE group, run on the host through the add, merge and round functions the kernels
  * call, in blocks of a few thousand values merged as the kernels merge their partial sums: bits[i] =
  * the bits of value i, is_null[i] != 0 = NULL (is_null may be NULL: no NULLs).  *out_bits = the exactly

@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "rj_frame.hpp"
 #include "rj_fsum.hpp"
 #include "rj_internal.hpp"
 #include "rj_radix_plan.hpp"
@@ -197,6 +198,16 @@ int rj_debug_sort_key_value(int32_t type, int32_t flags, uint64_t key, uint64_t*
     if (type != RJ_INT32 && type != RJ_INT64 && type != RJ_FP64) return RJ_ERR_ARG;
     *bits = rj::sort_key_value(key, type == RJ_INT32 ? 4 : 8, type == RJ_FP64, (flags & RJ_SORT_DESC) != 0);
     return RJ_OK;
+}
+
+int rj_debug_win_frame(uint64_t i, uint64_t ps, uint64_t pe, int64_t lo, int64_t hi, uint64_t* a, uint64_t* b) {
+    if (!a || !b) return 0;
+    return rj::frame_bounds(i, ps, pe, lo, hi, *a, *b) ? 1 : 0;
+}
+
+int64_t rj_debug_win_ntile(uint64_t r, uint64_t N, int64_t n) {
+    if (n < 1 || r >= N) return 0;
+    return rj::frame_ntile(r, N, n);
 }
 
 int rj_debug_fsum(const uint64_t* bits, const uint8_t* is_null, uint64_t n, uint64_t* out_bits, int32_t* out_is_null) {

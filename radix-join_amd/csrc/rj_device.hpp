@@ -564,6 +564,28 @@ struct WinScan {
     unsigned long long* mx;
 };
 
+// ---- ROWS frames, LAG / LEAD / FIRST_VALUE / LAST_VALUE and NTILE of RJ_NODE_WINDOW (rj_frame.hip): every
+// position knows its partition [ps, pe] from a k_win_ranks launch with Q := P (ROW_NUMBER gives ps,
+// the peer end gives pe); a frame is two positions (rj_frame.hpp).  COUNT / SUM are differences of two
+// entries of WinScan.  MIN / MAX read a RANGE-EXTREME TREE over the encoded values in the order: level
+// 0 has one word per position (a NULL is the identity), level k + 1 one word per FRAME_FANOUT words of
+// level k (the extreme of that aligned block), up to the first level of at most FRAME_FANOUT words; the
+// levels lie one behind the other in ONE array, so that a level's offset and length follow from the one
+// below it by arithmetic and no kernel indexes an array of pointers.  Above level 0 that is fewer than
+// n / (FRAME_FANOUT - 1) + 8 words.
+constexpr int FRAME_FANOUT = 16;
+constexpr int FRAME_THREADS = 256;  // a workgroup of the tree's build: FRAME_FANOUT^2 words of a level -> two levels
+static_assert(FRAME_THREADS == FRAME_FANOUT * FRAME_FANOUT && 64 % FRAME_FANOUT == 0, "a block of a level sits in one wave");
+// which end of the frame k_frame_pick reads
+enum FramePick : int32_t { FRAME_FIRST = 0, FRAME_LAST = 1 };
+// what k_frame_sum writes
+enum FrameSum : int32_t { FRAME_COUNT_STAR = 0, FRAME_COUNT = 1, FRAME_SUM = 2 };
+// every position's partition, as k_win_ranks leaves it
+struct FrameRows {
+    const unsigned long long* row_number;  // ps = i + 1 - row_number[i]
+    const uint32_t*           part_end;    // pe
+};
+
 // ---- Set operations (RJ_NODE_SETOP): the rows of both children in one relation (row id < n_left: a
 // left row), ordered and cut into runs by the sort's and the grouping's kernels; a run's rows and left
 // rows are differences of two prefix counts taken at its head and at the next run's, its multiplicity

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <functional>
 #include <set>
+#include <tuple>
 
 #include "rj_expr.hpp"
 #include "rj_internal.hpp"
@@ -1996,10 +1997,55 @@ class Exec {
     // kernels (rj_window.hip) turn the two masks into the ranks and every row's peer end, and scan one
     // value column per set of launches.  The passed-through columns are gathered through the permutation
     // as a sort's (emit_rows).  Host syncs: those of sort_column only — the result has the child's rows.
+    // The functions from RJ_WIN_LAG on (ROWS frames, LAG / LEAD / FIRST_VALUE / LAST_VALUE, NTILE) sit on top:
+    // a second k_win_ranks launch with Q := P gives every position its partition, and the k_frame_* kernels
+    // (rj_frame.hip) pick a row, subtract two entries of the scan or walk a range-extreme tree per frame
+    // (frame_column).  A plan without such a function launches and allocates what it did without them.
     struct WinCol {
         bool want_sum = false, want_mn = false, want_mx = false;
-        BufP nn, sum, mn, mx;
+        bool want_tree_mn = false, want_tree_mx = false;  // ROWS_MIN / ROWS_MAX: the range-extreme trees (rj_frame.hip)
+        BufP nn, sum, mn, mx, tree_mn, tree_mx;
     };
+    // One result column of a function from RJ_WIN_LAG on (the k_frame_* kernels, rj_frame.hip) over the
+    // frame [lo, hi]; `w`: the scans and trees of the value column, for the ROWS aggregates.
+    DCol frame_column(const Rel& child, uint32_t func, int col, int64_t lo, int64_t hi, int32_t type, uint32_t rows, const uint32_t* dperm,
+                      const FrameRows& fr, const WinCol* w) {
+        using ull = unsigned long long;
+        if (func == RJ_WIN_NTILE) {
+            const DCol d = new_col(type, rows, false);
+            launch_frame_ntile(L, rows, fr, lo, d.hold->as<ull>());
+            return d;
+        }
+        if (func == RJ_WIN_ROWS_COUNT_STAR) {
+            const DCol d = new_col(type, rows, false);
+            launch_frame_sum(L, nullptr, nullptr, rows, fr, lo, hi, FRAME_COUNT_STAR, d.hold->as<ull>(), nullptr);
+            return d;
+        }
+        const DCol& c = child.cols[(size_t)col];
+        if (func <= RJ_WIN_LAST_VALUE) {  // LAG, LEAD, FIRST_VALUE, LAST_VALUE: always nullable
+            const DCol d = new_col(type, rows, true);
+            launch_frame_pick(L, c.ref(), dperm, rows, fr, lo, hi, func == RJ_WIN_LAST_VALUE ? FRAME_LAST : FRAME_FIRST, d.hold->as<uint8_t>(),
+                              d.hold_valid->as<uint8_t>());
+            return d;
+        }
+        if (func == RJ_WIN_ROWS_COUNT) {
+            const DCol d = new_col(type, rows, false);
+            launch_frame_sum(L, ptr<uint32_t>(w->nn), nullptr, rows, fr, lo, hi, FRAME_COUNT, d.hold->as<ull>(), nullptr);
+            return d;
+        }
+        // NULL where the frame has no non-NULL value: a nullable column's frames can, and a frame that can miss the current row
+        const DCol d = new_col(type, rows, c.valid != nullptr || lo > 0 || hi < 0);
+        if (func == RJ_WIN_ROWS_SUM) {
+            launch_frame_sum(L, ptr<uint32_t>(w->nn), ptr<ull>(w->sum), rows, fr, lo, hi, FRAME_SUM, d.hold->as<ull>(), ptr<uint8_t>(d.hold_valid));
+        } else {
+            const bool is_max = func == RJ_WIN_ROWS_MAX;
+            const int  decode = c.type == RJ_FP64 ? GROUP_KEYF64 : (c.type == RJ_INT32 ? GROUP_KEY32 : GROUP_KEY64);
+            launch_frame_extreme(L, ptr<ull>(is_max ? w->tree_mx : w->tree_mn), ptr<uint32_t>(w->nn), rows, fr, lo, hi, is_max, decode, d.width,
+                                 d.hold->as<uint8_t>(), ptr<uint8_t>(d.hold_valid));
+        }
+        return d;
+    }
+
     Rel window(Rel& child, const rj_node& n, Result* root_res) {
         const size_t   cw = child.cols.size();
         const uint64_t n_keys = RJ_WINDOW_N_KEYS(&n), n_part = RJ_WINDOW_N_PART(&n);
@@ -2019,19 +2065,44 @@ class Exec {
         struct Out {
             uint32_t func;
             int      col;
+            int64_t  lo, hi;  // from RJ_WIN_LAG on: the frame (LAG / LEAD k as the frame [-k, -k] / [k, k]); NTILE: lo = n
         };
         std::vector<Out>      outs;
         std::map<int, WinCol> agg;  // per distinct value column
         bool                  want[RJ_WIN_COUNT_STAR + 1] = {false, false, false, false, false};
+        bool                  any_frame = false;  // a function that needs every position's partition
+        bool                  any_peer = false;   // ... every position's peer end: an aggregate under the default frame
+        const rj_win_arg*     args = nullptr;
         for (uint64_t k = 0; k < n.n_out; ++k) {
             const uint32_t func = RJ_WIN_FUNC(n.out_idx[k]);
             const uint64_t col = RJ_WIN_COL(n.out_idx[k]);
-            if (func > RJ_WIN_MAX) throw_fmt(RJ_ERR_ARG, "window: unknown function code %u", func);
+            if (func > RJ_WIN_ROWS_MAX || (func > RJ_WIN_MAX && func < RJ_WIN_LAG)) throw_fmt(RJ_ERR_ARG, "window: unknown function code %u", func);
             int32_t expect = RJ_INT64;
+            Out     o{func, (int)col, 0, 0};
+            if (func >= RJ_WIN_LAG) {
+                if (!args) args = RJ_WINDOW_ARGS(&n);
+                if (!args) throw_fmt(RJ_ERR_ARG, "window: function code %u takes an argument but RJ_WINDOW_ARGS is NULL", func);
+                o.lo = args[k].lo, o.hi = args[k].hi;
+                any_frame = true;
+            }
+            if (func == RJ_WIN_LAG || func == RJ_WIN_LEAD) {
+                if (o.lo < 0 || o.hi != 0)
+                    throw_fmt(RJ_ERR_ARG, "window: LAG / LEAD take an offset k >= 0 in arg.lo and 0 in arg.hi (output %llu)", (unsigned long long)k);
+                o.lo = o.hi = func == RJ_WIN_LAG ? -o.lo : o.lo;
+            } else if (func == RJ_WIN_NTILE) {
+                if (o.lo < 1 || o.hi != 0)
+                    throw_fmt(RJ_ERR_ARG, "window: NTILE takes a bucket count n >= 1 in arg.lo and 0 in arg.hi (output %llu)", (unsigned long long)k);
+            } else if (func >= RJ_WIN_LAG) {
+                if (o.lo > o.hi || o.lo == RJ_WIN_UNBOUNDED_FOLLOWING || o.hi == RJ_WIN_UNBOUNDED_PRECEDING)
+                    throw_fmt(RJ_ERR_ARG, "window: bad frame (output %llu): lo > hi, lo = UNBOUNDED FOLLOWING or hi = UNBOUNDED PRECEDING",
+                              (unsigned long long)k);
+            }
             if (func >= RJ_WIN_ROW_NUMBER && func <= RJ_WIN_COUNT_STAR) {
                 if (col != 0)
                     throw_fmt(RJ_ERR_ARG, "window: %s takes no column", func == RJ_WIN_COUNT_STAR ? "COUNT(*)" : "a ranking function");
                 want[func] = true;
+            } else if (func == RJ_WIN_NTILE || func == RJ_WIN_ROWS_COUNT_STAR) {
+                if (col != 0) throw_fmt(RJ_ERR_ARG, "window: %s takes no column", func == RJ_WIN_NTILE ? "NTILE" : "COUNT(*)");
             } else {
                 if (col >= cw) throw_fmt(RJ_ERR_ARG, "window: output attr out of range");
                 const DCol& c = child.cols[col];
@@ -2041,18 +2112,25 @@ class Exec {
                     if (c.type == RJ_VARCHAR)
                         throw_fmt(RJ_ERR_UNSUPPORTED, "window: function over a VARCHAR column (child column %llu): a VARCHAR value "
                                                       "travels as a row id, its pages are not read here", (unsigned long long)col);
-                    if (func == RJ_WIN_SUM && c.type == RJ_FP64)
+                    if ((func == RJ_WIN_SUM || func == RJ_WIN_ROWS_SUM) && c.type == RJ_FP64)
                         throw_fmt(RJ_ERR_UNSUPPORTED, "window: SUM over an FP64 column (child column %llu): a floating-point sum depends "
                                                       "on the order of the rows", (unsigned long long)col);
-                    if (func == RJ_WIN_MIN || func == RJ_WIN_MAX) expect = c.type;
-                    WinCol& w = agg[(int)col];
-                    w.want_sum = w.want_sum || func == RJ_WIN_SUM;
-                    w.want_mn = w.want_mn || func == RJ_WIN_MIN;
-                    w.want_mx = w.want_mx || func == RJ_WIN_MAX;
+                    if (func == RJ_WIN_MIN || func == RJ_WIN_MAX || func == RJ_WIN_ROWS_MIN || func == RJ_WIN_ROWS_MAX ||
+                        (func >= RJ_WIN_LAG && func <= RJ_WIN_LAST_VALUE))
+                        expect = c.type;
+                    if (func < RJ_WIN_LAG || func >= RJ_WIN_ROWS_COUNT) {  // (the running count, and what else the function reads)
+                        WinCol& w = agg[(int)col];
+                        any_peer = any_peer || func < RJ_WIN_LAG;
+                        w.want_sum = w.want_sum || func == RJ_WIN_SUM || func == RJ_WIN_ROWS_SUM;
+                        w.want_mn = w.want_mn || func == RJ_WIN_MIN;
+                        w.want_mx = w.want_mx || func == RJ_WIN_MAX;
+                        w.want_tree_mn = w.want_tree_mn || func == RJ_WIN_ROWS_MIN;
+                        w.want_tree_mx = w.want_tree_mx || func == RJ_WIN_ROWS_MAX;
+                    }
                 }
             }
             if (n.out_type[k] != expect) throw_fmt(RJ_ERR_ARG, "window: declared type differs from the function's result type");
-            outs.push_back(Out{func, (int)col});
+            outs.push_back(o);
         }
         check_rows(child);
         if (child.n == 0) return empty_rel(n, root_res);
@@ -2070,6 +2148,7 @@ class Exec {
         const uint32_t max_chunk = ctx->tune.win_grid > 0 ? (uint32_t)ctx->tune.win_grid : 0u;
         const uint32_t n_quarters = rows / WIN_QUARTER + (rows % WIN_QUARTER != 0);
         BufP           P, Q, rank_col[RJ_WIN_COUNT_STAR + 1], peer_end;
+        BufP           part_rowno, part_end;  // every position's partition [i + 1 - part_rowno[i], part_end[i]]
         using ull = unsigned long long;
         if (any_func) {
             const uint64_t mask_bytes = ((uint64_t)rows + 63) / 64 * 8;
@@ -2090,14 +2169,29 @@ class Exec {
             }
             for (uint32_t f = RJ_WIN_ROW_NUMBER; f <= RJ_WIN_COUNT_STAR; ++f)
                 if (want[f]) rank_col[f] = ctx->buf((uint64_t)rows * 8);
-            if (!agg.empty()) peer_end = ctx->buf((uint64_t)rows * 4);
+            // the partitions of the frame layer: k_win_ranks with Q := P, where ROW_NUMBER gives the
+            // partition's start and the peer end its end.  Without order keys Q is P: this launch serves.
+            const bool ranks_serve = any_frame && order_cols.empty();
+            if (ranks_serve && !rank_col[RJ_WIN_ROW_NUMBER]) rank_col[RJ_WIN_ROW_NUMBER] = ctx->buf((uint64_t)rows * 8);
+            if (any_peer || ranks_serve) peer_end = ctx->buf((uint64_t)rows * 4);
             BufP           marks[4];
             for (BufP& b : marks) b = ctx->buf((uint64_t)n_quarters * 4);
             const WinMarks m{ptr<uint32_t>(marks[0]), ptr<uint32_t>(marks[1]), ptr<uint32_t>(marks[2]), ptr<uint32_t>(marks[3])};
             const WinRanks r{ptr<ull>(rank_col[RJ_WIN_ROW_NUMBER]), ptr<ull>(rank_col[RJ_WIN_RANK]), ptr<ull>(rank_col[RJ_WIN_DENSE_RANK]),
                              ptr<ull>(rank_col[RJ_WIN_COUNT_STAR]), ptr<uint32_t>(peer_end)};
             launch_win_ranks(L, ptr<ull>(P), ptr<ull>(Q), rows, m, r, max_chunk);
+            if (ranks_serve) {
+                part_rowno = rank_col[RJ_WIN_ROW_NUMBER], part_end = peer_end;
+            } else if (any_frame) {
+                part_rowno = ctx->buf((uint64_t)rows * 8), part_end = ctx->buf((uint64_t)rows * 4);
+                BufP marks2[4];
+                for (BufP& b : marks2) b = ctx->buf((uint64_t)n_quarters * 4);
+                const WinMarks m2{ptr<uint32_t>(marks2[0]), ptr<uint32_t>(marks2[1]), ptr<uint32_t>(marks2[2]), ptr<uint32_t>(marks2[3])};
+                launch_win_ranks(L, ptr<ull>(P), ptr<ull>(P), rows, m2, WinRanks{ptr<ull>(part_rowno), nullptr, nullptr, nullptr, ptr<uint32_t>(part_end)},
+                                 max_chunk);
+            }
         }
+        const FrameRows frame_rows{ptr<ull>(part_rowno), ptr<uint32_t>(part_end)};
 
         // ---- the scans: one set of launches per distinct value column
         for (auto& kv : agg) {
@@ -2112,22 +2206,35 @@ class Exec {
             const WinTails tails{ptr<uint32_t>(t_head), ptr<uint32_t>(t_nn), ptr<ull>(t_sum), ptr<ull>(t_mn), ptr<ull>(t_mx)};
             const WinScan  scan{ptr<uint32_t>(w.nn), ptr<ull>(w.sum), ptr<ull>(w.mn), ptr<ull>(w.mx)};
             launch_win_scan(L, c.ref(), dperm, rows, c.type == RJ_FP64, ptr<ull>(P), tails, scan, max_chunk);
+            // ROWS_MIN / ROWS_MAX: one range-extreme tree per (value column, MIN or MAX), shared by all its frames
+            if (w.want_tree_mn) {
+                w.tree_mn = ctx->buf(frame_tree_words(rows) * 8);
+                launch_frame_tree(L, c.ref(), dperm, rows, c.type == RJ_FP64, false, ptr<ull>(w.tree_mn));
+            }
+            if (w.want_tree_mx) {
+                w.tree_mx = ctx->buf(frame_tree_words(rows) * 8);
+                launch_frame_tree(L, c.ref(), dperm, rows, c.type == RJ_FP64, true, ptr<ull>(w.tree_mx));
+            }
         }
 
         // ---- the output columns: a passed-through column is gathered once; a function column named several times is
         // made once (func_cols) and, at the root, encoded per output
-        Sink                     sink(this, root_res, rows);
-        std::map<uint64_t, DCol> func_cols;
+        // (func_cols; a function from RJ_WIN_LAG on is the same column only under the same argument)
+        Sink sink(this, root_res, rows);
+        std::map<std::tuple<uint64_t, int64_t, int64_t>, DCol> func_cols;
         for (size_t k = 0; k < outs.size(); ++k) {
-            const Out&     o = outs[k];
-            const uint64_t id = n.out_idx[k];
+            const Out& o = outs[k];
             if (o.func == RJ_WIN_COL) {  // (then the id is the plain column index)
-                emit_rows(child, &id, 1, perm, dperm, sink);
+                emit_rows(child, &n.out_idx[k], 1, perm, dperm, sink);
                 continue;
             }
+            const auto id = std::make_tuple(n.out_idx[k], o.lo, o.hi);
             if (!func_cols.count(id)) {
                 if (o.func <= RJ_WIN_COUNT_STAR) {
                     func_cols[id] = dense_col(n.out_type[k], rank_col[o.func]);
+                } else if (o.func >= RJ_WIN_LAG) {
+                    func_cols[id] = frame_column(child, o.func, o.col, o.lo, o.hi, n.out_type[k], rows, dperm, frame_rows,
+                                                 agg.count(o.col) ? &agg.at(o.col) : nullptr);
                 } else {
                     const WinCol& w = agg.at(o.col);
                     const DCol&   c = child.cols[(size_t)o.col];

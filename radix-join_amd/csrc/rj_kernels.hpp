@@ -15,7 +15,7 @@
 //   K8  page finish/encode  rj_pages.hip      Page headers + validity bitmaps of the result
 // The other node kinds build on these: rj_filter.hip (semi / anti joins), rj_outer.hip, rj_full.hip (outer and full
 // outer joins), rj_agg.hip (hash aggregation), rj_select.hip, rj_map.hip, rj_sort.hip, rj_group.hip, rj_fsum.hip,
-// rj_window.hip, rj_setop.hip; rj_varchar_dev.hip holds the VARCHAR kernels.
+// rj_window.hip, rj_frame.hip, rj_setop.hip; rj_varchar_dev.hip holds the VARCHAR kernels.
 // Reference counterparts are cited at each kernel (paths relative to the reference).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -341,6 +341,28 @@ void launch_win_scan(const Launch& L, const ColRef& col, const uint32_t* perm, u
 // decode = GroupDecode; validity bytes nn[peer_end[i]] != 0 where dst_valid is given, the value of a NULL is 0
 void launch_win_column(const Launch& L, const unsigned long long* src, const uint32_t* nn, const uint32_t* peer_end, uint64_t n, int decode,
                        int width, uint8_t* dst, uint8_t* dst_valid);
+
+// ======================================================================================================== rj_frame.hip
+// ---- the frame layer of RJ_NODE_WINDOW (rj_frame.hip): `rows` = every position's partition (k_win_ranks
+// with Q := P), lo / hi = ROWS BETWEEN lo AND hi as signed offsets (any int64_t: rj_frame.hpp clamps them)
+// k_frame_pick: row i = the value of `col` (through perm) at the frame's first or last position (end =
+// FramePick), its own bits; validity bytes 0 where the frame is empty or the value NULL
+void launch_frame_pick(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, const FrameRows& rows, int64_t lo, int64_t hi,
+                       int end, uint8_t* dst, uint8_t* dst_valid);
+// k_frame_ntile: NTILE(buckets), buckets >= 1
+void launch_frame_ntile(const Launch& L, uint32_t n_rows, const FrameRows& rows, int64_t buckets, unsigned long long* dst);
+// k_frame_sum: what = FrameSum over the frame, from the scan's running count nn and running sum (the
+// latter for FRAME_SUM only, neither for FRAME_COUNT_STAR); dst_valid optional
+void launch_frame_sum(const Launch& L, const uint32_t* nn, const unsigned long long* sum, uint32_t n_rows, const FrameRows& rows, int64_t lo,
+                      int64_t hi, int what, unsigned long long* dst, uint8_t* dst_valid);
+// the words of a range-extreme tree over n_rows positions, level 0 included
+uint64_t frame_tree_words(uint64_t n_rows);
+// k_frame_leaves, k_frame_levels: the tree of `col` under MIN or MAX
+void launch_frame_tree(const Launch& L, const ColRef& col, const uint32_t* perm, uint32_t n_rows, bool f64, bool is_max,
+                       unsigned long long* tree);
+// k_frame_extreme: MIN / MAX over the frame from the tree, NULL where the count nn says so; decode = GroupDecode
+void launch_frame_extreme(const Launch& L, const unsigned long long* tree, const uint32_t* nn, uint32_t n_rows, const FrameRows& rows, int64_t lo,
+                          int64_t hi, bool is_max, int decode, int width, uint8_t* dst, uint8_t* dst_valid);
 
 // ======================================================================================================== rj_setop.hip
 // ---- set operations (RJ_NODE_SETOP, rj_setop.hip): both children's rows in one relation of n_rows rows

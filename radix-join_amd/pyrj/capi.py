@@ -166,6 +166,8 @@ EXPORTS = [
     "rj_debug_parse_fp64",
     "rj_debug_sort_key",
     "rj_debug_sort_key_value",
+    "rj_debug_win_frame",
+    "rj_debug_win_ntile",
     "rj_debug_fsum",
     "rj_debug_map_eval",
     "rj_debug_partition_plan",
@@ -681,6 +683,27 @@ def sort_key_value(dtype: int, flags: int, key: int) -> int:
     if rc != 0:
         raise RjError(rc, "rj_debug_sort_key_value: bad type or flags")
     return int(bits.value)
+
+
+def win_frame(i: int, ps: int, pe: int, lo: int, hi: int):
+    """rj_debug_win_frame: the ROWS frame BETWEEN lo AND hi (signed offsets) of position i in the partition
+    [ps, pe], through the function the kernels call.  -> (a, b), or None for an empty frame."""
+    L = load()
+    L.rj_debug_win_frame.restype = C.c_int
+    L.rj_debug_win_frame.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    if not L.rj_debug_win_frame(i, ps, pe, lo, hi, C.byref(a), C.byref(b)):
+        return None
+    return int(a.value), int(b.value)
+
+
+def win_ntile(r: int, rows: int, buckets: int) -> int:
+    """rj_debug_win_ntile: the NTILE(buckets) bucket of the row with r rows of its partition (of `rows`
+    rows) in front of it, through the function the kernel calls; 0 for buckets < 1 or r >= rows."""
+    L = load()
+    L.rj_debug_win_ntile.restype = C.c_int64
+    L.rj_debug_win_ntile.argtypes = [C.c_uint64, C.c_uint64, C.c_int64]
+    return int(L.rj_debug_win_ntile(r, rows, buckets))
 
 
 def fsum(bits, is_null=None):

@@ -78,6 +78,11 @@ def agg_col(x):
 # rj_win_func and the RJ_WIN_OUT / RJ_WIN_FUNC / RJ_WIN_COL encoding of a window node's out_idx (the
 # bit layout of RJ_AGG_OUT)
 WIN_COL, WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX = range(9)
+# ... the functions that take an rj_win_arg (lo, hi): a ROWS frame as signed offsets from the current row,
+# LAG / LEAD's offset k or NTILE's bucket count in lo (9 .. 15 are not assigned)
+(WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_NTILE, WIN_ROWS_COUNT_STAR, WIN_ROWS_COUNT, WIN_ROWS_SUM, WIN_ROWS_MIN,
+ WIN_ROWS_MAX) = range(16, 26)
+WIN_UNBOUNDED_PRECEDING, WIN_UNBOUNDED_FOLLOWING = -(2**63), 2**63 - 1
 
 
 def win_out(func, col):
@@ -215,10 +220,13 @@ class WindowNode:
     lists [(column, flags)] as a SortNode's and either may be empty.  The PlanNode's output_attrs hold
     (RJ_WIN_OUT(func, column), result type) pairs; WIN_COL passes a child column through.  The frame is
     SQL's default: up to the current row's last peer with order keys, the whole partition without.  The
-    rows come out ordered by (part_keys, order_keys), promised only at the plan's root (include/rj.h)."""
+    rows come out ordered by (part_keys, order_keys), promised only at the plan's root (include/rj.h).
+    `args`: None, or one entry per output, (lo, hi) for a function from WIN_LAG on (its own ROWS frame as
+    signed offsets, LAG / LEAD's offset, NTILE's bucket count) and None for any other (RJ_WINDOW_ARGS)."""
     child: int
     part_keys: list
     order_keys: list
+    args: list = None
 
 
 @dataclass
@@ -314,9 +322,14 @@ class Plan:
     def new_window_node(self, child, part_keys, order_keys, outputs):
         """Window functions over PARTITION BY part_keys ORDER BY order_keys ([(column, flags)] each).
         outputs = [(func, column, result type)] with func one of WIN_COL ... WIN_MAX; the column of a
-        ranking function and of WIN_COUNT_STAR is 0."""
-        oa = [(win_out(f, c), t) for f, c, t in outputs]
-        self.nodes.append(PlanNode(WindowNode(child, [tuple(k) for k in part_keys], [tuple(k) for k in order_keys]), oa))
+        ranking function and of WIN_COUNT_STAR is 0.  A function from WIN_LAG on is (func, column, result
+        type, lo, hi): the ROWS frame as signed offsets (WIN_UNBOUNDED_PRECEDING / _FOLLOWING), LAG / LEAD's
+        offset or NTILE's bucket count in lo with hi = 0."""
+        oa = [(win_out(o[0], o[1]), o[2]) for o in outputs]
+        args = [(int(o[3]), int(o[4])) if len(o) == 5 else None for o in outputs]
+        if not any(a is not None for a in args):
+            args = None
+        self.nodes.append(PlanNode(WindowNode(child, [tuple(k) for k in part_keys], [tuple(k) for k in order_keys], args), oa))
         return len(self.nodes) - 1
 
     def new_map_node(self, child, program, outputs):
@@ -484,6 +497,10 @@ class rj_sort_key(C.Structure):
     _fields_ = [("column", C.c_int32), ("flags", C.c_int32)]
 
 
+class rj_win_arg(C.Structure):
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64)]
+
+
 class rj_column(C.Structure):
     _fields_ = [("type", C.c_int32), ("n_pages", C.c_uint64), ("pages", C.POINTER(C.c_void_p))]
 
@@ -595,6 +612,13 @@ def plan_to_c(plan: Plan, with_inputs: bool = True):
             nd.right = nk  # RJ_WINDOW_N_KEYS / RJ_WINDOW_KEYS / RJ_WINDOW_N_PART: the struct cannot grow
             nd.right_attr = C.addressof(karr) if nk else 0
             nd.left_attr = len(n.data.part_keys)
+            if any(win_func(a[0]) >= WIN_LAG for a in n.output_attrs):  # RJ_WINDOW_ARGS: read only then
+                wargs = list(n.data.args or []) + [None] * k
+                aarr = (rj_win_arg * max(1, k))()
+                for j in range(k):
+                    aarr[j].lo, aarr[j].hi = wargs[j] or (0, 0)
+                keep.append(aarr)
+                nd.base_table_id = C.addressof(aarr)
         elif isinstance(n.data, MapNode):
             from . import capi  # (capi imports this module)
 
